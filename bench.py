@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: Gbp of reads overlapped per second (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the overlap stage (seed collection -> sort -> chaining ->
 OverlapRange records on the host) over this rank's shard of the query reads, with
@@ -12,7 +12,9 @@ parameters).  For N > 1 the genome grows with N (weak scaling): reads shard by
 sequence id (flye_amd/dist.py), every rank holds the whole index, no data-path
 collective (SURVEY.md §8e option A).
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the JSON line: the headline figure, ms_per_step and
+`work` (what the timed passes counted).  --dump-outputs DIR writes what the last timed step returned to its caller
+as .npy files (dump_outputs()).  With --full the line also carries
   roofline     for the kernel that holds the device longest by itself (ranked in an untimed pass with the
                chaining stage serialised): algorithmic bytes (DESIGN.md "Algorithmic bytes") / its HIP-event
                time per launch in the timed region
@@ -69,6 +71,11 @@ def main():
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="weak: the genome (reads, index) grows with --gpus, per-rank queries stay ~fixed; strong: the "
                          "E. coli workload itself is split over the ranks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (records, offsets) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: the serialised ranking pass and the roofline figures, the CPU "
+                         "port, the compiled reference and its assemble stage (the --cpu-* / --no-* options below)")
     ap.add_argument("--cpu-sample-bp", type=float, default=250e6)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-cpu-reference", action="store_true",
@@ -80,6 +87,8 @@ def main():
     ap.add_argument("--no-assemble-stage", action="store_true",
                     help="skip the reference's whole `flye-modules assemble` stage (pure, and with the device seams)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     rank = int(os.environ.get("RANK", 0))
@@ -148,8 +157,9 @@ def main():
     # One more untimed pass with the chaining stage's size classes one after the other on the main stream: in the
     # timed passes they run side by side on three streams, where an event-bracketed duration includes the time a
     # kernel shares the chip with the others.  The serial pass says which kernel holds the device longest by itself.
+    # (--full only: the roofline figures are its only reader)
     serial_ktimes = {}
-    if rank == 0 and not os.environ.get("FLYE_BENCH_NO_SERIAL_PASS"):     # (the counter passes of tools/profile_round.sh want ONE pass)
+    if args.full and rank == 0:
         os.environ["FG_CHAIN_STREAMS"] = "1"
         step()
         serial_ktimes = {k_: v_ for k_, v_ in ctx.kernel_times().items() if not k_.startswith("host:")}
@@ -176,46 +186,15 @@ def main():
     elapsed = float(tt.item())
     total_bp = float(bp.item())
 
+    if args.dump_outputs:
+        dump_outputs(res, args.dump_outputs, rank, world)
+
     if rank == 0:
         value = total_bp * args.steps / elapsed / 1e9
         m = res.seed_hits / max(1, res.query_bp)
         d = res.dp_elements / max(1, res.query_bp)
         ovl = len(res.recs) / max(1, res.query_bp)
-        # dominant kernel of the timed region (HIP events on the library stream)
-        # (k_chain_dp and the sum of the ~28 k_sort_level launches are within a few per cent of each other:
-        # within 5 % of the maximum the kernel with the fewest launches is taken, so that the line does not
-        # flip between two kernels from run to run)
-        # dominance by the serial pass's exclusive times; duration and launch count from the timed region
-        if not serial_ktimes:
-            serial_ktimes = {k_: v_ for k_, v_ in ktimes.items() if not k_.startswith("host:")}
-        top = max(v_[0] for v_ in serial_ktimes.values())
-        dom_name = min((kv for kv in serial_ktimes.items() if kv[1][0] >= 0.95 * top), key=lambda kv: (kv[1][1], -kv[1][0]))[0]
-        dom_sec, dom_n = ktimes[dom_name]
-        launches_per_step = max(1, dom_n // args.steps)
-        avg_launch_s = dom_sec / max(1, dom_n)
         d_small = res.dp_elements_small / max(1, res.query_bp)
-        alg = algorithmic_bytes(dom_name, res.query_bp, m, d, ovl, d_small) / launches_per_step
-        achieved = alg / avg_launch_s / 1e9 if avg_launch_s > 0 else 0.0
-        # PMC traffic (FETCH_SIZE + WRITE_SIZE passes of tools/pmc_traffic.py) cannot be collected inside this
-        # process; the committed figure is used only while it was measured on THESE kernel sources and THIS
-        # detector configuration (stamp written by tools/pmc_traffic.py), otherwise traffic is null
-        traffic, traffic_note = None, "profiles/hbm_traffic.json absent"
-        prof = os.path.join(ROOT, "profiles", "hbm_traffic.json")
-        if os.path.exists(prof):
-            try:
-                tj = json.load(open(prof))
-                stamp = tj.get("_stamp", {})
-                if stamp.get("source_sha256") != kernel_source_digest():
-                    traffic_note = "stale: kernel sources changed since the PMC passes"
-                elif stamp.get("min_overlap") != det_min_ovlp:
-                    traffic_note = "stale: PMC passes ran another detector configuration"
-                else:
-                    traffic = tj.get(dom_name, {}).get("bytes_per_launch")
-                    traffic_note = "rocprofv3 --pmc FETCH_SIZE + WRITE_SIZE passes of this source state (profiles/)"
-            except Exception as e:  # noqa: BLE001
-                traffic_note = f"unreadable: {e}"
-        stages = stage_rooflines(serial_ktimes, res.query_bp, m, d, ovl, prof if os.path.exists(prof) and traffic_note.startswith("rocprofv3") else None)
-        dom_stage = max(stages.items(), key=lambda kv: kv[1]["exclusive_ms"])[0] if stages else None
         line = {
             "metric": "Gbp reads overlapped/sec", "value": round(value, 6), "unit": "Gbp/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -228,21 +207,6 @@ def main():
                        "sharding": (f"queries: reads by id over {world} ranks, no data-path collective; index: built sharded by "
                                     f"key range (counters, sort) + all-gather, then resident on every rank") if world > 1
                                    else "one rank: all queries, index built and resident on this GPU"},
-            "roofline": {"bound": "hbm", "kernel": dom_name, "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic,
-                         "traffic_source": traffic_note,
-                         "algorithmic_bytes_per_launch": int(alg), "avg_launch_ms": round(avg_launch_s * 1e3, 4),
-                         "launch": ("one level of the hit sort = the k_sort_level launch together with the k_sort_wide launch "
-                                    "for pieces above 16 k hits (levels 0-7 only) and the k_sort_route launch behind it, "
-                                    "bracketed by one pair of HIP events") if dom_name == "k_sort_level" else "one kernel launch",
-                         "dominant_by": "exclusive device time in an untimed pass with the chaining classes serialised "
-                                        "(FG_CHAIN_STREAMS=1); ms per pass there: " +
-                                        ", ".join(f"{k_} {v_[0] * 1e3:.1f}" for k_, v_ in
-                                                  sorted(serial_ktimes.items(), key=lambda kv: -kv[1][0])[:6])},
-            # whole stages (all launches of all their kernels against the stage's algorithmic bytes), so that a fraction
-            # cannot be moved by where a stage is cut into kernels; times = exclusive device time of the serialised pass
-            "roofline_stage": (dict(stages[dom_stage], stage=dom_stage, bound="hbm", peak=HBM_PEAK_GBS, unit="GB/s") if dom_stage else None),
-            "stages": stages,
             "work": {"seed_hits_per_bp": round(m, 4), "dp_elements_per_bp": round(d, 4),
                      "dp_elements_small_per_bp": round(d_small, 4),
                      "overlaps": int(len(res.recs)), "device_ms_per_step": round(dev_s / args.steps * 1e3, 3),
@@ -258,7 +222,9 @@ def main():
                      "read_gen_s": round(t_gen, 2),
                      "upload_s": round(t_upload, 3), "index_entries": int(st["index_entries"])},
         }
-        if world == 1 and not args.no_cpu:
+        if args.full:
+            line.update(roofline_figures(serial_ktimes, ktimes, res, args.steps, m, d, ovl, d_small, det_min_ovlp))
+        if args.full and world == 1 and not args.no_cpu:
             port = cpu_port(rs, cfg, vi, queries, args.cpu_sample_bp, det_min_ovlp)
             # parity on the timed workload itself: the sample's records must match
             port["sample_records_identical"] = bool(port.pop("_same")(res))
@@ -283,6 +249,100 @@ def main():
         print(json.dumps(line), flush=True)
     if world > 1:
         td.destroy_process_group()
+
+
+def roofline_figures(serial_ktimes, ktimes, res, steps, m, d, ovl, d_small, det_min_ovlp):
+    """--full: `roofline` (the dominant kernel of the pass against its algorithmic bytes), `stages` and
+    `roofline_stage` (whole stages), from the serialised pass's exclusive times and the timed region's launches."""
+    # dominant kernel of the timed region (HIP events on the library stream)
+    # (k_chain_dp and the sum of the ~28 k_sort_level launches are within a few per cent of each other:
+    # within 5 % of the maximum the kernel with the fewest launches is taken, so that the line does not
+    # flip between two kernels from run to run)
+    # dominance by the serial pass's exclusive times; duration and launch count from the timed region
+    top = max(v_[0] for v_ in serial_ktimes.values())
+    dom_name = min((kv for kv in serial_ktimes.items() if kv[1][0] >= 0.95 * top), key=lambda kv: (kv[1][1], -kv[1][0]))[0]
+    dom_sec, dom_n = ktimes[dom_name]
+    launches_per_step = max(1, dom_n // steps)
+    avg_launch_s = dom_sec / max(1, dom_n)
+    alg = algorithmic_bytes(dom_name, res.query_bp, m, d, ovl, d_small) / launches_per_step
+    achieved = alg / avg_launch_s / 1e9 if avg_launch_s > 0 else 0.0
+    # PMC traffic (FETCH_SIZE + WRITE_SIZE passes of tools/pmc_traffic.py) cannot be collected inside this
+    # process; the committed figure is used only while it was measured on THESE kernel sources and THIS
+    # detector configuration (stamp written by tools/pmc_traffic.py), otherwise traffic is null
+    traffic, traffic_note = None, "profiles/hbm_traffic.json absent"
+    prof = os.path.join(ROOT, "profiles", "hbm_traffic.json")
+    if os.path.exists(prof):
+        try:
+            tj = json.load(open(prof))
+            stamp = tj.get("_stamp", {})
+            if stamp.get("source_sha256") != kernel_source_digest():
+                traffic_note = "stale: kernel sources changed since the PMC passes"
+            elif stamp.get("min_overlap") != det_min_ovlp:
+                traffic_note = "stale: PMC passes ran another detector configuration"
+            else:
+                traffic = tj.get(dom_name, {}).get("bytes_per_launch")
+                traffic_note = "rocprofv3 --pmc FETCH_SIZE + WRITE_SIZE passes of this source state (profiles/)"
+        except Exception as e:  # noqa: BLE001
+            traffic_note = f"unreadable: {e}"
+    stages = stage_rooflines(serial_ktimes, res.query_bp, m, d, ovl, prof if os.path.exists(prof) and traffic_note.startswith("rocprofv3") else None)
+    dom_stage = max(stages.items(), key=lambda kv: kv[1]["exclusive_ms"])[0] if stages else None
+    return {
+        "roofline": {"bound": "hbm", "kernel": dom_name, "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS,
+                     "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic,
+                     "traffic_source": traffic_note,
+                     "algorithmic_bytes_per_launch": int(alg), "avg_launch_ms": round(avg_launch_s * 1e3, 4),
+                     "launch": ("one level of the hit sort = the k_sort_level launch together with the k_sort_wide launch "
+                                "for pieces above 16 k hits (levels 0-7 only) and the k_sort_route launch behind it, "
+                                "bracketed by one pair of HIP events") if dom_name == "k_sort_level" else "one kernel launch",
+                     "dominant_by": "exclusive device time in an untimed pass with the chaining classes serialised "
+                                    "(FG_CHAIN_STREAMS=1); ms per pass there: " +
+                                    ", ".join(f"{k_} {v_[0] * 1e3:.1f}" for k_, v_ in
+                                              sorted(serial_ktimes.items(), key=lambda kv: -kv[1][0])[:6])},
+        # whole stages (all launches of all their kernels against the stage's algorithmic bytes), so that a fraction
+        # cannot be moved by where a stage is cut into kernels; times = exclusive device time of the serialised pass
+        "roofline_stage": (dict(stages[dom_stage], stage=dom_stage, bound="hbm", peak=HBM_PEAK_GBS, unit="GB/s") if dom_stage else None),
+        "stages": stages,
+    }
+
+
+DUMP_QUERIES = 2048             # queries of the pass whose records --dump-outputs writes in full
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _segments(off, pick):
+    """Indices of the elements of segments `pick` of the offsets `off` (CSR), segment after segment."""
+    lo, n = off[pick], off[pick + 1] - off[pick]
+    start = np.concatenate([[0], np.cumsum(n)[:-1]]).astype(np.int64)
+    return np.repeat(lo - start, n) + np.arange(int(n.sum()), dtype=np.int64)
+
+
+def dump_outputs(res, out_dir, rank=0, world=1):
+    """--dump-outputs: what the last timed step returned to its caller (gpu.OverlapResult), as out_dir/<name>.npy, so
+    that two builds can be compared output for output on the same seeded inputs.  For every query of the pass: its
+    record count and divergence-sample count; for a fixed, seeded sample of DUMP_QUERIES queries: their ids and every
+    field of their records and their divergence samples (the float fields as float32, bit for bit; the integers as
+    float64, exactly).  Ranks > 1 of a multi-rank run prefix their files with rank<r>_ and share the sample size."""
+    os.makedirs(out_dir, exist_ok=True)
+    qoff = res.query_off.astype(np.int64)
+    soff = res.stat_off.astype(np.int64)
+    nq = len(qoff) - 1
+    rng = np.random.default_rng(1000 + rank)
+    pick = np.sort(rng.choice(nq, size=min(nq, max(1, DUMP_QUERIES // world)), replace=False))
+    while True:
+        ri, si = _segments(qoff, pick), _segments(soff, pick)
+        out = {"records_per_query": np.diff(qoff).astype(np.float64),
+               "div_stats_per_query": np.diff(soff).astype(np.float64),
+               "sample_queries": np.asarray(res.query_ids, np.int64)[pick].astype(np.float64)}
+        for f in res.recs.dtype.names:
+            col = res.recs[f][ri]
+            out["recs_" + f] = col if col.dtype == np.float32 else col.astype(np.float64)
+        out["div_stats"] = res.stats[si].astype(np.float32)
+        if sum(a.nbytes for a in out.values()) <= DUMP_MAX_BYTES // world or len(pick) == 1:
+            break
+        pick = pick[::2]
+    pre = f"rank{rank}_" if world > 1 else ""
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, pre + name + ".npy"), a)
 
 
 STAGES = {

@@ -3,7 +3,8 @@ import os
 import numpy as np
 import pytest
 
-REF_CFG = "/root/reference/flye/config/bin_cfg"
+# the reference's shipped config files (Flye 2.8.1 flye/config/bin_cfg/), stored verbatim as settings fixtures
+REF_CFG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bin_cfg")
 
 
 def _parse(path, out):
@@ -19,7 +20,6 @@ def _parse(path, out):
     return out
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG), reason="reference tree not present (GPU box)")
 @pytest.mark.parametrize("name", ["raw", "corrected", "hifi", "subasm"])
 def test_presets_equal_reference_cfg_files(name):
     from flye_amd import config
@@ -31,7 +31,6 @@ def test_presets_equal_reference_cfg_files(name):
         assert ref[k] == v, (name, k, ref[k], v)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG), reason="reference tree not present (GPU box)")
 @pytest.mark.parametrize("name", ["raw", "corrected", "hifi", "subasm"])
 def test_assemble_stage_cfg_equals_reference_cfg_files(name, tmp_path):
     """the cfg file written for the reference's assemble program holds the reference's values for every

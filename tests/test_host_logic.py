@@ -27,7 +27,7 @@ def test_shard_queries_partition():
     assert all(np.all(dist.owner_of((x - first) // 2, 8) == r) for r, x in enumerate(ids))
 
 
-def test_synth_is_deterministic():
+def test_synth_is_deterministic(built):
     from flye_amd import synth
     a = synth.simulate(seed=9, genome_len=20000, coverage=5, kind="ont_raw")
     b = synth.simulate(seed=9, genome_len=20000, coverage=5, kind="ont_raw")
@@ -61,3 +61,54 @@ def test_bench_byte_model_and_stage_attribution():
     assert abs(total - (16.25 + 44.0 * m + 20.0 * d + 44.0 * ovl) * bp) <= 3
     assert st["hit_sort"]["kernels"] == ["k_sort_lds", "k_sort_level"] and abs(st["hit_sort"]["exclusive_ms"] - 3.0) < 1e-9
     assert "traffic" not in st["chain"]
+
+
+def test_bench_dump_outputs_sample(tmp_path):
+    """bench.py --dump-outputs: per-query counts of every query, and every field of the records and divergence
+    samples of a fixed, seeded sample of the queries, exactly (integers as float64, floats bit for bit), the same
+    files from run to run and within the size budget."""
+    import types
+    import bench
+    from flye_amd import gpu
+    rng = np.random.default_rng(7)
+    nq = 5000
+    qoff = np.concatenate([[0], np.cumsum(rng.integers(0, 40, nq))]).astype(np.uint64)
+    soff = np.concatenate([[0], np.cumsum(rng.integers(0, 4, nq))]).astype(np.uint64)
+    recs = np.zeros(int(qoff[-1]), gpu.REC_DTYPE)
+    for f in recs.dtype.names:
+        recs[f] = rng.random(len(recs)) if f == "seq_divergence" else rng.integers(0, 1 << 24, len(recs))
+    res = types.SimpleNamespace(query_off=qoff, stat_off=soff, recs=recs, stats=rng.random(int(soff[-1])).astype(np.float32),
+                                query_ids=np.arange(1, 2 * nq, 2, dtype=np.uint32))
+    bench.dump_outputs(res, str(tmp_path / "a"))
+    bench.dump_outputs(res, str(tmp_path / "b"))
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == sorted(p.name for p in (tmp_path / "b").iterdir())
+    assert {"records_per_query.npy", "div_stats_per_query.npy", "sample_queries.npy", "div_stats.npy"} <= set(names)
+    assert sum((tmp_path / "a" / n).stat().st_size for n in names) <= bench.DUMP_MAX_BYTES
+    out = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    for n in names:
+        assert out[n[:-4]].dtype in (np.float32, np.float64)
+        assert np.array_equal(out[n[:-4]], np.load(tmp_path / "b" / n))
+    assert np.array_equal(out["records_per_query"], np.diff(qoff.astype(np.int64)))
+    pick = (out["sample_queries"].astype(np.int64) - 1) // 2
+    assert len(pick) == bench.DUMP_QUERIES and np.all(np.diff(pick) > 0)
+    ri = np.concatenate([np.arange(qoff[i], qoff[i + 1]) for i in pick]).astype(np.int64)
+    for f in recs.dtype.names:
+        assert np.array_equal(out["recs_" + f], recs[f][ri])
+    assert out["recs_seq_divergence"].dtype == np.float32
+    si = np.concatenate([np.arange(soff[i], soff[i + 1]) for i in pick]).astype(np.int64)
+    assert np.array_equal(out["div_stats"], res.stats[si])
+
+
+def test_bench_options():
+    """bench.py has --steps, --warmup, --dump-outputs and --full (the legs beyond the headline figure), and refuses
+    a run of no timed step before it touches a device."""
+    import os
+    import subprocess
+    import sys
+    here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    h = subprocess.run([sys.executable, os.path.join(here, "bench.py"), "--help"], capture_output=True, text=True, check=True)
+    for opt in ("--steps", "--warmup", "--dump-outputs", "--full"):
+        assert opt in h.stdout
+    r = subprocess.run([sys.executable, os.path.join(here, "bench.py"), "--steps", "0"], capture_output=True, text=True)
+    assert r.returncode == 2 and "--steps" in r.stderr

@@ -1,5 +1,5 @@
-"""Live check of the oracle against the compiled reference (only where
-/root/reference and oracle/_ref exist, i.e. the build container).  Minimizer
+"""Live check of the oracle against the compiled reference (only where build()
+could compile oracle/_ref, i.e. where the reference sources are).  Minimizer
 configs only: the reference's raw-read build spends ~90 s in its 8 GiB flat
 counter, the raw path is covered by the golden vectors."""
 import os
@@ -9,8 +9,10 @@ import pytest
 
 from oracle import oracle as O
 
-pytestmark = pytest.mark.skipif(not (O.have_ref() and os.path.isdir("/root/reference/flye/config/bin_cfg")),
-                                reason="reference build not available")
+pytestmark = pytest.mark.skipif(not O.have_ref(), reason="reference build not available")
+
+# the reference's shipped config files, stored as settings fixtures (tests/test_config.py)
+REF_CFG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bin_cfg")
 
 
 @pytest.mark.parametrize("preset,kind,opts", [
@@ -21,7 +23,7 @@ def test_oracle_equals_reference(built, tmp_path, preset, kind, opts):
     from flye_amd import config, synth
     fa = str(tmp_path / "r.fasta")
     rs = synth.simulate(seed=4242, genome_len=30_000, coverage=20, kind=kind, fasta_path=fa).filter_min_len(1000)
-    info = O.run_ref(fa, config="/root/reference/flye/config/bin_cfg/" + config.CFG_FILES[preset], threads=4,
+    info = O.run_ref(fa, config=os.path.join(REF_CFG, config.CFG_FILES[preset]), threads=4,
                      min_read_len=1000, index_out=str(tmp_path / "i.txt"), ovlp_out=str(tmp_path / "o.txt"),
                      rc_queries=opts.get("rc_queries", False), max_overlaps=opts.get("max_overlaps", 0))
     cfg = config.preset(preset)

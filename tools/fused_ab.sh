@@ -2,7 +2,7 @@
 # bench pass with the one-kernel small-group chaining path off / on at several caps
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 run() {
-python3 $ROOT/bench.py --no-cpu --steps 5 --warmup 1 2>/dev/null | python3 -c "
+python3 $ROOT/bench.py --full --no-cpu --steps 5 --warmup 1 2>/dev/null | python3 -c "
 import json,sys
 j=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=j['work']['kernel_ms_per_step']
