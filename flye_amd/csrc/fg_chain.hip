@@ -136,7 +136,8 @@ __global__ void k_group_list(u64 nGroups, u64 nHits, const u64* __restrict__ gro
 		}
 		f[t] = ok && n <= fusedMax;				// the whole chaining stage in one kernel (k_chain_small)
 		a[t] = ok && n > fusedMax && n <= bigMin;
-		b[t] = ok && n > bigMin;	// groups that k_group_prep handles in global memory
+		b[t] = ok && n > bigMin && n > fusedMax;	// groups that k_group_prep handles in global memory (never one that
+												// k_chain_small takes: FG_FUSED_CAP > PREP_CAP)
 		none[t] = false;
 	}
 	append2_multi(a, b, (u32)g0, list, listBig, counts);
@@ -178,7 +179,7 @@ __global__ void k_dp_list(u64 nGroups, const u32* __restrict__ dpSize, u32 hugeM
 		const u32 n = g0 + t < nGroups ? dpSize[g0 + t] : 0u;
 		a[t] = n > doneMax && n <= FIN_CAP_S;
 		b[t] = n > FIN_CAP_S && n > doneMax && n <= hugeMin;
-		h[t] = n > hugeMin;
+		h[t] = n > hugeMin && n > FIN_CAP_S && n > doneMax;	// disjoint from both classes above whatever FG_CHAIN_HUGE_MIN says
 		none[t] = false;
 	}
 	append2_multi(a, b, (u32)g0, listSmall, listMid, counts);

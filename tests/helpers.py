@@ -178,3 +178,26 @@ def sub_index(ex, rs, reads, k):
     pos = np.repeat(off[sel] - new_off[:-1], cnt) + np.arange(int(new_off[-1]), dtype=np.int64)
     return O.IndexExport(np.ascontiguousarray(ex.keys[sel]), new_off.astype(np.uint64),
                          np.ascontiguousarray(ex.entries[pos]), ex.repetitive)
+
+
+# ---- device against oracle, record for record -------------------------------------------------------
+def check_overlaps_equal(gres, ores, keep_aln, counts=True):
+    """Everything a device OverlapResult must share with the oracle's on the same index and call:
+    records (text form incl. the divergence bits and, with kmerMatches, their count and digest), the
+    per-query offsets, the divergence samples, the fields outside the text form, kmerMatches element by
+    element, the work counters.  ``counts`` = False: the DP counters are not compared (with a
+    max_overlaps limit the reference stops visiting groups early)."""
+    assert gres.lines() == ores.lines()
+    if keep_aln:
+        assert np.array_equal(gres.match_off, ores.match_off)
+        assert np.array_equal(gres.matches, ores.matches)
+    else:
+        assert gres.match_off is None
+    assert np.array_equal(gres.query_off, ores.query_off)
+    assert np.array_equal(gres.stats.view(np.uint32), ores.stats.view(np.uint32))
+    for f in ("chain_length", "filtered_positions", "edit_distance", "hpc_len_cur", "hpc_len_ext"):
+        assert np.array_equal(gres.recs[f], ores.recs[f]), f
+    assert (gres.query_kmers, gres.seed_hits) == (ores.query_kmers, ores.seed_hits)
+    if counts:
+        assert (gres.dp_groups, gres.dp_elements) == (ores.dp_groups, ores.dp_elements)
+        assert 0 <= gres.dp_elements_small <= gres.dp_elements      # the one-kernel chaining class's share

@@ -1,5 +1,7 @@
 #!/bin/bash
 # bench pass with the one-kernel small-group chaining path off / on at several caps
+# (caps above 320 are valid since the size classes were made disjoint: a group of 321..cap hits runs in
+# k_chain_small only, not also through k_group_prep)
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 run() {
 python3 $ROOT/bench.py --full --no-cpu --steps 5 --warmup 1 2>/dev/null | python3 -c "
