@@ -391,6 +391,7 @@ int fg_clear_index(fg_ctx* c)
 		c->indexBuilt = false;
 		c->indexBuild.reset();
 		c->gathering = false;
+		c->shardWorld = 1; c->shardRank = 0;
 		c->gKeys.release(); c->gKeyOff.release(); c->gEntries.release(); c->gRepKeys.release();
 		c->dKeys.release(); c->dKeyOff.release(); c->dEntries.release(); c->dRepKeys.release();
 		c->dTable.release(); c->dIndexedBits.release();
@@ -416,6 +417,79 @@ int fg_export_index(fg_ctx* c, uint64_t* n_keys, uint64_t* n_entries, uint64_t* 
 	});
 }
 
+static int checkOverlapArgs(const fg_ctx* c, const struct fg_detector_params* p, const uint32_t* query_ids, uint32_t n_queries,
+							int32_t max_overlaps)
+{
+	if (p->partition_bad_mappings && max_overlaps != 0) return FG_ERR_UNSUPPORTED;
+	if (p->max_jump <= 0 || p->min_overlap <= 0 || max_overlaps < 0) return FG_ERR_ARG;
+	const u32 base = c->hasQ ? c->qFirstId : c->firstId;
+	const u32 cnt = c->hasQ ? c->nQReads : c->nReads;
+	for (u32 i = 0; i < n_queries; ++i)
+		if (query_ids[i] < base || query_ids[i] - base >= 2 * cnt) return FG_ERR_ARG;
+	return FG_OK;
+}
+
+int fg_index_keep_targets(fg_ctx* c, uint32_t world, uint32_t rank, uint64_t* n_entries_kept)
+{
+	if (!c) return FG_ERR_ARG;
+	return guarded(c, [&]()
+	{
+		HIP_CHECK(hipSetDevice(c->device));
+		u64 kept = 0;
+		fgIndexKeepTargets(c, world, rank, &kept);
+		if (n_entries_kept) *n_entries_kept = kept;
+	});
+}
+
+int fg_index_shard(const fg_ctx* c, uint32_t* world, uint32_t* rank)
+{
+	if (!c) return FG_ERR_ARG;
+	if (world) *world = c->shardWorld;
+	if (rank) *rank = c->shardRank;
+	return FG_OK;
+}
+
+int fg_probe_hits(fg_ctx* c, const uint32_t* query_ids, uint32_t n_queries, uint64_t* hit_counts,
+				  const struct fg_seed_hit** d_hits, uint64_t* n_hits)
+{
+	if (!c || !d_hits || !n_hits || (n_queries && (!query_ids || !hit_counts))) return FG_ERR_ARG;
+	*d_hits = nullptr; *n_hits = 0;
+	if (!c->indexBuilt) return FG_ERR_STATE;
+	{
+		const u32 base = c->hasQ ? c->qFirstId : c->firstId;
+		const u32 cnt = c->hasQ ? c->nQReads : c->nReads;
+		for (u32 i = 0; i < n_queries; ++i)
+			if (query_ids[i] < base || query_ids[i] - base >= 2 * cnt) return FG_ERR_ARG;
+	}
+	return guarded(c, [&]()
+	{
+		HIP_CHECK(hipSetDevice(c->device));
+		fgProbeHits(c, query_ids, n_queries, (u64*)hit_counts, d_hits, (u64*)n_hits);
+	});
+}
+
+int fg_overlaps_from_hits(fg_ctx* c, const struct fg_detector_params* p, const uint32_t* query_ids, uint32_t n_queries,
+						  int32_t max_overlaps, uint8_t force_local, uint32_t n_src, const uint64_t* hit_counts,
+						  const struct fg_seed_hit* d_hits, struct fg_overlap_batch* out)
+{
+	if (!c || !p || !out || (n_queries && !query_ids) || n_src == 0 || (n_queries && !hit_counts)) return FG_ERR_ARG;
+	memset(out, 0, sizeof(*out));
+	if (!c->indexBuilt) return FG_ERR_STATE;
+	const int chk = checkOverlapArgs(c, p, query_ids, n_queries, max_overlaps);
+	if (chk != FG_OK) return chk;
+	const int rc = guarded(c, [&]()
+	{
+		HIP_CHECK(hipSetDevice(c->device));
+		fgOverlapsFromHits(c, p, query_ids, n_queries, max_overlaps, force_local, n_src, (const u64*)hit_counts, d_hits, out);
+	});
+	if (rc != FG_OK)
+	{
+		BatchOwner::release((BatchOwner*)out->owner_);
+		memset(out, 0, sizeof(*out));
+	}
+	return rc;
+}
+
 int fg_overlaps(fg_ctx* c, const struct fg_detector_params* p, const uint32_t* query_ids,
 				uint32_t n_queries, int32_t max_overlaps, uint8_t force_local,
 				struct fg_overlap_batch* out)
@@ -423,14 +497,14 @@ int fg_overlaps(fg_ctx* c, const struct fg_detector_params* p, const uint32_t* q
 	if (!c || !p || !out || (n_queries && !query_ids)) return FG_ERR_ARG;
 	memset(out, 0, sizeof(*out));
 	if (!c->indexBuilt) return FG_ERR_STATE;
-	if (p->partition_bad_mappings && max_overlaps != 0) return FG_ERR_UNSUPPORTED;
-	if (p->max_jump <= 0 || p->min_overlap <= 0 || max_overlaps < 0) return FG_ERR_ARG;
+	if (c->shardWorld != 1)
 	{
-		const u32 base = c->hasQ ? c->qFirstId : c->firstId;
-		const u32 cnt = c->hasQ ? c->nQReads : c->nReads;
-		for (u32 i = 0; i < n_queries; ++i)
-			if (query_ids[i] < base || query_ids[i] - base >= 2 * cnt) return FG_ERR_ARG;
+		c->lastError = "the index holds the entries of 1/" + std::to_string(c->shardWorld) + " of the target reads "
+			"(fg_index_keep_targets): collect seed hits with fg_probe_hits and compute overlaps with fg_overlaps_from_hits";
+		return FG_ERR_STATE;
 	}
+	const int chk = checkOverlapArgs(c, p, query_ids, n_queries, max_overlaps);
+	if (chk != FG_OK) return chk;
 	const int rc = guarded(c, [&]()
 	{
 		HIP_CHECK(hipSetDevice(c->device));

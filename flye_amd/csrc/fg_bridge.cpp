@@ -521,6 +521,10 @@ int fgb_create(fgb_container** out, fg_ctx* ctx, const struct fg_detector_params
 			   uint32_t max_batch, uint32_t linger_us)
 {
 	if (!out || !ctx || !params) return FG_ERR_ARG;
+	// an index restricted to one shard of the targets (fg_index_keep_targets) answers through fg_probe_hits /
+	// fg_overlaps_from_hits only: no overlaps against 1/world of the targets
+	uint32_t world = 1;
+	if (fg_index_shard(ctx, &world, nullptr) != FG_OK || world != 1) return FG_ERR_STATE;
 	try
 	{
 		std::unique_ptr<fgb_container> c(new fgb_container);

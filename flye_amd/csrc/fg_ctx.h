@@ -321,6 +321,9 @@ struct fg_ctx {
 	bool tableWide = false;
 	FgTable table{};
 	DevBuf<u32> dIndexedBits;	// one bit per forward k-mer position: contributes an entry
+	// option B (fg_index_keep_targets): the lists hold only the entries of target reads i with i % shardWorld ==
+	// shardRank; the indexed bits of the other reads are cleared.  1 / 0 = the whole index
+	u32 shardWorld = 1, shardRank = 0;
 
 	// second lane of fg_overlaps: a context of its own scratch, streams and timers whose read / index / probe buffers
 	// are views of this one's (fg_overlap.hip: sub-ranges of a call's queries run on two lanes side by side)
@@ -356,6 +359,10 @@ struct fg_ctx {
 	DevBuf<u32> dGroupExt, dGroupFirstCur, dGroupLastCur;
 	DevBuf<uint8_t> dGroupExtSorted;	// written by k_group_prep: the DP runs in extPos order (overlap.cpp:268-275)
 	DevBuf<u32> dTmp32;
+	// option B: the seed hits fg_probe_hits hands out; the receiver's run table, gather slots and error flag
+	DevBuf<fg_seed_hit> dSeedHits;
+	DevBuf<u64> dRecvRun, dRecvIdx;
+	DevBuf<u32> dRecvErr;
 	DevBuf<u64> dCntA, dCntB, dGroupCnt, dGroupOff, dPrimCnt, dPrimOff, dDpGroups, dDpElems;
 	DevBuf<u32> dPrimFlag, dDpSize, dListSmall, dListBig, dListDp, dListFused, dListCnt;
 	DevBuf<u32> dCur, dExt;		// (cur, ext) columns of the groups in DP order
@@ -642,5 +649,19 @@ void fgKswAlign(fg_ctx* c, u32 nPairs, const uint8_t* trg, const u64* trgOff, co
 				std::vector<u64>& runOff, std::vector<u32>& runs);
 void fgDebugSortPairs(fg_ctx* c, u64* keys, u32* vals, const u64* segOff, u32 nSeg);
 void fgDebugEditDistances(fg_ctx* c, u32 nPairs, int useHpc, i32* outDist, i32* outLenA, i32* outLenB);
+// option B: seed hits gathered from index shards, as the overlap stage takes them in place of its own seed
+// expansion.  Per query qi of the call and source s: the run of hits[runStart[qi * nSrc + s] ..] of runLen[..]
+// hits (any order inside a run); total[qi] = the query's hits over all sources
+struct RecvHits {
+	u32 nSrc;
+	const u64* runStart;
+	const u64* runLen;
+	const u64* total;
+	const fg_seed_hit* hits;	// device
+};
 void fgOverlaps(fg_ctx* c, const fg_detector_params* p, const u32* queryIds, u32 nq, i32 maxOverlaps,
-				uint8_t forceLocal, fg_overlap_batch* out);
+				uint8_t forceLocal, fg_overlap_batch* out, const RecvHits* recv = nullptr);
+void fgIndexKeepTargets(fg_ctx* c, u32 world, u32 rank, u64* nKept);
+void fgProbeHits(fg_ctx* c, const u32* queryIds, u32 nq, u64* hitCounts, const fg_seed_hit** dHits, u64* nHits);
+void fgOverlapsFromHits(fg_ctx* c, const fg_detector_params* p, const u32* queryIds, u32 nq, i32 maxOverlaps,
+						uint8_t forceLocal, u32 nSrc, const u64* hitCounts, const fg_seed_hit* dHits, fg_overlap_batch* out);

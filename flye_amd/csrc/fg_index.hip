@@ -816,6 +816,7 @@ void clearIndex(fg_ctx* c)
 {
 	c->indexBuilt = false;
 	c->gathering = false;
+	c->shardWorld = 1; c->shardRank = 0;
 	c->gKeys.release(); c->gKeyOff.release(); c->gEntries.release(); c->gRepKeys.release();
 	c->dKeys.release(); c->dKeyOff.release(); c->dEntries.release(); c->dRepKeys.release();
 	c->dTable.release(); c->dIndexedBits.release();
@@ -1443,6 +1444,7 @@ void fgIndexGatherBegin(fg_ctx* c, u64 nKeys, u64 nEntries, u64 nRep, u64** full
 	if (!c->indexBuilt || c->gathering) throw FgError{FG_ERR_STATE, "gather needs a finished piece (fg_index_finish)"};
 	c->timer.reset();
 	c->indexBuilt = false;
+	c->shardWorld = 1; c->shardRank = 0;
 	c->dTable.release(); c->dIndexedBits.release();
 	c->gKeys.swap(c->dKeys); c->gKeyOff.swap(c->dKeyOff); c->gEntries.swap(c->dEntries); c->gRepKeys.swap(c->dRepKeys);
 	c->gNKeys = c->nKeys; c->gNEntries = c->nEntries; c->gNRep = c->nRep;
@@ -1462,5 +1464,99 @@ void fgIndexGatherEnd(fg_ctx* c, float sampleRate)
 	c->sampleRate = sampleRate;
 	checkCsr(c);
 	fgIndexLookupStructures(c, false);
+	c->timer.collect();
+}
+
+// ---- option B: the index restricted to the entries of the target reads a rank owns -----------------
+// After any complete index.  Per key, the entries whose target read index ((record) >> 1) % world == rank are counted,
+// the counts scanned into the new list offsets, and every list copied -- in its ascending order -- into an entry array
+// of exactly the kept size; the old array is freed (DevBuf grows only: the swap is the deliberate step that gives the
+// memory back).  Keys, the lookup table (it stores key indices; the counts come from the rewritten offsets), the
+// repetitive k-mers and the sample rate stay.  The "owns an entry" bits of the reads this rank does not own are
+// cleared: a query's own entry is then in this shard's list exactly when the bit is set (k_probe's self flag).
+namespace {
+
+__global__ void k_keep_count(const u64* __restrict__ keyOff, u64 nKeys, const u64* __restrict__ entries, u32 world, u32 rank,
+							 u64* __restrict__ cnt)
+{
+	const u64 j = (u64)blockIdx.x * WG + threadIdx.x;
+	if (j > nKeys) return;
+	u64 n = 0;
+	if (j < nKeys)
+		for (u64 e = keyOff[j]; e < keyOff[j + 1]; ++e) n += (u32)((entries[e] >> 33) % world) == rank;
+	cnt[j] = n;		// cnt[nKeys] = 0: the exclusive scan's last element is the kept total
+}
+
+__global__ void k_keep_copy(const u64* __restrict__ keyOff, u64 nKeys, const u64* __restrict__ entries, u32 world, u32 rank,
+							const u64* __restrict__ newOff, u64* __restrict__ out)
+{
+	const u64 j = (u64)blockIdx.x * WG + threadIdx.x;
+	if (j >= nKeys) return;
+	u64 o = newOff[j];
+	for (u64 e = keyOff[j]; e < keyOff[j + 1]; ++e)
+	{
+		const u64 v = entries[e];
+		if ((u32)((v >> 33) % world) == rank) out[o++] = v;
+	}
+}
+
+// one block per read this rank does not own: its bits [kmerOff[r], kmerOff[r + 1]) cleared (words at the read's
+// ends are shared with the neighbours: atomic AND)
+__global__ void k_keep_bits(const u64* __restrict__ kmerOff, u32 world, u32 rank, u32* __restrict__ bits)
+{
+	const u32 r = blockIdx.x;
+	if (r % world == rank) return;
+	const u64 a = kmerOff[r], b = kmerOff[r + 1];
+	if (b <= a) return;
+	for (u64 w = (a >> 5) + threadIdx.x; w <= ((b - 1) >> 5); w += WG)
+	{
+		const u64 lo = a > (w << 5) ? a : (w << 5), hi = b < (w << 5) + 32 ? b : (w << 5) + 32;
+		const u32 n = (u32)(hi - lo), sh = (u32)(lo & 31);
+		const u32 mask = (n == 32 ? 0xFFFFFFFFu : ((1u << n) - 1u)) << sh;
+		atomicAnd(&bits[w], ~mask);
+	}
+}
+
+} // namespace
+
+void fgIndexKeepTargets(fg_ctx* c, u32 world, u32 rank, u64* nKept)
+{
+	if (world == 0 || rank >= world) throw FgError{FG_ERR_ARG, "keep_targets: rank must be below world"};
+	if (!c->indexBuilt || c->gathering) throw FgError{FG_ERR_STATE, "keep_targets needs a complete index (build, gather or import)"};
+	if (nKept) *nKept = c->nEntries;
+	if (world == 1) return;
+	if (c->shardWorld != 1)
+	{
+		if (c->shardWorld == world && c->shardRank == rank) return;
+		throw FgError{FG_ERR_STATE, "keep_targets: the index is already restricted to another shard"};
+	}
+	hipStream_t s = c->stream;
+	c->timer.reset();
+	const u64 nKeys = c->nKeys;
+	{
+		DevBuf<u64> cnt, newOff, scratch;
+		cnt.alloc(nKeys + 1); newOff.alloc(nKeys + 1);
+		scratch.alloc(fgprim::scanScratchElems(nKeys + 1));
+		{ ScopedK t(c->timer, "k_keep_count");
+		  hipLaunchKernelGGL(k_keep_count, gridFor(nKeys + 1), WG, 0, s, c->dKeyOff.p, nKeys, c->dEntries.p, world, rank, cnt.p); }
+		{ ScopedK t(c->timer, "k_keep_scan");
+		  fgprim::scan<u64>(s, cnt.p, newOff.p, nKeys + 1, false, scratch.p); }
+		const u64 kept = fetch(c, newOff.p + nKeys);
+		DevBuf<u64> ent;
+		ent.alloc(kept);
+		{ ScopedK t(c->timer, "k_keep_copy");
+		  if (nKeys) hipLaunchKernelGGL(k_keep_copy, gridFor(nKeys), WG, 0, s, c->dKeyOff.p, nKeys, c->dEntries.p, world, rank, newOff.p, ent.p); }
+		if (c->nReads && c->dIndexedBits.p)
+		{ ScopedK t(c->timer, "k_keep_bits");
+		  hipLaunchKernelGGL(k_keep_bits, c->nReads, WG, 0, s, c->dKmerOff.p, world, rank, c->dIndexedBits.p); }
+		HIP_CHECK(hipStreamSynchronize(s));
+		c->dEntries.swap(ent);		// the full array leaves with `ent`
+		c->dKeyOff.swap(newOff);
+		c->nEntries = kept;
+	}
+	// the table reads the list bounds through this pointer
+	c->table.keyOff = (const unsigned long long*)c->dKeyOff.p;
+	c->shardWorld = world; c->shardRank = rank;
+	if (nKept) *nKept = c->nEntries;
 	c->timer.collect();
 }

@@ -257,7 +257,7 @@ __global__ void k_probe_count(const u64* __restrict__ qKmerOff, const u64* __res
 // KT = u64: key = extId << 32 | curPos.  KT = u32 (when record index and position fit 32 bits
 // together): key = record << curBits | curPos -- same order, a third less sort traffic.
 // KT = PK: one 64-bit record per hit (fg_ctx.h), no value array.  Consumers read any of the
-// three through HitKeyView<KT>.
+// three through HitKeyView<KT>.  KT = fg_seed_hit: the (curPos, extPos, extId) tuples fg_probe_hits exports.
 #ifndef FILL_ITEMS
 #define FILL_ITEMS 4
 #endif
@@ -339,7 +339,9 @@ __global__ void k_fill(const u32* __restrict__ query, const i32* __restrict__ le
 			u32 srec = (u32)(e >> 32);
 			i32 spos = (i32)(u32)e;
 			if (so & FLAG_FLIP) { spos = len[srec >> 1] - spos - k; srec ^= 1u; }
-			if constexpr (std::is_same<KT, PK>::value)
+			if constexpr (std::is_same<KT, fg_seed_hit>::value)
+				hitKey[hbase + o] = fg_seed_hit{p0 + (i32)t, spos, firstId + srec};	// option B's export form (fg_probe_hits)
+			else if constexpr (std::is_same<KT, PK>::value)
 				hitKey[hbase + o] = PK(((u64)srec << (curBits + FG_PK_VALBITS)) | ((u64)(u32)(p0 + (i32)t) << FG_PK_VALBITS) |
 									   (u64)(u32)spos);
 			else
@@ -352,6 +354,118 @@ __global__ void k_fill(const u32* __restrict__ query, const i32* __restrict__ le
 		__syncthreads();
 		hbase += tot;
 		fbase += ftot;
+	}
+}
+
+// ---- option B receiver: seed hits gathered from index shards, back in emission order --------------------------------
+// The shards' runs of one query arrive in any order.  k_fill emits (overlap.cpp:176-196) by ascending curPos and, per
+// query k-mer, by ascending STORED global position (record << 32 | pos, vertex_index.cpp:108-114); the stored side of a
+// hit is what it reported, turned back where the query k-mer at curPos was flipped: (record ^ 1, len - pos - k)
+// (vertex_index.h:158-174).  (query k-mer, stored record, stored position) is a total order -- no two hits of a query
+// share it -- so a stable radix sort (fg_devprim.h) on
+//   g << (recBits + posBits) | record << posBits | position,   g = the query k-mer's index in the sub-range
+// restores the order for all queries of a sub-range at once (two stable passes, stored side first, when that exceeds
+// 64 bits).  The sorted hits are then written in the stage's key form, where k_fill would have written them.
+
+// the repetitive query positions of every query (curFilteredPos, overlap.cpp:407-413), ascending, as k_fill lists them
+__global__ void k_filt_pos(const u64* __restrict__ qKmerOff, const u64* __restrict__ probe, const u64* __restrict__ filtOff,
+						   i32* __restrict__ filtPos)
+{
+	__shared__ u32 sh[WG / 64 + 1];
+	const u32 q = blockIdx.x;
+	const u64 a = qKmerOff[q];
+	const i32 nk = (i32)(qKmerOff[q + 1] - a);
+	u64 fbase = filtOff[q];
+	for (i32 p0 = 0; p0 < nk; p0 += WG)
+	{
+		const i32 p = p0 + (i32)threadIdx.x;
+		const u64 v = p < nk ? probe[a + p] : 0;
+		const u32 rep = (v != 0 && (u32)(v & FG_CNT_MASK) == FG_CNT_REPETITIVE) ? 1u : 0u;
+		u32 tot;
+		const u32 off = block_exscan(rep, sh, &tot);
+		if (rep) filtPos[fbase + off] = p;
+		fbase += tot;
+	}
+}
+
+// one block per query of the sub-range: every (source) run of its hits -> sort key + slot; run[2 (q nSrc + s)] =
+// {start in hits, length}; the query's slots start at hitOff[q].  Mode 0: the full key; mode 1: the stored side only
+// (the first of two passes).  A hit outside its query or target sets *err and gets key 0 (nothing is read through it).
+__global__ void k_recv_keys(const u32* __restrict__ query, const u64* __restrict__ qKmerOff, const u64* __restrict__ qWords,
+							const u64* __restrict__ qWordOff, const i32* __restrict__ qLen, const i32* __restrict__ len, int k,
+							u32 firstId, u32 nRec, const fg_seed_hit* __restrict__ hits, const u64* __restrict__ run, u32 nSrc,
+							const u64* __restrict__ hitOff, int recBits, int posBits, int mode, u64* __restrict__ keys,
+							u64* __restrict__ vals, u64* __restrict__ hitIdx, u32* __restrict__ err)
+{
+	const u32 q = blockIdx.x;
+	const u32 rec = query[q];
+	const i32 nk = qLen[rec >> 1] - k;
+	const bool rc = rec & 1;
+	const u64* w = qWords + qWordOff[rec >> 1];
+	const u64 g0 = qKmerOff[q] - qKmerOff[0];
+	u64 out = hitOff[q];
+	for (u32 s = 0; s < nSrc; ++s)
+	{
+		const u64 start = run[2 * ((u64)q * nSrc + s)], n = run[2 * ((u64)q * nSrc + s) + 1];
+		for (u64 j = threadIdx.x; j < n; j += WG)
+		{
+			const fg_seed_hit h = hits[start + j];
+			u64 key = 0;
+			const u32 srec0 = h.ext_id - firstId;
+			if (h.cur_pos < 0 || h.cur_pos >= nk || h.ext_id < firstId || srec0 >= nRec || h.ext_pos < 0 ||
+				h.ext_pos > len[srec0 >> 1] - k)
+				atomicOr(err, 1u);
+			else
+			{
+				// the orientation of the query k-mer at curPos, as k_probe finds it
+				const i32 qf = rc ? nk - h.cur_pos : h.cur_pos;
+				u64 a, b;
+				fg_kmer_pair(w, qf, k, a, b);
+				const u64 fw = rc ? b : a, rv = rc ? a : b;
+				u32 srec = srec0;
+				u32 spos = (u32)h.ext_pos;
+				if (rv < fw) { srec ^= 1u; spos = (u32)(len[srec >> 1] - h.ext_pos - k); }
+				key = ((u64)srec << posBits) | spos;
+				if (mode == 0) key |= (g0 + (u64)h.cur_pos) << (recBits + posBits);
+			}
+			keys[out + j] = key;
+			vals[out + j] = out + j;
+			hitIdx[out + j] = start + j;
+		}
+		out += n;
+	}
+}
+
+// second pass of the two-pass form: the key becomes the query k-mer index g of the hit in slot vals[i]
+__global__ void k_recv_gkey(const u64* __restrict__ vals, u64 n, const u64* __restrict__ hitOff, u32 nq,
+							const u64* __restrict__ qKmerOff, const fg_seed_hit* __restrict__ hits,
+							const u64* __restrict__ hitIdx, u64* __restrict__ keys)
+{
+	const u64 i = (u64)blockIdx.x * WG + threadIdx.x;
+	if (i >= n) return;
+	const u64 slot = vals[i];
+	u32 lo = 0, hi = nq;		// the query: last q with hitOff[q] <= slot
+	while (hi - lo > 1) { const u32 m = (lo + hi) >> 1; if (hitOff[m] <= slot) lo = m; else hi = m; }
+	keys[i] = qKmerOff[lo] - qKmerOff[0] + (u64)hits[hitIdx[slot]].cur_pos;
+}
+
+// sorted hit i -> the stage's key form at slot i (what k_fill writes)
+template <class KT>
+__global__ void k_recv_place(const u64* __restrict__ vals, u64 n, const fg_seed_hit* __restrict__ hits,
+							 const u64* __restrict__ hitIdx, u32 firstId, int curBits, KT* __restrict__ hitKey,
+							 u32* __restrict__ hitVal)
+{
+	const u64 i = (u64)blockIdx.x * WG + threadIdx.x;
+	if (i >= n) return;
+	const fg_seed_hit h = hits[hitIdx[vals[i]]];
+	const u32 srec = h.ext_id - firstId;
+	if constexpr (std::is_same<KT, PK>::value)
+		hitKey[i] = PK(((u64)srec << (curBits + FG_PK_VALBITS)) | ((u64)(u32)h.cur_pos << FG_PK_VALBITS) | (u64)(u32)h.ext_pos);
+	else
+	{
+		if (sizeof(KT) == 8) hitKey[i] = (KT)(((u64)h.ext_id << 32) | (u32)h.cur_pos);
+		else hitKey[i] = (KT)((srec << curBits) | (u32)h.cur_pos);
+		hitVal[i] = (u32)h.ext_pos;
 	}
 }
 
@@ -1075,11 +1189,76 @@ static void probeChunk(fg_ctx* c, const u32* hq, const u64* hQKmerOff, u32 qa, u
 	HIP_CHECK(hipStreamSynchronize(s));
 }
 
+// Option B: the sub-range's hits come from the shards (recv; query callQ0 of the call is query 0 of the probed chunk)
+// instead of k_fill -- the repetitive positions from this context's probes, the hits in emission order at the slots
+// k_fill would have written (see k_recv_keys).
+template <class KT>
+static void recvFill(fg_ctx* c, const RecvHits* recv, u32 callQ0, u32 sub0, u32 nq, u64 nHits, int curBits, KT* hitKey, u32* hitVal)
+{
+	hipStream_t s = c->stream;
+	const int k = c->k;
+	const u32* dQuery = c->dQuery.p + sub0;
+	const u64* dQKmerOff = c->dQKmerOff.p + sub0;
+	{ ScopedK t(c->timer, "k_filt_pos");
+	  hipLaunchKernelGGL(k_filt_pos, nq, WG, 0, s, dQKmerOff, c->dProbe.p, c->dFiltOff.p, c->dFiltPos.p); }
+	if (nHits == 0) return;
+	if (nHits > fgprim::RS_MAX_N) throw FgError{FG_ERR_ARG, "more than 2^30 - 1 seed hits in one sub-range"};
+	const u32 ns = recv->nSrc;
+	std::vector<u64> run(2 * (size_t)nq * ns);
+	for (u32 i = 0; i < nq; ++i)
+		for (u32 src = 0; src < ns; ++src)
+		{
+			const size_t at = (size_t)(callQ0 + sub0 + i) * ns + src;
+			run[2 * ((size_t)i * ns + src)] = recv->runStart[at];
+			run[2 * ((size_t)i * ns + src) + 1] = recv->runLen[at];
+		}
+	c->dRecvRun.reserve(run.size());
+	c->dRecvIdx.reserve(nHits);
+	c->dRecvErr.reserve(1);
+	c->dPartK0.reserve(nHits); c->dPartV0.reserve(nHits); c->dPartK1.reserve(nHits); c->dPartV1.reserve(nHits);
+	c->dPartScratch.reserve(fgprim::radixSortScratchBytes(nHits));
+	HIP_CHECK(hipMemcpyAsync(c->dRecvRun.p, run.data(), run.size() * 8, hipMemcpyHostToDevice, s));
+	HIP_CHECK(hipMemsetAsync(c->dRecvErr.p, 0, 4, s));
+	// bits of the stored side and of the query k-mer index
+	int recBits = 1, posBits = 1, gBits = 1;
+	while ((1ULL << recBits) < 2ULL * c->nReads) ++recBits;
+	while ((1LL << posBits) <= (long long)c->maxLen) ++posBits;
+	u64 hQK[2] = {0, 0};
+	HIP_CHECK(hipMemcpyAsync(hQK, dQKmerOff, 8, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(hipMemcpyAsync(hQK + 1, dQKmerOff + nq, 8, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(hipStreamSynchronize(s));		// also keeps `run` alive until its copy has run
+	while ((1ULL << gBits) < hQK[1] - hQK[0]) ++gBits;
+	const int storedBits = recBits + posBits;
+	const bool onePass = gBits + storedBits <= 64;
+	const bool qs = c->hasQ;
+	{ ScopedK t(c->timer, "k_recv_keys");
+	  hipLaunchKernelGGL(k_recv_keys, nq, WG, 0, s, dQuery, dQKmerOff, qs ? c->dQWords.p : c->dWords.p, qs ? c->dQWordOff.p : c->dWordOff.p,
+						 qs ? c->dQLen.p : c->dLen.p, c->dLen.p, k, c->firstId, 2 * c->nReads, recv->hits, c->dRecvRun.p, ns,
+						 c->dHitOff.p, recBits, posBits, onePass ? 0 : 1, c->dPartK0.p, c->dPartV0.p, c->dRecvIdx.p, c->dRecvErr.p); }
+	if (fetchScalar(c, c->dRecvErr.p)) throw FgError{FG_ERR_ARG, "a received seed hit lies outside its query or its target"};
+	u64 *k0 = c->dPartK0.p, *v0 = c->dPartV0.p, *k1 = c->dPartK1.p, *v1 = c->dPartV1.p;
+	{ ScopedK t(c->timer, "k_recv_sort");
+	  if (fgprim::radixSortPairs(s, k0, v0, k1, v1, nHits, 0, onePass ? gBits + storedBits : storedBits, c->dPartScratch.p))
+		  { std::swap(k0, k1); std::swap(v0, v1); } }
+	if (!onePass)
+	{
+		{ ScopedK t(c->timer, "k_recv_keys");
+		  hipLaunchKernelGGL(k_recv_gkey, (unsigned)((nHits + WG - 1) / WG), WG, 0, s, v0, nHits, c->dHitOff.p, nq, dQKmerOff,
+							 recv->hits, c->dRecvIdx.p, k0); }
+		ScopedK t(c->timer, "k_recv_sort");
+		if (fgprim::radixSortPairs(s, k0, v0, k1, v1, nHits, 0, gBits, c->dPartScratch.p)) { std::swap(k0, k1); std::swap(v0, v1); }
+	}
+	{ ScopedK t(c->timer, "k_recv_place");
+	  hipLaunchKernelGGL(k_recv_place<KT>, (unsigned)((nHits + WG - 1) / WG), WG, 0, s, v0, nHits, recv->hits, c->dRecvIdx.p,
+						 c->firstId, curBits, hitKey, hitVal); }
+}
+
 // The stage behind the probes for the queries [sub0, sub0 + nq) of the probed chunk: seed expansion -> sort ->
 // groups -> chaining -> (edit distance) -> compacted primaries in c->hPrim (behind primBase records) / offsets in
 // c->hOff.
 static void deviceSub(fg_ctx* c, const fg_detector_params* p, uint8_t forceLocal, u32 sub0, u32 nq, u64 primBase,
-					  u64 hitCapHint /* the largest sub-range of the chunk: scratch is sized once, not regrown */, ChunkResult* res)
+					  u64 hitCapHint /* the largest sub-range of the chunk: scratch is sized once, not regrown */, ChunkResult* res,
+					  const RecvHits* recv = nullptr, u32 callQ0 = 0)
 {
 	hipStream_t s = c->stream;
 	const int k = c->k;
@@ -1115,7 +1294,8 @@ static void deviceSub(fg_ctx* c, const fg_detector_params* p, uint8_t forceLocal
 	if (keyMode == 0)
 	{
 		c->dHitKey32.reserve(hitCap + 1); c->dHitVal.reserve(hitCap + 1);
-		{ ScopedK t(c->timer, "k_fill");
+		if (recv) recvFill<u32>(c, recv, callQ0, sub0, nq, nHits, curBits, c->dHitKey32.p, c->dHitVal.p);
+		else { ScopedK t(c->timer, "k_fill");
 		  hipLaunchKernelGGL(k_fill<u32>, nq, WG, 0, s, dQuery, c->dLen.p, qLen, dQKmerOff, k, c->firstId, curBits,
 							 c->dProbe.p, c->dEntries.p, c->dHitOff.p, c->dFiltOff.p, c->dHitKey32.p, c->dHitVal.p, c->dFiltPos.p); }
 		sortSegments<u32>(c, c->dHitOff.p, nq, c->dHitKey32.p, c->dHitVal.p, nHits);
@@ -1123,7 +1303,8 @@ static void deviceSub(fg_ctx* c, const fg_detector_params* p, uint8_t forceLocal
 	else if (keyMode == 1)
 	{
 		c->dHitKey.reserve(hitCap + 1);
-		{ ScopedK t(c->timer, "k_fill");
+		if (recv) recvFill<PK>(c, recv, callQ0, sub0, nq, nHits, curBits, (PK*)c->dHitKey.p, (u32*)nullptr);
+		else { ScopedK t(c->timer, "k_fill");
 		  hipLaunchKernelGGL(k_fill<PK>, nq, WG, 0, s, dQuery, c->dLen.p, qLen, dQKmerOff, k, c->firstId, curBits,
 							 c->dProbe.p, c->dEntries.p, c->dHitOff.p, c->dFiltOff.p, (PK*)c->dHitKey.p, (u32*)nullptr, c->dFiltPos.p); }
 		sortSegments<PK>(c, c->dHitOff.p, nq, (PK*)c->dHitKey.p, (u32*)nullptr, nHits, curBits);
@@ -1131,7 +1312,8 @@ static void deviceSub(fg_ctx* c, const fg_detector_params* p, uint8_t forceLocal
 	else
 	{
 		c->dHitKey.reserve(hitCap + 1); c->dHitVal.reserve(hitCap + 1);
-		{ ScopedK t(c->timer, "k_fill");
+		if (recv) recvFill<u64>(c, recv, callQ0, sub0, nq, nHits, curBits, c->dHitKey.p, c->dHitVal.p);
+		else { ScopedK t(c->timer, "k_fill");
 		  hipLaunchKernelGGL(k_fill<u64>, nq, WG, 0, s, dQuery, c->dLen.p, qLen, dQKmerOff, k, c->firstId, 0,
 							 c->dProbe.p, c->dEntries.p, c->dHitOff.p, c->dFiltOff.p, c->dHitKey.p, c->dHitVal.p, c->dFiltPos.p); }
 		sortSegments<u64>(c, c->dHitOff.p, nq, c->dHitKey.p, c->dHitVal.p, nHits, curBits);
@@ -1229,6 +1411,26 @@ static void deviceSub(fg_ctx* c, const fg_detector_params* p, uint8_t forceLocal
 	for (u32 i = 0; i < nq; ++i) { res->dpGroups += c->hOff.p[(nq + 1) + i]; res->dpElems += c->hOff.p[2 * (size_t)(nq + 1) + i]; }
 }
 
+// Chunk budgets of the overlap stage: query k-mers per probed chunk, seed hits per sub-range
+static void stageBudgets(fg_ctx* c, u64& kmerBudget, u64& hitBudget)
+{
+	kmerBudget = getenv("FG_KMER_BUDGET") ? strtoull(getenv("FG_KMER_BUDGET"), nullptr, 10) : (1ULL << 30);
+	hitBudget = getenv("FG_HIT_BUDGET") ? strtoull(getenv("FG_HIT_BUDGET"), nullptr, 10) : (3ULL << 29);
+	if (!getenv("FG_KMER_BUDGET") && !getenv("FG_HIT_BUDGET"))
+	{
+		// ... and by what the device has left beside the resident index (a CHM13-sized index leaves ~80 of 288 GB):
+		// the chunk scratch may grow into the free memory plus what it already holds, less a reserve
+		size_t freeB = 0, totalB = 0;
+		HIP_CHECK(hipMemGetInfo(&freeB, &totalB));
+		const u64 held = c->dHitKey.bytes() + c->dHitKey32.bytes() + c->dHitVal.bytes() + c->dCur.bytes() + c->dExt.bytes() +
+						 c->dScore.bytes() + c->dBack.bytes() + c->dTmp32.bytes() + c->dCand.bytes() + c->dProbe.bytes();
+		const u64 avail = (u64)freeB + held;
+		const u64 usable = avail > (8ULL << 30) ? (avail - (4ULL << 30)) / 10 * 9 : avail / 2;
+		hitBudget = std::min(hitBudget, std::max<u64>(16ULL << 20, usable / 100 * 85 / 80));	// ~70 B per hit, grow-only slack
+		kmerBudget = std::min(kmerBudget, std::max<u64>(16ULL << 20, usable / 100 * 15 / 9));	// 8 B per query k-mer
+	}
+}
+
 // ---- two lanes ------------------------------------------------------------------------------------------------
 // The stage behind the probes alternates between bandwidth-bound kernels (seed expansion, the sort levels) and
 // issue- / latency-bound ones that end on a handful of long waves (the per-group kernels of the chaining stage).  A call
@@ -1284,7 +1486,7 @@ struct SubResult {
 };
 
 void fgOverlaps(fg_ctx* c, const fg_detector_params* p, const u32* queryIds, u32 nq, i32 maxOverlaps,
-				uint8_t forceLocal, fg_overlap_batch* out)
+				uint8_t forceLocal, fg_overlap_batch* out, const RecvHits* recv)
 {
 	hipStream_t s = c->stream;
 	const int k = c->k;
@@ -1337,21 +1539,11 @@ void fgOverlaps(fg_ctx* c, const fg_detector_params* p, const u32* queryIds, u32
 	// The batch is cut into chunks so that the per-chunk scratch (8 B per query k-mer,
 	// ~70 B per seed hit) stays bounded whatever the caller passes; a chunk whose hits
 	// exceed the budget is halved.  E. coli 50x is one chunk.
-	u64 kmerBudget = getenv("FG_KMER_BUDGET") ? strtoull(getenv("FG_KMER_BUDGET"), nullptr, 10) : (1ULL << 30);
-	u64 hitBudget = getenv("FG_HIT_BUDGET") ? strtoull(getenv("FG_HIT_BUDGET"), nullptr, 10) : (3ULL << 29);
-	if (!getenv("FG_KMER_BUDGET") && !getenv("FG_HIT_BUDGET"))
-	{
-		// ... and by what the device has left beside the resident index (a CHM13-sized index leaves ~80 of 288 GB):
-		// the chunk scratch may grow into the free memory plus what it already holds, less a reserve
-		size_t freeB = 0, totalB = 0;
-		HIP_CHECK(hipMemGetInfo(&freeB, &totalB));
-		const u64 held = c->dHitKey.bytes() + c->dHitKey32.bytes() + c->dHitVal.bytes() + c->dCur.bytes() + c->dExt.bytes() +
-						 c->dScore.bytes() + c->dBack.bytes() + c->dTmp32.bytes() + c->dCand.bytes() + c->dProbe.bytes();
-		const u64 avail = (u64)freeB + held;
-		const u64 usable = avail > (8ULL << 30) ? (avail - (4ULL << 30)) / 10 * 9 : avail / 2;
-		hitBudget = std::min(hitBudget, std::max<u64>(16ULL << 20, usable / 100 * 85 / 80));	// ~70 B per hit, grow-only slack
-		kmerBudget = std::min(kmerBudget, std::max<u64>(16ULL << 20, usable / 100 * 15 / 9));	// 8 B per query k-mer
-	}
+	u64 kmerBudget, hitBudget;
+	stageBudgets(c, kmerBudget, hitBudget);
+	// option B: the receiver's re-ordering adds ~40 B per hit (two key / slot pairs, each slot's index into the received hits) and
+	// sorts at most 2^30 - 1 pairs at a time
+	if (recv) hitBudget = std::min<u64>(hitBudget * 2 / 3, 1ULL << 29);
 	std::vector<std::pair<u32, u32>> chunks;	// [qa, qb) bounded by the k-mer budget
 	{
 		u32 qa = 0;
@@ -1380,6 +1572,13 @@ void fgOverlaps(fg_ctx* c, const fg_detector_params* p, const u32* queryIds, u32
 	{
 		probeChunk(c, hq.data(), hQKmerOff.data(), ch.first, ch.second, hitsPerQuery);
 		const u32 cn = ch.second - ch.first;
+		if (recv)
+		{
+			// the hits come from the shards: their totals replace what this context's own probes counted
+			hitsPerQuery.assign(recv->total + ch.first, recv->total + ch.second);
+			HIP_CHECK(hipMemcpyAsync(c->dCntA.p, hitsPerQuery.data(), cn * 8ULL, hipMemcpyHostToDevice, s));
+			HIP_CHECK(hipStreamSynchronize(s));
+		}
 		u64 chunkHits = 0;
 		for (u32 i = 0; i < cn; ++i) chunkHits += hitsPerQuery[i];
 		// sub-ranges of the chunk's queries whose hits fit the budget (a single query above it is one of its own);
@@ -1451,7 +1650,8 @@ void fgOverlaps(fg_ctx* c, const fg_detector_params* p, const u32* queryIds, u32
 					SubResult& sr = *subs[sub0Index + i];
 					sr.lane = lane;
 					sr.lanePrimBase = lanePrim[lane];
-					deviceSub(lc, p, forceLocal, ranges[i].first, ranges[i].second - ranges[i].first, lanePrim[lane], maxSubHits, &sr.cr);
+					deviceSub(lc, p, forceLocal, ranges[i].first, ranges[i].second - ranges[i].first, lanePrim[lane], maxSubHits, &sr.cr,
+							  recv, ch.first);
 					const u32 n = ranges[i].second - ranges[i].first;
 					sr.primOff.assign(lc->hOff.p, lc->hOff.p + n + 1);
 					if (keepAln)
@@ -1701,4 +1901,85 @@ void fgOverlaps(fg_ctx* c, const fg_detector_params* p, const u32* queryIds, u32
 							std::chrono::duration<double>(tHost1 - tHost0).count(), 1});
 	c->timer.last.push_back(fg_kernel_time{"host:shim (divergence, gate, records)",
 							std::chrono::duration<double>(tHost2 - tHost1).count(), 1});
+}
+
+// ---- option B: the sender and the receiver ---------------------------------------------------------
+// Sender: seed collection of the queries against this context's (shard) index -- probeChunk's k_probe, then k_fill
+// in its export form -- chunk by chunk (the same k-mer budget as fgOverlaps) into one growing device array.
+void fgProbeHits(fg_ctx* c, const u32* queryIds, u32 nq, u64* hitCounts, const fg_seed_hit** dHits, u64* nHits)
+{
+	hipStream_t s = c->stream;
+	const int k = c->k;
+	c->timer.reset();
+	std::vector<u32> hq(nq);
+	std::vector<u64> hQKmerOff(nq + 1, 0);
+	for (u32 i = 0; i < nq; ++i)
+	{
+		hq[i] = queryIds[i] - (c->hasQ ? c->qFirstId : c->firstId);
+		const i32 L = (c->hasQ ? c->hQLen : c->hLen)[hq[i] >> 1];
+		hQKmerOff[i + 1] = hQKmerOff[i] + (u64)std::max(0, L - k);
+	}
+	u64 kmerBudget, hitBudget;
+	stageBudgets(c, kmerBudget, hitBudget);
+	const i32* qLen = c->hasQ ? c->dQLen.p : c->dLen.p;
+	std::vector<u64> hitsPerQuery;
+	u64 total = 0;
+	for (u32 qa = 0; qa < nq;)
+	{
+		u32 qb = qa + 1;
+		while (qb < nq && hQKmerOff[qb + 1] - hQKmerOff[qa] <= kmerBudget) ++qb;
+		probeChunk(c, hq.data(), hQKmerOff.data(), qa, qb, hitsPerQuery);
+		const u32 cn = qb - qa;
+		u64 chunkHits = 0;
+		for (u32 i = 0; i < cn; ++i) { hitCounts[qa + i] = hitsPerQuery[i]; chunkHits += hitsPerQuery[i]; }
+		// the export array grows keeping what the chunks before wrote; a size the device cannot hold is refused here
+		if (total + chunkHits + 1 > c->dSeedHits.n)
+		{
+			size_t freeB = 0, totalB = 0;
+			HIP_CHECK(hipMemGetInfo(&freeB, &totalB));
+			const u64 want = (total + chunkHits + 1) * sizeof(fg_seed_hit);
+			if (want > (u64)freeB + c->dSeedHits.bytes())
+				throw FgError{FG_ERR_NOMEM, "seed hits of this call (" + std::to_string(want) + " bytes) exceed the free device memory"};
+			DevBuf<fg_seed_hit> grown;
+			grown.alloc(total + chunkHits + 1);
+			if (total) HIP_CHECK(hipMemcpyAsync(grown.p, c->dSeedHits.p, total * sizeof(fg_seed_hit), hipMemcpyDeviceToDevice, s));
+			HIP_CHECK(hipStreamSynchronize(s));
+			c->dSeedHits.swap(grown);
+		}
+		{ ScopedK t(c->timer, "k_exscan");
+		  hipLaunchKernelGGL(k_exscan, 1, 1024, 0, s, c->dCntA.p, c->dHitOff.p, cn);
+		  hipLaunchKernelGGL(k_exscan, 1, 1024, 0, s, c->dCntB.p, c->dFiltOff.p, cn); }
+		c->dFiltPos.reserve(fetchScalar(c, c->dFiltOff.p + cn) + 1);
+		{ ScopedK t(c->timer, "k_fill");
+		  hipLaunchKernelGGL(k_fill<fg_seed_hit>, cn, WG, 0, s, c->dQuery.p, c->dLen.p, qLen, c->dQKmerOff.p, k, c->firstId, 0,
+							 c->dProbe.p, c->dEntries.p, c->dHitOff.p, c->dFiltOff.p, c->dSeedHits.p + total, (u32*)nullptr,
+							 c->dFiltPos.p); }
+		total += chunkHits;
+		qa = qb;
+	}
+	HIP_CHECK(hipStreamSynchronize(s));
+	c->timer.collect();
+	*dHits = total ? c->dSeedHits.p : nullptr;
+	*nHits = total;
+}
+
+// Receiver: the run table of the received hits (sources one after another, inside a source the queries in list
+// order), then the overlap stage with those hits in place of its own seed expansion.
+void fgOverlapsFromHits(fg_ctx* c, const fg_detector_params* p, const u32* queryIds, u32 nq, i32 maxOverlaps,
+						uint8_t forceLocal, u32 nSrc, const u64* hitCounts, const fg_seed_hit* dHits, fg_overlap_batch* out)
+{
+	std::vector<u64> runStart((size_t)nq * nSrc), runLen((size_t)nq * nSrc), total(nq, 0);
+	u64 at = 0;
+	for (u32 src = 0; src < nSrc; ++src)
+		for (u32 q = 0; q < nq; ++q)
+		{
+			const u64 n = hitCounts[(size_t)src * nq + q];
+			runStart[(size_t)q * nSrc + src] = at;
+			runLen[(size_t)q * nSrc + src] = n;
+			total[q] += n;
+			at += n;
+		}
+	if (at && !dHits) throw FgError{FG_ERR_ARG, "hit counts without hits"};
+	const RecvHits recv{nSrc, runStart.data(), runLen.data(), total.data(), dHits};
+	fgOverlaps(c, p, queryIds, nq, maxOverlaps, forceLocal, out, &recv);
 }

@@ -1,4 +1,6 @@
-"""Multi-GPU layout of the path (option A): one process per GPU.
+"""Multi-GPU layouts of the path: one process per GPU.
+
+Option A (what bench.py runs): the index replicated on every rank.
 
 * INDEX BUILD, sharded by key range (``build_index_sharded``).  ``balanced_bin_ranges`` cuts the 4096 key bins
   into ``world`` contiguous ranges of about equal weight; rank r holds the exact k-mer counters of ITS range only,
@@ -11,6 +13,18 @@
 * OVERLAP STAGE: reads shard by sequence id, rank r owns the forward reads i with i % world == r and
   computes their lists against its full index copy: no data-path collective; only the barrier / max-time
   reduction of the bench.
+
+Option B (``build_index_option_b`` + ``overlaps_option_b``): the index sharded by TARGET read.  The same key-range
+build and all-gather, then every rank keeps only the list entries of the target reads it owns (read i, i % world ==
+rank; ``fg_index_keep_targets``): the entry arrays -- the only part of the index that shrinks when sharded -- take
+1/world of the memory; keys, lookup table and repetitive k-mers stay replicated.  Queries walk in global batches
+that every rank cuts the same way; each rank probes the whole batch against its shard (``fg_probe_hits``), the
+per-(destination, query) hit counts and then the 12-byte hits go to the queries' owners with two
+``all_to_all_single`` (device to device with nccl = RCCL, through host copies with gloo), and each owner restores
+the reference's emission order on the device and runs the rest of getSeqOverlaps (``fg_overlaps_from_hits``).
+Bit-exact against the replicated index by test (tests/test_option_b.py: W shards as W contexts on one GPU, and two
+gloo processes).  What the per-rank memory saving amounts to at CHM13 scale is still arithmetic: the
+gather lands the whole index on every rank before keep_targets cuts it, and no multi-GPU run has been measured.
 """
 from __future__ import annotations
 
@@ -40,9 +54,9 @@ def merge_sharded(per_rank_ids, per_rank_lists):
 
 
 # ---- option B of SURVEY.md §8(e): index sharded by TARGET read, seed hits exchanged -----------------------------
-# Not the layout bench.py runs (the replicated index fits 288 GB for every BASELINE config); what is
-# kept here, tested on CPU (tests/test_dist.py), is the part of it that bit parity hangs on: the order in which the
-# query's owner must line the received hits up before the std::sort emulation.
+# Not the layout bench.py runs (the replicated index fits 288 GB for every BASELINE config).  The order in
+# which the query's owner must line the received hits up before the std::sort emulation, in numpy (the device form is
+# k_recv_keys / k_recv_place in fg_overlap.hip):
 def owner_of_target(record, world: int):
     """the rank whose index shard holds the entries of this stored record (forward or reverse strand of read i)"""
     return (np.asarray(record) >> 1) % world
@@ -286,3 +300,75 @@ def build_index_sharded(vi, cfg: dict, rank: int, world: int, on_device: bool):
               select_and_sort_s=t1 - t0, finish_s=t2 - t1, allgather_s=t3 - t2, import_s=0.0, build_seconds=t3 - t0)
     vi.stats = st
     return st
+
+
+# ---- option B: build and overlap stage ----------------------------------------------------------------------------
+def build_index_option_b(vi, cfg: dict, rank: int, world: int, on_device: bool):
+    """The key-range sharded build (``build_index_sharded``), then the index restricted to the entries of the target
+    reads this rank owns.  Statistics and getSampleRate() stay those of the whole index."""
+    st = build_index_sharded(vi, cfg, rank, world, on_device)
+    st["shard_entries"] = vi.keep_targets(world, rank)
+    vi.stats = st
+    return st
+
+
+def _hits_tensor(hits, n: int):
+    """probe_hits' hits as an int32 tensor [n, 3]: a device pointer is wrapped without a copy (a stand-in detector
+    may hand a SEED_HIT_DTYPE numpy array)"""
+    import torch
+    if isinstance(hits, np.ndarray):
+        return torch.from_numpy(np.ascontiguousarray(hits).view(np.int32).reshape(-1, 3).copy())
+    return _view(int(hits), 3 * n, torch.device("cuda", torch.cuda.current_device()), "<i4").reshape(-1, 3)
+
+
+def exchange_hits(counts, hits, owner, rank: int, world: int, on_device: bool):
+    """The two all_to_all_single of option B for one batch.  ``counts[q]`` hits of batch query q in ``hits`` (int32
+    tensor [n, 3], query after query), ``owner[q]`` its rank.  Returns (counts [world, n_mine] of this rank's queries
+    in batch order, sources in rank order; the received hits [sum, 3]: sources one after another, inside a source the
+    queries in batch order)."""
+    import torch
+    import torch.distributed as td
+    counts = np.asarray(counts, np.int64)
+    owner = np.asarray(owner, np.int64)
+    order = np.argsort(owner, kind="stable")                 # queries grouped by destination, batch order inside
+    start = np.concatenate([[0], np.cumsum(counts)])[:-1]
+    c_sorted = counts[order]
+    before = np.concatenate([[0], np.cumsum(c_sorted)])[:-1]
+    idx = np.repeat(start[order] - before, c_sorted) + np.arange(int(c_sorted.sum()), dtype=np.int64)
+    n_to = np.bincount(owner, minlength=world)              # queries per destination
+    h_to = np.bincount(owner, weights=counts, minlength=world).astype(np.int64)
+    n_mine = int(n_to[rank])
+    dev = hits.device if on_device else torch.device("cpu")
+    send_c = torch.from_numpy(c_sorted.copy()).to(dev)
+    recv_c = torch.empty(world * n_mine, dtype=torch.int64, device=dev)
+    td.all_to_all_single(recv_c, send_c, output_split_sizes=[n_mine] * world, input_split_sizes=n_to.tolist())
+    rc = recv_c.cpu().numpy().reshape(world, n_mine)
+    h_from = rc.sum(axis=1)
+    src = hits if on_device else hits.cpu()
+    send_h = src.index_select(0, torch.from_numpy(idx).to(src.device)).reshape(-1).contiguous()
+    recv_h = torch.empty(3 * int(h_from.sum()), dtype=torch.int32, device=send_h.device)
+    td.all_to_all_single(recv_h, send_h, output_split_sizes=(3 * h_from).tolist(), input_split_sizes=(3 * h_to).tolist())
+    return rc, recv_h.reshape(-1, 3)
+
+
+def overlaps_option_b(det, rank: int, world: int, on_device: bool, batch_reads: int = 4096):
+    """The overlap stage of option B over all reads of the context (forward query ids): global batches of
+    ``batch_reads`` reads, every rank probes the whole batch against its shard, the hits go to the queries' owners
+    (read i -> rank i % world, as ``shard_queries``), each rank computes its own queries from what it received.
+    Returns ([(this rank's query ids, OverlapResult)] per batch, bytes of hits sent to other ranks)."""
+    import torch
+    ctx = det.ctx
+    n_reads, first = int(ctx.n_reads), int(ctx.first_id)
+    out, moved = [], 0
+    for b0 in range(0, n_reads, batch_reads):
+        reads = np.arange(b0, min(n_reads, b0 + batch_reads), dtype=np.int64)
+        q = (first + 2 * reads).astype(np.uint32)
+        owner = owner_of(reads, world)
+        counts, hits, n = det.probe_hits(q)
+        rc, recv = exchange_hits(counts, _hits_tensor(hits, n), owner, rank, world, on_device)
+        moved += 12 * int(np.asarray(counts, np.int64)[owner != rank].sum())
+        if on_device:
+            torch.cuda.synchronize()
+        mine = q[owner == rank]
+        out.append((mine, det.getSeqOverlapsFromHits(mine, rc, recv)))
+    return out, moved

@@ -42,7 +42,11 @@ ABI_SYMBOLS = ["fg_abi_version", "fg_create", "fg_destroy", "fg_strerror", "fg_l
                "fg_index_kmer_hist", "fg_index_count_slice", "fg_index_batch_freq", "fg_index_batch_select",
                "fg_index_selection_done", "fg_index_gather_begin", "fg_index_gather_end", "fg_memory_stats",
                "fg_import_index", "fg_index_device_arrays", "fg_clear_index", "fg_export_index", "fg_overlaps", "fg_release_batch",
-               "fg_kernel_times", "fg_debug_sort_pairs", "fg_debug_edit_distances", "fg_align_cigar_ksw", "fg_release_cigars"]
+               "fg_kernel_times", "fg_debug_sort_pairs", "fg_debug_edit_distances", "fg_align_cigar_ksw", "fg_release_cigars",
+               "fg_index_keep_targets", "fg_index_shard", "fg_probe_hits", "fg_overlaps_from_hits"]
+
+# struct fg_seed_hit: KmerMatch{curPos, extPos, extId} (overlap.cpp:176-196)
+SEED_HIT_DTYPE = np.dtype([("cur_pos", "<i4"), ("ext_pos", "<i4"), ("ext_id", "<u4")])
 
 
 class FlyeGpuError(RuntimeError):
@@ -148,6 +152,12 @@ def load_library():
         L.fg_overlaps.argtypes = [C.c_void_p, C.POINTER(DetectorParams), C.c_void_p, C.c_uint32,
                                   C.c_int32, C.c_uint8, C.POINTER(OverlapBatch)]
         L.fg_release_batch.argtypes = [C.POINTER(OverlapBatch)]
+        L.fg_index_keep_targets.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
+        L.fg_index_shard.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.fg_probe_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_void_p),
+                                    C.POINTER(C.c_uint64)]
+        L.fg_overlaps_from_hits.argtypes = [C.c_void_p, C.POINTER(DetectorParams), C.c_void_p, C.c_uint32, C.c_int32,
+                                            C.c_uint8, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(OverlapBatch)]
         L.fg_kernel_times.argtypes = [C.c_void_p, C.POINTER(KernelTime), C.c_int]
         L.fg_debug_sort_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
         L.fg_debug_edit_distances.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -275,6 +285,7 @@ class Context:
             raise FlyeGpuError(rc, self.L.fg_strerror(rc).decode())
         self.h = h
         self.k = kmer_size
+        self.device = device
         self.first_id = 0
         self.n_reads = 0
 
@@ -503,6 +514,20 @@ class VertexIndex:
     def clear(self):
         self.ctx._check(self.ctx.L.fg_clear_index(self.ctx.h))
 
+    def keep_targets(self, world: int, rank: int) -> int:
+        """Option B (fg_index_keep_targets): keep only the entries of the target reads i with i % world == rank.
+        Keys, repetitive k-mers, statistics and getSampleRate() stay those of the whole index.  Returns the entries
+        kept."""
+        n = C.c_uint64()
+        self.ctx._check(self.ctx.L.fg_index_keep_targets(self.ctx.h, int(world), int(rank), C.byref(n)))
+        return n.value
+
+    def shard(self):
+        """(world, rank) of the restriction; (1, 0) for the whole index"""
+        w, r = C.c_uint32(), C.c_uint32()
+        self.ctx._check(self.ctx.L.fg_index_shard(self.ctx.h, C.byref(w), C.byref(r)))
+        return w.value, r.value
+
     def getSampleRate(self) -> float:
         return self.stats["sample_rate"] if self.stats else self._sample_rate_init
 
@@ -546,6 +571,62 @@ class OverlapDetector:
         self.ctx._check(L.fg_overlaps(self.ctx.h, C.byref(self.p), q.ctypes.data, len(q), maxOverlaps,
                                       int(bool(forceLocal)), C.byref(b)))
         return OverlapResult(L, q, b)
+
+    # ---- option B: index sharded by target read (flye_amd/dist.py) ----------------------------------------------
+    def probe_hits(self, query_ids):
+        """Seed collection only, against this context's (shard) index: (hits per query as uint64, device pointer
+        of the fg_seed_hit array -- query after query, each in emission order; valid until the next call on the
+        context --, number of hits)."""
+        q = np.ascontiguousarray(query_ids, dtype=np.uint32)
+        counts = np.zeros(len(q), np.uint64)
+        ptr, n = C.c_void_p(), C.c_uint64()
+        self.ctx._check(self.ctx.L.fg_probe_hits(self.ctx.h, q.ctypes.data, len(q), counts.ctypes.data, C.byref(ptr),
+                                                 C.byref(n)))
+        return counts, ptr.value or 0, n.value
+
+    def getSeqOverlapsFromHits(self, query_ids, counts, hits, forceLocal=False, maxOverlaps=0) -> OverlapResult:
+        """getSeqOverlaps of ``query_ids`` from the hits of n_src shards: ``counts[s, q]`` hits of query q from
+        source s; ``hits`` holds the sources one after another, inside a source the queries in list order (any order
+        inside a run) -- a device pointer (int), a torch tensor or a SEED_HIT_DTYPE numpy array (copied to the
+        context's device)."""
+        q = np.ascontiguousarray(query_ids, dtype=np.uint32)
+        cnt = np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1, len(q)) if len(q) else \
+            np.zeros((max(1, len(counts)), 0), np.uint64)
+        keep = None
+        if isinstance(hits, (int, np.integer)):
+            ptr = int(hits)
+        else:
+            import torch
+            dev = torch.device("cuda", self.ctx_device())
+            if isinstance(hits, np.ndarray):
+                hits = torch.from_numpy(np.ascontiguousarray(hits, SEED_HIT_DTYPE).view(np.int32).copy())
+            t = hits.reshape(-1)
+            if t.numel() != 3 * int(cnt.sum()):
+                raise FlyeGpuError(-3, f"{t.numel() // 3} hits given, counts add up to {int(cnt.sum())}")
+            keep = t.to(dev, dtype=torch.int32).contiguous() if t.numel() else torch.zeros(3, dtype=torch.int32, device=dev)
+            torch.cuda.synchronize(dev)          # the library reads it on its own stream
+            ptr = keep.data_ptr()
+        b = OverlapBatch()
+        L = self.ctx.L
+        self.ctx._check(L.fg_overlaps_from_hits(self.ctx.h, C.byref(self.p), q.ctypes.data, len(q), maxOverlaps,
+                                                int(bool(forceLocal)), cnt.shape[0], cnt.ctypes.data, ptr or None,
+                                                C.byref(b)))
+        del keep
+        return OverlapResult(L, q, b)
+
+    def ctx_device(self) -> int:
+        return getattr(self.ctx, "device", 0)
+
+
+def seed_hits_to_host(ptr: int, n: int, device: int = 0) -> np.ndarray:
+    """Copy of n fg_seed_hit records at device pointer ``ptr`` (what probe_hits returns) as a SEED_HIT_DTYPE array."""
+    if not n:
+        return np.empty(0, SEED_HIT_DTYPE)
+    import torch
+    arr = {"shape": (3 * n,), "typestr": "<i4", "data": (int(ptr), False), "version": 2}
+    holder = type("_DevHits", (), {"__cuda_array_interface__": arr})()
+    t = torch.as_tensor(holder, device=torch.device("cuda", device))
+    return t.cpu().numpy().view(SEED_HIT_DTYPE).copy()
 
 
 def seq_name(read_names, first_id, rec_id) -> str:

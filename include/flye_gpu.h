@@ -195,6 +195,7 @@ int fg_index_device_arrays(fg_ctx* ctx, uint64_t* n_keys, uint64_t* n_entries, u
 /* VertexIndex::clear() (vertex_index.cpp:486-496) */
 int fg_clear_index(fg_ctx* ctx);
 
+
 /* Read-only export of the built index for parity tests: keys ascending,
  * key_off[n_keys+1] into entries; an entry is (record_index << 32) | position
  * with record_index = FastaRecord id - first_seq_id, i.e. the same order as the
@@ -277,6 +278,47 @@ int fg_overlaps(fg_ctx* ctx, const struct fg_detector_params* p,
                 int32_t max_overlaps, uint8_t force_local,
                 struct fg_overlap_batch* out);
 void fg_release_batch(struct fg_overlap_batch* b);
+
+/* Option B of the multi-GPU layout: the index sharded by TARGET read.  Every rank keeps the list
+ * entries of the target reads it owns, probes ALL queries against that shard (fg_probe_hits) and sends each query's
+ * seed hits to the query's owner, which restores the reference's emission order and runs the rest of getSeqOverlaps
+ * on them (fg_overlaps_from_hits).
+ *
+ * fg_index_keep_targets restricts a complete index (a build, an option-A gather or an import) to the entries whose
+ * target read index i = (record id - first_seq_id) >> 1 has i % world == rank.  Each key's list stays ascending, the
+ * entry array shrinks to the kept entries (the memory goes back to the device).  Keys, the lookup table, the
+ * repetitive k-mers and getSampleRate() are kept as they are: minimizer mode takes the sample rate over the WHOLE
+ * index (vertex_index.cpp:480-482), and it feeds the divergence estimate (overlap.cpp:420).  A restricted context
+ * refuses fg_overlaps and fgb_create (FG_ERR_STATE): its lists hold 1/world of the targets.  A new build, an import
+ * or fg_clear_index lifts the restriction.  world == 1 changes nothing; rank >= world is FG_ERR_ARG; no index is
+ * FG_ERR_STATE; a second restriction to another (world, rank) is FG_ERR_STATE.  *n_entries_kept may be NULL.
+ * fg_index_shard reports the restriction (world = 1, rank = 0 when there is none). */
+int fg_index_keep_targets(fg_ctx* ctx, uint32_t world, uint32_t rank, uint64_t* n_entries_kept);
+int fg_index_shard(const fg_ctx* ctx, uint32_t* world, uint32_t* rank);
+
+/* One seed hit as getSeqOverlaps collects it (overlap.cpp:176-196): KmerMatch{curPos, extPos, extId}, the target
+ * side in the query k-mer's orientation (vertex_index.h:158-174). */
+struct fg_seed_hit { int32_t cur_pos; int32_t ext_pos; uint32_t ext_id; };
+
+/* Seed collection only, against this context's (shard) index: hit_counts[q] per query to the host; the hits in
+ * device memory owned by the context (*d_hits, *n_hits in total; valid until the next call on the context), query
+ * after query in list order, each query's in emission order (ascending curPos, then ascending stored global
+ * position; the trivial self hit dropped, overlap.cpp:188-190).  Queries live in the container fg_set_queries gave,
+ * if any.  FG_ERR_NOMEM when the hits do not fit the device. */
+int fg_probe_hits(fg_ctx* ctx, const uint32_t* query_ids, uint32_t n_queries, uint64_t* hit_counts,
+                  const struct fg_seed_hit** d_hits, uint64_t* n_hits);
+
+/* getSeqOverlaps for query_ids, as fg_overlaps returns it on the FULL index, from the seed hits that n_src index
+ * shards (fg_probe_hits) produced for them.  d_hits (device memory of this context's device) holds the sources one
+ * after another and, inside source s, the queries in list order, hit_counts[s * n_queries + q] hits each; the order
+ * of the hits inside one (source, query) run is arbitrary.  The receiver restores the reference's emission order
+ * (curPos, stored record, stored position) on the device; this context's own index supplies the repetitive query
+ * positions (overlap.cpp:407-413) and must hold the same keys and repetitive k-mers as the shards (any shard of the
+ * same index, or the full index).  FG_ERR_ARG for a hit outside its query or target. */
+int fg_overlaps_from_hits(fg_ctx* ctx, const struct fg_detector_params* p, const uint32_t* query_ids,
+                          uint32_t n_queries, int32_t max_overlaps, uint8_t force_local, uint32_t n_src,
+                          const uint64_t* hit_counts, const struct fg_seed_hit* d_hits,
+                          struct fg_overlap_batch* out);
 
 /* Per-kernel device time of the most recent fg_overlaps / build call, measured
  * with hipEvents on the library's own stream.  names[i] are static strings. */
