@@ -391,6 +391,9 @@ int fg_clear_index(fg_ctx* c)
 		c->indexBuilt = false;
 		c->indexBuild.reset();
 		c->gathering = false;
+		c->scattering = false;
+		c->splitWorld = 0;
+		c->sCounts.release(); c->sEntries.release();
 		c->shardWorld = 1; c->shardRank = 0;
 		c->gKeys.release(); c->gKeyOff.release(); c->gEntries.release(); c->gRepKeys.release();
 		c->dKeys.release(); c->dKeyOff.release(); c->dEntries.release(); c->dRepKeys.release();
@@ -449,7 +452,35 @@ int fg_index_shard(const fg_ctx* c, uint32_t* world, uint32_t* rank)
 	return FG_OK;
 }
 
-int fg_probe_hits(fg_ctx* c, const uint32_t* query_ids, uint32_t n_queries, uint64_t* hit_counts,
+int fg_index_piece_split(fg_ctx* c, uint32_t world, const uint64_t** d_counts, const uint64_t** d_entries,
+						 uint64_t* dest_totals)
+{
+	if (!c || !d_counts || !d_entries || !dest_totals) return FG_ERR_ARG;
+	return guarded(c, [&]()
+	{
+		HIP_CHECK(hipSetDevice(c->device));
+		fgIndexPieceSplit(c, world, (const u64**)d_counts, (const u64**)d_entries, (u64*)dest_totals);
+	});
+}
+
+int fg_index_scatter_begin(fg_ctx* c, uint32_t world, uint32_t rank, uint64_t n_keys, uint64_t n_shard_entries,
+						   uint64_t n_repetitive, uint64_t** full)
+{
+	if (!c || !full) return FG_ERR_ARG;
+	return guarded(c, [&]()
+	{
+		HIP_CHECK(hipSetDevice(c->device));
+		fgIndexScatterBegin(c, world, rank, n_keys, n_shard_entries, n_repetitive, (u64**)full);
+	});
+}
+
+int fg_index_scatter_end(fg_ctx* c, float sample_rate)
+{
+	if (!c) return FG_ERR_ARG;
+	return guarded(c, [&]() { HIP_CHECK(hipSetDevice(c->device)); fgIndexScatterEnd(c, sample_rate); });
+}
+
+int fg_probe_hits(fg_ctx* c,const uint32_t* query_ids, uint32_t n_queries, uint64_t* hit_counts,
 				  const struct fg_seed_hit** d_hits, uint64_t* n_hits)
 {
 	if (!c || !d_hits || !n_hits || (n_queries && (!query_ids || !hit_counts))) return FG_ERR_ARG;

@@ -334,6 +334,14 @@ struct fg_ctx {
 	bool gathering = false;
 	DevBuf<u64> gKeys, gKeyOff, gEntries, gRepKeys;
 	u64 gNKeys = 0, gNEntries = 0, gNRep = 0;
+	// option B built directly (fg_index_piece_split / fg_index_scatter_begin / _end): the piece's per-(destination,
+	// key) entry counts (splitWorld rows of nKeys, + 1 element) and its entries in destination-major order;
+	// splitWorld == 0: no split at hand.  Between scatter_begin and _end the piece sits in the g* buffers above and
+	// the context's arrays are the shard's, being filled by the caller's all-to-all
+	u32 splitWorld = 0;
+	DevBuf<u64> sCounts, sEntries;
+	bool scattering = false;
+	u32 scatterWorld = 1, scatterRank = 0;
 
 	// overlap-stage scratch (grow-only)
 	DevBuf<u32> dQuery;			// query record indices
@@ -662,6 +670,11 @@ struct RecvHits {
 void fgOverlaps(fg_ctx* c, const fg_detector_params* p, const u32* queryIds, u32 nq, i32 maxOverlaps,
 				uint8_t forceLocal, fg_overlap_batch* out, const RecvHits* recv = nullptr);
 void fgIndexKeepTargets(fg_ctx* c, u32 world, u32 rank, u64* nKept);
+// option B without the full entry array: piece -> per-destination parts -> shard (fg_index.hip)
+#define FG_SPLIT_MAX_WORLD 128		// k_split_*: world * 64 cursors of 4 bytes + world bases in one wave's LDS
+void fgIndexPieceSplit(fg_ctx* c, u32 world, const u64** dCounts, const u64** dEntries, u64* destTotals);
+void fgIndexScatterBegin(fg_ctx* c, u32 world, u32 rank, u64 nKeys, u64 nShardEntries, u64 nRep, u64** full);
+void fgIndexScatterEnd(fg_ctx* c, float sampleRate);
 void fgProbeHits(fg_ctx* c, const u32* queryIds, u32 nq, u64* hitCounts, const fg_seed_hit** dHits, u64* nHits);
 void fgOverlapsFromHits(fg_ctx* c, const fg_detector_params* p, const u32* queryIds, u32 nq, i32 maxOverlaps,
 						uint8_t forceLocal, u32 nSrc, const u64* hitCounts, const fg_seed_hit* dHits, fg_overlap_batch* out);

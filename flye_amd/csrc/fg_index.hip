@@ -817,6 +817,9 @@ void clearIndex(fg_ctx* c)
 	c->indexBuilt = false;
 	c->gathering = false;
 	c->shardWorld = 1; c->shardRank = 0;
+	c->scattering = false;
+	c->splitWorld = 0;
+	c->sCounts.release(); c->sEntries.release();
 	c->gKeys.release(); c->gKeyOff.release(); c->gEntries.release(); c->gRepKeys.release();
 	c->dKeys.release(); c->dKeyOff.release(); c->dEntries.release(); c->dRepKeys.release();
 	c->dTable.release(); c->dIndexedBits.release();
@@ -1558,5 +1561,294 @@ void fgIndexKeepTargets(fg_ctx* c, u32 world, u32 rank, u64* nKept)
 	c->table.keyOff = (const unsigned long long*)c->dKeyOff.p;
 	c->shardWorld = world; c->shardRank = rank;
 	if (nKept) *nKept = c->nEntries;
+	c->timer.collect();
+}
+
+// ---- option B built directly: key-range piece -> per-destination parts -> target shard ------------------------------
+// fg_index_keep_targets needs the whole index on the rank first.  Here every rank splits ITS piece (key range s, keys and
+// lists ascending) by target owner; the parts travel with one all-to-all; what arrives from the sources in rank order
+// = key order is already the shard's CSR entry array, and the received count rows, scanned, are its list offsets.
+//
+// The split, for gfx950: one wave per block of 64 consecutive keys.  The block's entries are contiguous, so the wave
+// walks them 64 at a time with coalesced loads, whatever the list lengths are (a long list simply takes more rounds
+// of all 64 lanes; a thread per key would leave 63 lanes idle on it).  Each lane finds its entry's key in the block's
+// 65 list bounds (LDS, binary search).
+//   k_split_count  counts for ALL destinations in one pass: LDS counters [world][64], written out row by row;
+//   k_split_scan   one exclusive scan over the flattened world x nKeys matrix (+ 1): the start of every
+//                  (destination, key) run in the split array, destination major;
+//   k_split_copy   the same walk; a lane's rank inside its (key, destination) run is the popcount of the lower lanes
+//                  of the same destination (ballot) inside the key's lane interval -- lane order is list order, so the
+//                  partition is stable; the runs' cursors live in LDS between rounds.  The entries of one destination
+//                  in a round go to consecutive addresses (key major), so the stores coalesce per destination.
+namespace {
+
+// list bounds of the block's keys into LDS (clamped to the entry count: nothing below reads past the array even
+// through offsets that are not what the build left); returns the number of keys in the block
+__device__ __forceinline__ u32 split_load_bounds(const u64* __restrict__ keyOff, u64 nKeys, u64 nEntries, u64 j0, u64* sOff)
+{
+	const u32 lane = threadIdx.x;
+	const u32 nk = (u32)(nKeys - j0 < 64 ? nKeys - j0 : 64);
+	if (lane <= nk) { const u64 o = keyOff[j0 + lane]; sOff[lane] = o < nEntries ? o : nEntries; }
+	if (lane == 0) { const u64 o = keyOff[j0 + nk]; sOff[nk] = o < nEntries ? o : nEntries; }
+	return nk;
+}
+
+// the key (inside the block) of entry e, sOff[0] <= e < sOff[nk]: the last one whose list starts at or before e
+__device__ __forceinline__ u32 split_key_of(const u64* sOff, u32 nk, u64 e)
+{
+	u32 lo = 0, hi = nk;
+	while (hi - lo > 1) { const u32 m = (lo + hi) >> 1; if (sOff[m] <= e) lo = m; else hi = m; }
+	return lo;
+}
+
+__global__ void __launch_bounds__(64) k_split_count(const u64* __restrict__ keyOff, u64 nKeys, const u64* __restrict__ entries,
+													 u64 nEntries, u32 world, u64* __restrict__ counts)
+{
+	extern __shared__ u64 splitSmem[];
+	u64* sOff = splitSmem;						// 65 (+ 1 pad)
+	u32* cnt = (u32*)(splitSmem + 66);			// [world][64]
+	const u32 lane = threadIdx.x;
+	const u64 j0 = (u64)blockIdx.x * 64;
+	const u32 nk = split_load_bounds(keyOff, nKeys, nEntries, j0, sOff);
+	for (u32 i = lane; i < world * 64; i += 64) cnt[i] = 0;
+	__syncthreads();
+	const u64 eBeg = sOff[0], eEnd = sOff[nk];
+	for (u64 base = eBeg; base < eEnd; base += 64)
+	{
+		const u64 e = base + lane;
+		if (e < eEnd)
+		{
+			const u32 d = (u32)(entries[e] >> 33) % world;
+			atomicAdd(&cnt[d * 64 + split_key_of(sOff, nk, e)], 1u);
+		}
+	}
+	__syncthreads();
+	if (lane < nk)
+		for (u32 d = 0; d < world; ++d) counts[(u64)d * nKeys + j0 + lane] = cnt[d * 64 + lane];
+}
+
+__global__ void __launch_bounds__(64) k_split_copy(const u64* __restrict__ keyOff, u64 nKeys, const u64* __restrict__ entries,
+													u64 nEntries, u32 world, const u64* __restrict__ offs, u64* __restrict__ out)
+{
+	extern __shared__ u64 splitSmem[];
+	u64* sOff = splitSmem;						// 65 (+ 1 pad)
+	u64* sBase = splitSmem + 66;				// [world]: where destination d's part of this block starts
+	u32* cur = (u32*)(splitSmem + 66 + world);	// [world][64]: next free slot of run (d, key), relative to sBase[d]
+	const u32 lane = threadIdx.x;
+	const u64 j0 = (u64)blockIdx.x * 64;
+	const u32 nk = split_load_bounds(keyOff, nKeys, nEntries, j0, sOff);
+	for (u32 d = lane; d < world; d += 64) sBase[d] = offs[(u64)d * nKeys + j0];
+	__syncthreads();
+	for (u32 d = 0; d < world; ++d)
+		cur[d * 64 + lane] = lane < nk ? (u32)(offs[(u64)d * nKeys + j0 + lane] - sBase[d]) : 0u;
+	__syncthreads();
+	const u64 eBeg = sOff[0], eEnd = sOff[nk];
+	for (u64 base = eBeg; base < eEnd; base += 64)
+	{
+		const u64 e = base + lane;
+		const bool valid = e < eEnd;
+		u64 v = 0, segMask = 0;
+		u32 jl = 0, d = world;
+		if (valid)
+		{
+			v = entries[e];
+			d = (u32)(v >> 33) % world;
+			jl = split_key_of(sOff, nk, e);
+			// the lanes of this round that hold entries of the same key: [a, b]
+			const u64 lo = sOff[jl], hi = sOff[jl + 1];
+			const u32 a = lo > base ? (u32)(lo - base) : 0u;
+			const u32 b = hi < base + 64 ? (u32)(hi - base) - 1u : 63u;
+			segMask = (b >= 63 ? ~0ULL : ((2ULL << b) - 1ULL)) & ~((1ULL << a) - 1ULL);
+		}
+		u64 remaining = __ballot(valid);
+		while (remaining)		// one turn per destination present in the round (wave-uniform)
+		{
+			const int lead = __ffsll((unsigned long long)remaining) - 1;
+			const u32 dd = (u32)__shfl((int)d, lead);
+			const bool mine = valid && d == dd;
+			const u64 m = __ballot(mine);
+			u32 c0 = 0, rank = 0, tot = 0;
+			if (mine)
+			{
+				const u64 mm = m & segMask;
+				rank = (u32)__popcll(mm & ((1ULL << lane) - 1ULL));
+				tot = (u32)__popcll(mm);
+				c0 = cur[dd * 64 + jl];
+				const u64 pos = sBase[dd] + c0 + rank;
+				if (pos < nEntries) out[pos] = v;
+			}
+			__syncthreads();		// every lane of the run has read its cursor before the run's first lane moves it
+			if (mine && rank == 0) cur[dd * 64 + jl] = c0 + tot;
+			remaining &= ~m;
+		}
+		__syncthreads();
+	}
+}
+
+__global__ void k_split_totals(const u64* __restrict__ offs, u64 nKeys, u32 world, u64* __restrict__ tot)
+{
+	const u32 d = blockIdx.x * blockDim.x + threadIdx.x;
+	if (d < world) tot[d] = offs[(u64)(d + 1) * nKeys] - offs[(u64)d * nKeys];
+}
+
+// what scatter_end checks of the received entries, after k_check_csr has passed (the offsets are then safe to read
+// through).  bad[0]: entries of another rank's targets; bad[1]: positions e with entries[e] >= entries[e + 1];
+// bad[2]: those of them that sit on the last entry of one list and the first of the next (the only place a descent
+// may be).  Every list is strictly ascending exactly when bad[1] == bad[2].
+__global__ void k_shard_check_entries(const u64* __restrict__ entries, u64 n, u32 world, u32 rank, unsigned long long* __restrict__ bad)
+{
+	const u64 e = (u64)blockIdx.x * WG + threadIdx.x;
+	bool foreign = false, desc = false;
+	if (e < n)
+	{
+		const u64 v = entries[e];
+		foreign = (u32)(v >> 33) % world != rank;
+		desc = e + 1 < n && v >= entries[e + 1];
+	}
+	const u64 bf = __ballot(foreign), bd = __ballot(desc);
+	if ((threadIdx.x & 63) == 0)
+	{
+		if (bf) atomicAdd(&bad[0], (unsigned long long)__popcll(bf));
+		if (bd) atomicAdd(&bad[1], (unsigned long long)__popcll(bd));
+	}
+}
+
+__global__ void k_shard_check_bounds(const u64* __restrict__ keyOff, u64 nKeys, const u64* __restrict__ entries,
+									 unsigned long long* __restrict__ bad)
+{
+	const u64 j = (u64)blockIdx.x * WG + threadIdx.x;
+	bool desc = false;
+	if (j < nKeys)
+	{
+		const u64 o = keyOff[j];
+		desc = o > 0 && o < keyOff[j + 1] && entries[o - 1] >= entries[o];
+	}
+	const u64 bd = __ballot(desc);
+	if ((threadIdx.x & 63) == 0 && bd) atomicAdd(&bad[2], (unsigned long long)__popcll(bd));
+}
+
+size_t splitLdsBytes(u32 world) { return (size_t)(66 + world) * 8 + (size_t)world * 64 * 4; }
+
+} // namespace
+
+void fgIndexPieceSplit(fg_ctx* c, u32 world, const u64** dCounts, const u64** dEntries, u64* destTotals)
+{
+	if (world == 0 || world > FG_SPLIT_MAX_WORLD)
+		throw FgError{FG_ERR_ARG, "piece_split: world must be between 1 and " + std::to_string(FG_SPLIT_MAX_WORLD)};
+	if (!c->indexBuilt || c->gathering || c->scattering)
+		throw FgError{FG_ERR_STATE, "piece_split needs a finished piece (fg_index_finish)"};
+	if (c->shardWorld != 1) throw FgError{FG_ERR_STATE, "piece_split: the index is already restricted to a shard"};
+	hipStream_t s = c->stream;
+	c->timer.reset();
+	c->splitWorld = 0;
+	const u64 nKeys = c->nKeys, nEnt = c->nEntries, nCnt = (u64)world * nKeys + 1;
+	if ((nKeys + 63) / 64 > 0x7fffffffULL) throw FgError{FG_ERR_UNSUPPORTED, "piece_split: too many keys"};
+	try
+	{
+		c->sCounts.alloc(nCnt); c->sEntries.alloc(nEnt);
+		DevBuf<u64> offs, scratch, tot;
+		offs.alloc(nCnt); scratch.alloc(fgprim::scanScratchElems(nCnt)); tot.alloc(world);
+		// one extra zero element so that the exclusive scan also yields the total
+		HIP_CHECK(hipMemsetAsync(c->sCounts.p + (nCnt - 1), 0, 8, s));
+		const unsigned blocks = (unsigned)((nKeys + 63) / 64);
+		const size_t lds = splitLdsBytes(world);
+		if (nKeys)
+		{
+			ScopedK t(c->timer, "k_split_count");
+			hipLaunchKernelGGL(k_split_count, blocks, 64, lds, s, c->dKeyOff.p, nKeys, c->dEntries.p, nEnt, world, c->sCounts.p);
+		}
+		{ ScopedK t(c->timer, "k_split_scan");
+		  fgprim::scan<u64>(s, c->sCounts.p, offs.p, nCnt, false, scratch.p); }
+		if (nKeys && nEnt)
+		{
+			ScopedK t(c->timer, "k_split_copy");
+			hipLaunchKernelGGL(k_split_copy, blocks, 64, lds, s, c->dKeyOff.p, nKeys, c->dEntries.p, nEnt, world, offs.p, c->sEntries.p);
+		}
+		hipLaunchKernelGGL(k_split_totals, 1, FG_SPLIT_MAX_WORLD, 0, s, offs.p, nKeys, world, tot.p);
+		HIP_CHECK(hipMemcpyAsync(destTotals, tot.p, (size_t)world * 8, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(hipStreamSynchronize(s));
+		HIP_CHECK(hipGetLastError());
+	}
+	catch (...)
+	{
+		(void)hipStreamSynchronize(s);
+		c->sCounts.release(); c->sEntries.release();
+		throw;
+	}
+	c->splitWorld = world;
+	*dCounts = c->sCounts.p; *dEntries = c->sEntries.p;
+	c->timer.collect();
+}
+
+void fgIndexScatterBegin(fg_ctx* c, u32 world, u32 rank, u64 nKeys, u64 nShardEntries, u64 nRep, u64** full)
+{
+	if (world == 0 || rank >= world) throw FgError{FG_ERR_ARG, "scatter_begin: rank must be below world"};
+	if (!c->indexBuilt || c->gathering || c->scattering)
+		throw FgError{FG_ERR_STATE, "scatter needs a finished piece (fg_index_finish)"};
+	if (c->shardWorld != 1) throw FgError{FG_ERR_STATE, "scatter_begin: the index is already restricted to a shard"};
+	if (c->splitWorld != world) throw FgError{FG_ERR_STATE, "scatter_begin: call fg_index_piece_split for this world first"};
+	c->timer.reset();
+	c->indexBuilt = false;
+	// the piece's lookup structures go before the shard's arrays come
+	c->dTable.release(); c->dIndexedBits.release();
+	c->tableSlots = 0;
+	c->gKeys.swap(c->dKeys); c->gKeyOff.swap(c->dKeyOff); c->gEntries.swap(c->dEntries); c->gRepKeys.swap(c->dRepKeys);
+	c->gNKeys = c->nKeys; c->gNEntries = c->nEntries; c->gNRep = c->nRep;
+	try
+	{
+		c->dKeys.alloc(nKeys); c->dKeyOff.alloc(nKeys + 1); c->dEntries.alloc(nShardEntries); c->dRepKeys.alloc(nRep);
+	}
+	catch (...) { clearIndex(c); throw; }
+	c->nKeys = nKeys; c->nEntries = nShardEntries; c->nRep = nRep;
+	c->scattering = true;
+	c->scatterWorld = world; c->scatterRank = rank;
+	full[0] = c->dKeys.p; full[1] = c->dKeyOff.p; full[2] = c->dEntries.p; full[3] = c->dRepKeys.p;
+}
+
+void fgIndexScatterEnd(fg_ctx* c, float sampleRate)
+{
+	if (!c->scattering) throw FgError{FG_ERR_STATE, "no scatter in progress"};
+	hipStream_t s = c->stream;
+	c->scattering = false;
+	c->splitWorld = 0;
+	c->gKeys.release(); c->gKeyOff.release(); c->gEntries.release(); c->gRepKeys.release();
+	c->sCounts.release(); c->sEntries.release();
+	c->sampleRate = sampleRate;
+	const u32 world = c->scatterWorld, rank = c->scatterRank;
+	const u64 nKeys = c->nKeys, nEnt = c->nEntries;
+	try
+	{
+		{
+			// key_off holds the per-key counts of the shard: exclusive scan in place, the extra element gives the total
+			DevBuf<u64> scratch;
+			scratch.alloc(fgprim::scanScratchElems(nKeys + 1));
+			HIP_CHECK(hipMemsetAsync(c->dKeyOff.p + nKeys, 0, 8, s));
+			{ ScopedK t(c->timer, "k_scatter_scan");
+			  fgprim::scan<u64>(s, c->dKeyOff.p, c->dKeyOff.p, nKeys + 1, false, scratch.p); }
+			HIP_CHECK(hipStreamSynchronize(s));
+		}
+		checkCsr(c);
+		DevBuf<unsigned long long> bad;
+		bad.alloc(3);
+		HIP_CHECK(hipMemsetAsync(bad.p, 0, 24, s));
+		{
+			ScopedK t(c->timer, "k_shard_check");
+			if (nEnt) hipLaunchKernelGGL(k_shard_check_entries, gridFor(nEnt), WG, 0, s, c->dEntries.p, nEnt, world, rank, bad.p);
+			if (nKeys) hipLaunchKernelGGL(k_shard_check_bounds, gridFor(nKeys), WG, 0, s, c->dKeyOff.p, nKeys, c->dEntries.p, bad.p);
+		}
+		unsigned long long hb[3];
+		HIP_CHECK(hipMemcpyAsync(hb, bad.p, 24, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(hipStreamSynchronize(s));
+		if (hb[0]) throw FgError{FG_ERR_ARG, "scatter_end: " + std::to_string(hb[0]) + " entries belong to another rank's target reads"};
+		if (hb[1] != hb[2]) throw FgError{FG_ERR_ARG, "scatter_end: a list is not in ascending order"};
+		fgIndexLookupStructures(c, false);
+	}
+	catch (...)
+	{
+		(void)hipStreamSynchronize(s);
+		clearIndex(c);
+		throw;
+	}
+	c->shardWorld = world; c->shardRank = rank;
 	c->timer.collect();
 }

@@ -23,8 +23,22 @@ per-(destination, query) hit counts and then the 12-byte hits go to the queries'
 ``all_to_all_single`` (device to device with nccl = RCCL, through host copies with gloo), and each owner restores
 the reference's emission order on the device and runs the rest of getSeqOverlaps (``fg_overlaps_from_hits``).
 Bit-exact against the replicated index by test (tests/test_option_b.py: W shards as W contexts on one GPU, and two
-gloo processes).  What the per-rank memory saving amounts to at CHM13 scale is still arithmetic: the
-gather lands the whole index on every rank before keep_targets cuts it, and no multi-GPU run has been measured.
+gloo processes).  ``build_index_option_b`` lands the whole index on every rank before keep_targets cuts it, so its
+build peak is that of option A.
+
+Option B built directly (``build_index_option_b_direct``): the same key-range build up to ``finish``, then
+``scatter_pieces_inplace`` instead of the all-gather.  Every rank splits its piece by target owner on the device
+(``fg_index_piece_split``: a world x keys count matrix and the entries in destination-major order), keys and repetitive
+keys are replicated by broadcasts, and the count rows and entry segments travel with one ``all_to_all_single`` each
+straight into the shard's own arrays (``fg_index_scatter_begin``); sources arrive in rank order = key order, so what
+lands is the shard's CSR, and ``fg_index_scatter_end`` scans the counts into offsets, checks the arrays on the device
+and builds the lookup structures.  With K keys, R repetitive keys, table bytes T, bits B of the whole index, a piece
+of (K_s, E_s, R_s) with table T_s and a shard of E_shard entries, the library holds above the reads at most
+    max(P + T_s + B + 8 E_s + 16 (W K_s + 1),  P + 8 E_s + 8 (W K_s + 1) + S,  S + T + B) + scan scratch,
+    P = 8 (2 K_s + 1 + E_s + R_s),  S = 8 (2 K + 1 + R + E_shard)
+-- no term in the total entry count.  MEASURED on one GPU (tests/test_option_b_direct.py: W = 4 on 52 Mbp, asserted;
+the gather + keep_targets path exceeds the bound on the same input); the figure at CHM13 scale stays
+arithmetic, and no run on more than one GPU has been measured.
 """
 from __future__ import annotations
 
@@ -236,21 +250,11 @@ def gather_pieces_inplace(vi, rank: int, world: int, on_device: bool, sample_rat
     return (K, E, R), moved
 
 
-def build_index_sharded(vi, cfg: dict, rank: int, world: int, on_device: bool):
-    """The build main_assemble.cpp:195-223 selects, sharded over the ranks of the default process group
-    (SURVEY.md §8e).  ``on_device``: collectives on device memory (nccl = RCCL over xGMI); otherwise through host
-    copies (gloo rehearsal).
-
-    * solid k-mers: the key bins are cut into ``world`` ranges holding equal numbers of k-mer positions
-      (``fg_index_kmer_hist``, identical on every rank); rank r keeps the exact counters of ITS range only (an
-      eighth of the 4^k array at 8 ranks) and counts those k-mers over all reads; then, batch of reads by batch
-      (bounded scratch), every rank writes the frequencies it knows, an all-reduce makes the array complete, and
-      every rank runs the per-read selection on it (replicated: it is cheap and leaves every rank with the same
-      selection bits, so nothing else of the selection is exchanged);
-    * minimizers: the selection needs no counters and no exchange; ranges are balanced on the accepted positions;
-    * rank r sorts and run-length encodes its range (the same range its counters cover); all-reduce of
-      filterFrequentKmers' two sums; finish; all-gather of the CSR pieces in place.
-    Returns the index statistics plus what the collectives moved."""
+def _build_piece(vi, cfg: dict, rank: int, world: int, on_device: bool):
+    """The key-range part of a sharded build, up to and including ``finish``: this rank's piece is in the context.
+    -> (statistics so far, (bin ranges, piece sizes, frequency all-reduce bytes, (t0, t1, t2)), sample_rate_of,
+    whether collectives run).  What follows -- the all-gather of option A, the scatter of option B built directly --
+    is the caller's."""
     import torch
     import torch.distributed as td
     cuda = torch.device("cuda", torch.cuda.current_device())
@@ -292,6 +296,25 @@ def build_index_sharded(vi, cfg: dict, rank: int, world: int, on_device: bool):
             return float(total_bases / np.float32(E)) if E else float("inf")
         return vi._sample_rate_init
 
+    return st, (ranges, (nk, ne, nr), freq_bytes, (t0, t1, t2)), sample_rate_of, coll
+
+
+def build_index_sharded(vi, cfg: dict, rank: int, world: int, on_device: bool):
+    """The build main_assemble.cpp:195-223 selects, sharded over the ranks of the default process group
+    (SURVEY.md §8e).  ``on_device``: collectives on device memory (nccl = RCCL over xGMI); otherwise through host
+    copies (gloo rehearsal).
+
+    * solid k-mers: the key bins are cut into ``world`` ranges holding equal numbers of k-mer positions
+      (``fg_index_kmer_hist``, identical on every rank); rank r keeps the exact counters of ITS range only (an
+      eighth of the 4^k array at 8 ranks) and counts those k-mers over all reads; then, batch of reads by batch
+      (bounded scratch), every rank writes the frequencies it knows, an all-reduce makes the array complete, and
+      every rank runs the per-read selection on it (replicated: it is cheap and leaves every rank with the same
+      selection bits, so nothing else of the selection is exchanged);
+    * minimizers: the selection needs no counters and no exchange; ranges are balanced on the accepted positions;
+    * rank r sorts and run-length encodes its range (the same range its counters cover); all-reduce of
+      filterFrequentKmers' two sums; finish; all-gather of the CSR pieces in place.
+    Returns the index statistics plus what the collectives moved."""
+    st, (ranges, (nk, ne, nr), freq_bytes, (t0, t1, t2)), sample_rate_of, coll = _build_piece(vi, cfg, rank, world, on_device)
     (K, E, R), moved = gather_pieces_inplace(vi, rank, world, on_device, sample_rate_of, force=coll)
     t3 = time.perf_counter()
     st.update(vi.stats)
@@ -308,6 +331,130 @@ def build_index_option_b(vi, cfg: dict, rank: int, world: int, on_device: bool):
     reads this rank owns.  Statistics and getSampleRate() stay those of the whole index."""
     st = build_index_sharded(vi, cfg, rank, world, on_device)
     st["shard_entries"] = vi.keep_targets(world, rank)
+    vi.stats = st
+    return st
+
+
+# ---- option B built directly: key-range pieces -> per-destination parts -> target shards ---------------------------
+def split_piece_host(keys, key_off, entries, world: int):
+    """Host reference of ``fg_index_piece_split``: the piece (keys, key_off[len(keys) + 1], entries ascending per
+    key) partitioned by target owner ((entry >> 33) % world).  -> (counts[world, n_keys] = entries of key j owned by
+    rank d, the entries destination major / key major inside a destination / list order inside a key,
+    totals[world] = entries per destination), all uint64."""
+    off = np.asarray(key_off).astype(np.int64)
+    ent = np.ascontiguousarray(entries, np.uint64)
+    nk = len(off) - 1
+    assert nk == len(keys) and (nk == 0 or int(off[-1]) == len(ent))
+    owner = ((ent >> np.uint64(33)) % np.uint64(world)).astype(np.int64)
+    slot = owner * nk + np.repeat(np.arange(nk, dtype=np.int64), np.diff(off))
+    counts = np.bincount(slot, minlength=world * nk).astype(np.uint64).reshape(world, nk)
+    return counts, ent[np.argsort(slot, kind="stable")], counts.sum(axis=1, dtype=np.uint64)
+
+
+def _all_to_all_dev(out, inp, out_splits, in_splits, on_device: bool, coll: bool):
+    """all_to_all_single of 1-d tensors with the given split sizes: on the tensors themselves (RCCL), or (gloo
+    rehearsal) through host copies; without collectives (one rank) the input is the output"""
+    import torch
+    import torch.distributed as td
+    if not coll:
+        out.copy_(inp)
+    elif on_device:
+        td.all_to_all_single(out, inp, output_split_sizes=out_splits, input_split_sizes=in_splits)
+    else:
+        h = torch.empty(out.numel(), dtype=out.dtype)
+        td.all_to_all_single(h, inp.cpu().contiguous(), output_split_sizes=out_splits, input_split_sizes=in_splits)
+        out.copy_(h)
+
+
+def exchange_split_parts(piece_keys, piece_rep, counts, split_entries, totals, rank: int, world: int, on_device: bool,
+                         alloc=None, force=False):
+    """The exchange of the direct option-B build, on int64 tensors (views of the context's device arrays in
+    ``scatter_pieces_inplace``; CPU tensors in the gloo rehearsal).  This rank gives its piece's keys and repetitive
+    keys, the flattened [world, n_keys] count matrix, the split entries and the entries per destination
+    (``fg_index_piece_split`` / ``split_piece_host``).  Sizes are exchanged first (one all-reduce: the pieces' sizes
+    and every rank's per-destination totals); keys and repetitive keys are replicated by broadcasts of each rank's
+    slice, as in ``gather_pieces_inplace``; the count rows and the entry segments go through one
+    ``all_to_all_single`` each.  Sources arrive in rank order = key order: the received counts are the shard's
+    per-key list lengths for all keys, the received entries ARE its entry array in CSR order.
+    ``alloc(K, E_shard, R)`` -> the destination tensors (keys[K], key_off[K + 1], entries[E_shard], repetitive[R]).
+    Returns (keys, key_off -- the COUNTS in [0, K), not yet scanned --, entries, repetitive, (K, E, R) of the whole
+    index, E_shard, bytes moved)."""
+    import torch
+    import torch.distributed as td
+    dev = piece_keys.device
+    red = dev if on_device else torch.device("cpu")
+    coll = world > 1 or force
+    nk, ne, nr = len(piece_keys), len(split_entries), len(piece_rep)
+    totals = [int(x) for x in np.asarray(totals)]
+    assert len(totals) == world and sum(totals) == ne and counts.numel() == world * nk
+    sizes = torch.zeros((world, 3 + world), dtype=torch.int64, device=red)
+    sizes[rank] = torch.tensor([nk, ne, nr] + totals, dtype=torch.int64, device=red)
+    if coll:
+        td.all_reduce(sizes)
+    sz = sizes.cpu().numpy()
+    K, E, R = (int(x) for x in sz[:, :3].sum(axis=0))
+    kb = np.concatenate([[0], np.cumsum(sz[:, 0])]).astype(np.int64)
+    rb = np.concatenate([[0], np.cumsum(sz[:, 2])]).astype(np.int64)
+    e_from = sz[:, 3 + rank]                                 # entries source s holds for this rank
+    e_shard = int(e_from.sum())
+    if alloc is None:
+        def alloc(K, e_shard, R):
+            return tuple(torch.empty(n, dtype=torch.int64, device=dev) for n in (K, K + 1, e_shard, R))
+    keys, off, ent, rep = alloc(K, e_shard, R)
+    if nk:
+        keys[kb[rank]:kb[rank + 1]] = piece_keys
+    if nr:
+        rep[rb[rank]:rb[rank + 1]] = piece_rep
+    moved = world * 8 * (3 + world)
+    if coll:
+        for r in range(world):
+            for arr, b in ((keys, kb), (rep, rb)):
+                if b[r + 1] > b[r]:
+                    _broadcast_dev(arr[b[r]:b[r + 1]], r, on_device)
+                    moved += int(b[r + 1] - b[r]) * 8
+    _all_to_all_dev(off[:K], counts, [int(x) for x in sz[:, 0]], [nk] * world, on_device, coll)
+    _all_to_all_dev(ent[:e_shard], split_entries, [int(x) for x in e_from], totals, on_device, coll)
+    moved += 8 * (world * nk + ne)
+    return keys, off, ent, rep, (K, E, R), e_shard, moved
+
+
+def scatter_pieces_inplace(vi, rank: int, world: int, on_device: bool, sample_rate_of, force=False):
+    """From the ranks' key-range pieces (what ``finish`` left in the contexts) straight to the ranks' target shards:
+    split on the device (``fg_index_piece_split``), ``exchange_split_parts`` into the arrays ``fg_index_scatter_begin``
+    allocates, ``fg_index_scatter_end`` (scan, device checks, lookup structures).  No rank allocates the full entry
+    array: DESIGN.md §6 has the peak.  ``sample_rate_of(E)`` gives VertexIndex::getSampleRate() for the whole index.
+    Returns ((K, E, R) of the whole index, this shard's entries, bytes moved)."""
+    import torch
+    cuda = torch.device("cuda", torch.cuda.current_device())
+    (nk, ne, nr), piece = vi.device_arrays()             # the piece's arrays stay where they are until scatter_end
+    cnt_ptr, ent_ptr, totals = vi.split_piece(world)
+
+    def alloc(K, e_shard, R):
+        full = vi.scatter_begin(world, rank, K, e_shard, R)
+        return _view(full[0], K, cuda), _view(full[1], K + 1, cuda), _view(full[2], e_shard, cuda), _view(full[3], R, cuda)
+
+    _, _, _, _, (K, E, R), e_shard, moved = exchange_split_parts(
+        _view(piece[0], nk, cuda), _view(piece[3], nr, cuda), _view(cnt_ptr, world * nk, cuda), _view(ent_ptr, ne, cuda),
+        totals, rank, world, on_device, alloc, force)
+    torch.cuda.synchronize()
+    vi.scatter_end(sample_rate_of(E))
+    vi.stats = dict(vi.stats or {}, selected_kmers=K, index_entries=E, repetitive_kmers=R, shard_entries=e_shard,
+                    sample_rate=float(np.float32(sample_rate_of(E))))
+    return (K, E, R), e_shard, moved
+
+
+def build_index_option_b_direct(vi, cfg: dict, rank: int, world: int, on_device: bool):
+    """Option B without the all-gather: the key-range build of ``build_index_sharded`` up to and including ``finish``,
+    then ``scatter_pieces_inplace``.  The context ends as after ``build_index_option_b`` -- the shard of the target
+    reads this rank owns, statistics and getSampleRate() those of the whole index -- but never held more entries
+    than its piece, the piece's split copy and its shard."""
+    st, (ranges, (nk, ne, nr), freq_bytes, (t0, t1, t2)), sample_rate_of, coll = _build_piece(vi, cfg, rank, world, on_device)
+    (K, E, R), e_shard, moved = scatter_pieces_inplace(vi, rank, world, on_device, sample_rate_of, force=coll)
+    t3 = time.perf_counter()
+    st.update(vi.stats)
+    st.update(bin_range=ranges[rank], piece=(int(nk), int(ne), int(nr)), shard_entries=e_shard,
+              collective_bytes=moved + 24 + freq_bytes, freq_allreduce_bytes=freq_bytes,
+              select_and_sort_s=t1 - t0, finish_s=t2 - t1, scatter_s=t3 - t2, build_seconds=t3 - t0)
     vi.stats = st
     return st
 

@@ -43,7 +43,8 @@ ABI_SYMBOLS = ["fg_abi_version", "fg_create", "fg_destroy", "fg_strerror", "fg_l
                "fg_index_selection_done", "fg_index_gather_begin", "fg_index_gather_end", "fg_memory_stats",
                "fg_import_index", "fg_index_device_arrays", "fg_clear_index", "fg_export_index", "fg_overlaps", "fg_release_batch",
                "fg_kernel_times", "fg_debug_sort_pairs", "fg_debug_edit_distances", "fg_align_cigar_ksw", "fg_release_cigars",
-               "fg_index_keep_targets", "fg_index_shard", "fg_probe_hits", "fg_overlaps_from_hits"]
+               "fg_index_keep_targets", "fg_index_shard", "fg_probe_hits", "fg_overlaps_from_hits",
+               "fg_index_piece_split", "fg_index_scatter_begin", "fg_index_scatter_end"]
 
 # struct fg_seed_hit: KmerMatch{curPos, extPos, extId} (overlap.cpp:176-196)
 SEED_HIT_DTYPE = np.dtype([("cur_pos", "<i4"), ("ext_pos", "<i4"), ("ext_id", "<u4")])
@@ -154,6 +155,9 @@ def load_library():
         L.fg_release_batch.argtypes = [C.POINTER(OverlapBatch)]
         L.fg_index_keep_targets.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
         L.fg_index_shard.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.fg_index_piece_split.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p]
+        L.fg_index_scatter_begin.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]
+        L.fg_index_scatter_end.argtypes = [C.c_void_p, C.c_float]
         L.fg_probe_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_void_p),
                                     C.POINTER(C.c_uint64)]
         L.fg_overlaps_from_hits.argtypes = [C.c_void_p, C.POINTER(DetectorParams), C.c_void_p, C.c_uint32, C.c_int32,
@@ -527,6 +531,29 @@ class VertexIndex:
         w, r = C.c_uint32(), C.c_uint32()
         self.ctx._check(self.ctx.L.fg_index_shard(self.ctx.h, C.byref(w), C.byref(r)))
         return w.value, r.value
+
+    # ---- option B built directly from the key-range pieces (flye_amd/dist.py::scatter_pieces_inplace) ------
+    SPLIT_MAX_WORLD = 128
+
+    def split_piece(self, world: int):
+        """fg_index_piece_split: the piece's entries partitioned by target owner.  -> (device pointer of the
+        world x n_keys count matrix, device pointer of the split entries, entries per destination [world])"""
+        cnt, ent = C.c_void_p(), C.c_void_p()
+        totals = np.zeros(max(int(world), 1), np.uint64)
+        self.ctx._check(self.ctx.L.fg_index_piece_split(self.ctx.h, int(world), C.byref(cnt), C.byref(ent),
+                                                        totals.ctypes.data))
+        return cnt.value or 0, ent.value or 0, totals
+
+    def scatter_begin(self, world: int, rank: int, n_keys: int, n_shard_entries: int, n_rep: int):
+        """fg_index_scatter_begin -> the shard's device pointers [keys, key_off (receives the counts), entries,
+        repetitive]"""
+        full = (C.c_void_p * 4)()
+        self.ctx._check(self.ctx.L.fg_index_scatter_begin(self.ctx.h, int(world), int(rank), int(n_keys),
+                                                          int(n_shard_entries), int(n_rep), full))
+        return [x or 0 for x in full]
+
+    def scatter_end(self, sample_rate: float):
+        self.ctx._check(self.ctx.L.fg_index_scatter_end(self.ctx.h, float(sample_rate)))
 
     def getSampleRate(self) -> float:
         return self.stats["sample_rate"] if self.stats else self._sample_rate_init

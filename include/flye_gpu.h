@@ -296,6 +296,36 @@ void fg_release_batch(struct fg_overlap_batch* b);
 int fg_index_keep_targets(fg_ctx* ctx, uint32_t world, uint32_t rank, uint64_t* n_entries_kept);
 int fg_index_shard(const fg_ctx* ctx, uint32_t* world, uint32_t* rank);
 
+/* The same shard built DIRECTLY from the key-range pieces of a sharded build, without any rank ever holding the full
+ * entry array.  Rank order is key order; an entry's owner is ((entry >> 33) % world), as in fg_index_keep_targets.
+ *
+ * fg_index_piece_split, after fg_index_finish on a context that holds a piece (or a whole index): *d_counts receives
+ * the device pointer of the world x n_keys matrix (uint64, row d contiguous) of "entries of key j owned by rank d",
+ * *d_entries that of the piece's n_entries entries rewritten destination major, key major inside a destination, list
+ * order inside a key (a stable world-way partition of every list); dest_totals[world] (host) = entries per
+ * destination.  The piece itself is untouched.  The two buffers belong to the context and live until
+ * fg_index_scatter_end, a new build, an import or fg_clear_index.  world == 0 or world > 128 is FG_ERR_ARG; no
+ * finished piece, a gather or scatter in progress, or an already restricted context is FG_ERR_STATE.
+ *
+ * fg_index_scatter_begin (after a split for the same world) sets the piece and its split buffers aside -- the
+ * pointers fg_index_device_arrays gave for the piece stay valid until scatter_end -- and allocates the shard's arrays:
+ * full[4] = device pointers of keys[n_keys], key_off[n_keys + 1], entries[n_shard_entries],
+ * repetitive[n_repetitive].  The caller's collectives fill them: keys and repetitive keys of all pieces in rank
+ * order; into key_off[0 .. n_keys) the COUNT rows received from the sources in rank order (source s sends its row
+ * `rank`); into entries the sources' segments for `rank`, in rank order.  rank >= world or world == 0 is FG_ERR_ARG.
+ *
+ * fg_index_scatter_end frees the piece and the split buffers, turns the counts into list offsets (exclusive scan in
+ * place) and checks on the device, before any list is read through them: offsets end at n_shard_entries, keys
+ * strictly ascending, every entry owned by `rank`, every list strictly ascending.  A violation is FG_ERR_ARG and
+ * leaves the context without an index.  Then the lookup structures are built and the context is a shard exactly as
+ * after fg_index_keep_targets(world, rank): fg_index_shard, the refusals of fg_overlaps / fgb_create, fg_probe_hits
+ * and fg_overlaps_from_hits.  sample_rate = getSampleRate() of the WHOLE index. */
+int fg_index_piece_split(fg_ctx* ctx, uint32_t world, const uint64_t** d_counts, const uint64_t** d_entries,
+                         uint64_t* dest_totals);
+int fg_index_scatter_begin(fg_ctx* ctx, uint32_t world, uint32_t rank, uint64_t n_keys, uint64_t n_shard_entries,
+                           uint64_t n_repetitive, uint64_t** full);
+int fg_index_scatter_end(fg_ctx* ctx, float sample_rate);
+
 /* One seed hit as getSeqOverlaps collects it (overlap.cpp:176-196): KmerMatch{curPos, extPos, extId}, the target
  * side in the query k-mer's orientation (vertex_index.h:158-174). */
 struct fg_seed_hit { int32_t cur_pos; int32_t ext_pos; uint32_t ext_id; };
