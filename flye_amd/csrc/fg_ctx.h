@@ -196,8 +196,8 @@ struct ScopedK {
 	~ScopedK() { try { t.end(id, on); } catch (...) {} }
 };
 
-// Worker threads of the host shim, kept between calls: spawning 2 x 16 std::threads per fg_overlaps call and
-// faulting in fresh result-sized vectors cost more than the shim's own arithmetic.
+// Worker threads of the host shim, kept between calls: spawning 16 std::threads per fg_overlaps call cost more
+// than the shim's own arithmetic.
 // CPUs this process may actually use: the cgroup's quota where there is one (a container that shows 256 threads but
 // is granted 16 CPUs of time runs host loops slower on 32 threads than on 16)
 inline unsigned fg_usable_cpus()
@@ -279,11 +279,13 @@ struct fg_ctx {
 	// stream (fork / join by events), so that neither class waits for the other's last waves
 	hipStream_t stream2 = nullptr, stream3 = nullptr;
 	hipEvent_t evFork = nullptr, evJoin = nullptr, evJoin3 = nullptr;
-	// the primaries of a chunk leave for the host in FG_D2H_PIECES copies; the shim's threads start on a piece as
-	// soon as ITS copy has landed (piece i covers the primaries below pieceEnd[i], counted over the whole call)
-#define FG_D2H_PIECES 4
-	hipEvent_t evOff = nullptr, evPiece[FG_D2H_PIECES] = {};
-	unsigned long long pieceEnd[FG_D2H_PIECES] = {};
+	// the primaries of a chunk leave for the host in nPieces copies with an event behind each; the shim's tasks start
+	// on a piece as soon as ITS copy has landed (piece i covers the primaries below pieceEnd[i], counted over the
+	// whole call)
+#define FG_D2H_MAX_PIECES 16
+	hipEvent_t evOff = nullptr, evPiece[FG_D2H_MAX_PIECES] = {};
+	unsigned long long pieceEnd[FG_D2H_MAX_PIECES] = {};
+	int nPieces = 0;
 	std::string lastError;
 	KernelTimer timer;
 
@@ -391,12 +393,8 @@ struct fg_ctx {
 	PinnedBuf<char> hPrim;
 	PinnedBuf<u64> hOff;
 	PinnedBuf<u64> hScalar;		// staging of the counts the host reads between kernels (pinned: no bounce buffer)
-	// host shim: worker threads and result-sized scratch kept between calls
+	// host shim: worker threads kept between calls (the record pass needs no result-sized scratch, fg_taskchain.h)
 	ShimPool shimPool;
-	std::vector<float> shimDiv;
-	std::vector<uint8_t> shimKeep;
-	std::vector<u32> shimNStat;
-	std::vector<u64> shimNMatch;
 
 	~fg_ctx()
 	{

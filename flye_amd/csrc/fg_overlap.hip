@@ -23,6 +23,7 @@
 #include "fg_ctx.h"
 #include "fg_wavesort.h"
 #include "fg_devprim.h"
+#include "fg_taskchain.h"
 #include <atomic>
 
 #include <algorithm>
@@ -1274,8 +1275,12 @@ static void deviceSub(fg_ctx* c, const fg_detector_params* p, uint8_t forceLocal
 	{ ScopedK t(c->timer, "k_exscan");
 	  hipLaunchKernelGGL(k_exscan, 1, 1024, 0, s, c->dCntA.p + sub0, c->dHitOff.p, nq);
 	  hipLaunchKernelGGL(k_exscan, 1, 1024, 0, s, c->dCntB.p + sub0, c->dFiltOff.p, nq); }
-	const u64 nHits = fetchScalar(c, c->dHitOff.p + nq);
-	const u64 nFilt = fetchScalar(c, c->dFiltOff.p + nq);
+	// both totals with one synchronisation
+	c->hScalar.reserve(8);
+	HIP_CHECK(hipMemcpyAsync(c->hScalar.p, c->dHitOff.p + nq, 8, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(hipMemcpyAsync(c->hScalar.p + 1, c->dFiltOff.p + nq, 8, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(hipStreamSynchronize(s));
+	const u64 nHits = c->hScalar.p[0], nFilt = c->hScalar.p[1];
 	res->nHits = nHits;
 	const u64 hitCap = std::max(nHits, hitCapHint);		// what the per-hit buffers below are reserved for
 	c->hitCapHint = hitCap;
@@ -1393,16 +1398,18 @@ static void deviceSub(fg_ctx* c, const fg_detector_params* p, uint8_t forceLocal
 	  HIP_CHECK(hipEventRecord(c->evOff, s));
 	  // the records in pieces, an event behind each: the caller does not wait for them here (the host shim's
 	  // threads wait for the piece they read)
-	  const int nPieces = nPrim >= 100000 ? FG_D2H_PIECES : 1;	// a small result is one copy (the unused events are recorded all the same)
-	  for (int i = 0; i < FG_D2H_PIECES; ++i)
+	  static const int wantPieces = getenv("FG_D2H_PIECES") ? std::max(1, std::min(FG_D2H_MAX_PIECES, atoi(getenv("FG_D2H_PIECES")))) : 12;
+	  const int nPieces = nPrim >= 100000 ? wantPieces : 1;	// a small result is one copy
+	  for (int i = 0; i < nPieces; ++i)
 	  {
-		  const u64 a = i < nPieces ? nPrim * i / nPieces : nPrim, b = i < nPieces ? nPrim * (i + 1) / nPieces : nPrim;
+		  const u64 a = nPrim * i / nPieces, b = nPrim * (i + 1) / nPieces;
 		  if (b > a)
 			  HIP_CHECK(hipMemcpyAsync(c->hPrim.p + (primBase + a) * sizeof(PrimRec), c->dPrimOut.p + a * sizeof(PrimRec),
 									   (b - a) * sizeof(PrimRec), hipMemcpyDeviceToHost, s));
 		  HIP_CHECK(hipEventRecord(c->evPiece[i], s));
 		  c->pieceEnd[i] = primBase + b;
-	  } }
+	  }
+	  c->nPieces = nPieces; }
 	HIP_CHECK(hipEventSynchronize(c->evOff));
 	if (keepAln) HIP_CHECK(hipStreamSynchronize(s));		// the match lists are read by the caller right away
 	res->nPrim = nPrim;
@@ -1512,12 +1519,15 @@ void fgOverlaps(fg_ctx* c, const fg_detector_params* p, const u32* queryIds, u32
 	std::vector<u32> hq(nq);
 	std::vector<u64> hQKmerOff(nq + 1, 0);
 	u64 queryBp = 0;
+	const int STAT_WND = 10000;
+	u64 statCap = 0;		// window statistics the call can produce at most
 	for (u32 i = 0; i < nq; ++i)
 	{
 		hq[i] = queryIds[i] - (c->hasQ ? c->qFirstId : c->firstId);
 		const i32 L = (c->hasQ ? c->hQLen : c->hLen)[hq[i] >> 1];
 		hQKmerOff[i + 1] = hQKmerOff[i] + (u64)std::max(0, L - k);
 		queryBp += L;
+		statCap += (u64)(L / STAT_WND + 1);
 	}
 	out->query_bp = queryBp;
 	out->query_kmers = hQKmerOff[nq];
@@ -1708,165 +1718,168 @@ void fgOverlaps(fg_ctx* c, const fg_detector_params* p, const u32* queryIds, u32
 	const u64* hPrimOff = primOffAll.data();
 	const auto tHost1 = std::chrono::steady_clock::now();
 	const int dev = c->device;
-	std::atomic<int> waitErr{0};		// worker threads must not throw
 	const bool pieceWait = !laned && subs.size() <= 1;
-	auto waitPrim = [c, dev, &waitErr, pieceWait](u64 endIdx)
+	auto waitPrim = [c, dev, pieceWait](u64 endIdx)
 	{
 		if (!pieceWait) return;
 		// primaries below endIdx are on the host when the first piece reaching that far has landed (copies of one
 		// stream complete in order; earlier chunks' pieces lie below this chunk's first)
 		(void)hipSetDevice(dev);
-		for (int i = 0; i < FG_D2H_PIECES; ++i)
-			if (c->pieceEnd[i] >= endIdx || i == FG_D2H_PIECES - 1)
+		for (int i = 0; i < c->nPieces; ++i)
+			if (c->pieceEnd[i] >= endIdx || i == c->nPieces - 1)
 			{
 				const hipError_t e = hipEventSynchronize(c->evPiece[i]);
-				if (e != hipSuccess) waitErr.store((int)e);
+				if (e != hipSuccess) throw FgError{FG_ERR_HIP, std::string("waiting for the result copy: ") + hipGetErrorString(e)};
 				return;
 			}
 	};
 
 	// ---- host shim: floats with the host libm, the gate, prefix rule, window stats ----
-	// two passes over the queries, both fanned out over host threads: (1) divergence,
-	// gate and per-query counts, (2) after a prefix sum, the records themselves
+	// One ordered pass over small tasks of queries (fg_taskchain.h), fanned out over host threads.  A task waits for
+	// the copy that covers its primaries, computes divergence, gate and the window statistics of its queries, takes
+	// its place in the result from the running sums of the task before it and writes its records at once, while
+	// the primaries it has just read are still in cache.  No pass over all queries, no join between the two halves.
 	const float sampleRate = c->sampleRate;
 	const float maxDiv = p->max_divergence;
 	const bool nucl = p->nucl_alignment;
 	const bool partition = p->partition_bad_mappings;	// only with maxOverlaps == 0 (fg_api.hip)
-	const int STAT_WND = 10000;
-	// result-sized scratch lives in the context (grow-only, never zero-filled: pass 1 writes every element)
-	if (c->shimDiv.size() < nPrim) { c->shimDiv.resize(nPrim + nPrim / 8); c->shimKeep.resize(c->shimDiv.size()); }
-	if (c->shimNStat.size() < nq) { c->shimNStat.resize(nq + nq / 8); c->shimNMatch.resize(c->shimNStat.size()); }
-	float* div = c->shimDiv.data();
-	uint8_t* keep = c->shimKeep.data();
-	u32* nStat = c->shimNStat.data();
-	u64* nMatch = c->shimNMatch.data();
-	std::vector<std::vector<float>> statVals;
+	const u32 TASK_Q = 128;		// queries per task: a few thousand primaries, read and written within a core's cache
+	const u32 nTasks = (nq + TASK_Q - 1) / TASK_Q;
 	// host threads of the shim: the hardware threads, capped by the cgroup CPU quota (a container that
 	// shows 256 threads but is granted 16 CPUs of time runs the shim slower on 32 threads than on 16)
 	const unsigned usableCpus = fg_usable_cpus();
 	unsigned nThreads = std::max(1u, std::min(usableCpus, 32u));
 	if (getenv("FG_SHIM_THREADS")) nThreads = std::max(1, atoi(getenv("FG_SHIM_THREADS")));
 	if (nPrim < 20000) nThreads = 1;
-	statVals.resize(nThreads);
-	std::vector<std::vector<u32>> statQ(nThreads);
-	auto pass1 = [&](unsigned t)
-	{
-		struct Wnd { i32 range; float div; };
+	nThreads = std::min(nThreads, nTasks);
+	// the arena holds what the call can produce at most (kept <= nPrim); grow-only, never zero-filled
+	own->reserveRecs(nPrim);
+	if (partition) own->needsTrim.assign(nPrim, 0);
+	if (keepAln) { own->reserveMatches(mData.size()); own->matchOff.assign(nPrim + 1, 0); }
+	own->stats.resize(statCap);
+	enum { SUM_RECS, SUM_STATS, SUM_MATCHES };
+	struct Wnd { i32 range; float div; };
+	struct Scratch {
+		std::vector<float> div; std::vector<uint8_t> keep;		// per primary of the task
+		std::vector<u32> nRec, nStat;							// per query of the task
+		std::vector<float> stat;
 		std::vector<Wnd> wnd;
-		const u32 q0 = (u32)((u64)nq * t / nThreads), q1 = (u32)((u64)nq * (t + 1) / nThreads);
-		if (q1 > q0) waitPrim(hPrimOff[q1]);
-		if (waitErr.load()) return;
-		for (u32 qi = q0; qi < q1; ++qi)
+	};
+	std::vector<Scratch> scratch(nThreads);
+	FgTaskChain<3> chain(nTasks);
+	auto worker = [&](unsigned th)
+	{
+		Scratch& S = scratch[th];
+		auto count = [&](u32 task, uint64_t* mine)
 		{
-			const i32 curLen = (c->hasQ ? c->hQLen : c->hLen)[hq[qi] >> 1];
-			wnd.assign(curLen / STAT_WND + 1, Wnd{0, 0.0f});
-			size_t detected = 0;
-			u32 prevExt = 0xFFFFFFFFu;
-			if (keepAln) nMatch[qi] = 0;
-			const PrimRec* hPrim = primPtr[qi];
-			for (u64 j = hPrimOff[qi]; j < hPrimOff[qi + 1]; ++j)
+			const u32 q0 = task * TASK_Q, q1 = std::min(nq, q0 + TASK_Q);
+			waitPrim(hPrimOff[q1]);
+			const u64 j0 = hPrimOff[q0];
+			S.div.resize(hPrimOff[q1] - j0); S.keep.resize(hPrimOff[q1] - j0);		// every element is written below
+			S.nRec.resize(q1 - q0); S.nStat.resize(q1 - q0);
+			S.stat.clear();
+			float* div = S.div.data() - j0;
+			uint8_t* keep = S.keep.data() - j0;
+			for (u32 qi = q0; qi < q1; ++qi)
 			{
-				const PrimRec& r = hPrim[j];
-				// groups are visited in ascending extId; the limit is tested only at a group
-				// start, against the overlaps accepted so far (overlap.cpp:218-219) -- a group
-				// with several primaries (onlyMaxExt = false) is never cut in the middle
-				if (r.extId != prevExt)
+				const i32 curLen = (c->hasQ ? c->hQLen : c->hLen)[hq[qi] >> 1];
+				S.wnd.assign(curLen / STAT_WND + 1, Wnd{0, 0.0f});
+				size_t detected = 0;
+				u32 prevExt = 0xFFFFFFFFu;
+				const PrimRec* hPrim = primPtr[qi];
+				for (u64 j = hPrimOff[qi]; j < hPrimOff[qi + 1]; ++j)
 				{
-					if (maxOverlaps != 0 && detected >= (size_t)maxOverlaps)
+					const PrimRec& r = hPrim[j];
+					// groups are visited in ascending extId; the limit is tested only at a group
+					// start, against the overlaps accepted so far (overlap.cpp:218-219) -- a group
+					// with several primaries (onlyMaxExt = false) is never cut in the middle
+					if (r.extId != prevExt)
 					{
-						for (u64 jj = j; jj < hPrimOff[qi + 1]; ++jj) keep[jj] = 0;	// the scratch is not zero-filled
-						break;
+						if (maxOverlaps != 0 && detected >= (size_t)maxOverlaps)
+						{
+							for (u64 jj = j; jj < hPrimOff[qi + 1]; ++jj) keep[jj] = 0;	// the scratch is not zero-filled
+							break;
+						}
+						prevExt = r.extId;
 					}
-					prevExt = r.extId;
+					// overlap.cpp:414-423
+					float normLen = std::max(r.curEnd - r.curBegin, r.extEnd - r.extBegin) - r.filtered;
+					float matchRate = (float)r.chainLength * sampleRate / normLen;
+					matchRate = std::min(matchRate, 1.0f);
+					float d = std::log(1 / matchRate) / k;
+					if (nucl)	// alignment.cpp:244-245
+						d = (float)r.editDistance / std::max((size_t)r.hpcLenExt, (size_t)r.hpcLenCur);
+					div[j] = d;
+					if (d < maxDiv) { keep[j] = 1; ++detected; }
+					else if (partition) { keep[j] = 2; ++detected; }	// handed back for the caller's checkIdyAndTrim
+					else keep[j] = 0;
+					if (keep[j] && keepAln) mine[SUM_MATCHES] += mOff[j + 1] - mOff[j];
+					const size_t w = r.curBegin / STAT_WND;
+					if (r.curEnd - r.curBegin > S.wnd[w].range) { S.wnd[w].range = r.curEnd - r.curBegin; S.wnd[w].div = d; }
 				}
-				// overlap.cpp:414-423
-				float normLen = std::max(r.curEnd - r.curBegin, r.extEnd - r.extBegin) - r.filtered;
-				float matchRate = (float)r.chainLength * sampleRate / normLen;
-				matchRate = std::min(matchRate, 1.0f);
-				float d = std::log(1 / matchRate) / k;
-				if (nucl)	// alignment.cpp:244-245
-					d = (float)r.editDistance / std::max((size_t)r.hpcLenExt, (size_t)r.hpcLenCur);
-				div[j] = d;
-				if (d < maxDiv) { keep[j] = 1; ++detected; }
-				else if (partition) { keep[j] = 2; ++detected; }	// handed back for the caller's checkIdyAndTrim
-				else keep[j] = 0;
-				if (keep[j] && keepAln) nMatch[qi] += mOff[j + 1] - mOff[j];
-				const size_t w = r.curBegin / STAT_WND;
-				if (r.curEnd - r.curBegin > wnd[w].range) { wnd[w].range = r.curEnd - r.curBegin; wnd[w].div = d; }
+				u32 ns = 0;
+				for (auto& w : S.wnd) if (w.range > 0) { S.stat.push_back(w.div); ++ns; }
+				S.nRec[qi - q0] = (u32)detected; S.nStat[qi - q0] = ns;
+				mine[SUM_RECS] += detected; mine[SUM_STATS] += ns;
 			}
-			own->queryOff[qi + 1] = detected;
-			u32 ns = 0;
-			for (auto& w : wnd) if (w.range > 0) { statVals[t].push_back(w.div); ++ns; }
-			nStat[qi] = ns;
-		}
-	};
-	auto runThreads = [&](const std::function<void(unsigned)>& fn) { c->shimPool.run(nThreads, fn); };
-	if (!pieceWait) HIP_CHECK(hipStreamSynchronize(s));		// several sub-ranges: their copies are simply waited for
-	runThreads(pass1);
-	HIP_CHECK(hipStreamSynchronize(s));		// everything has landed by now; also surfaces a failed copy
-	if (waitErr.load()) throw FgError{FG_ERR_HIP, std::string("waiting for the result copy: ") + hipGetErrorString((hipError_t)waitErr.load())};
-	own->queryOff[0] = 0;
-	for (u32 qi = 0; qi < nq; ++qi)
-	{
-		own->queryOff[qi + 1] += own->queryOff[qi];
-		own->statOff[qi + 1] = own->statOff[qi] + nStat[qi];
-	}
-	own->reserveRecs(own->queryOff[nq]);
-	own->nRecs = own->queryOff[nq];
-	if (partition) own->needsTrim.assign(own->nRecs, 0);
-	std::vector<u64> qMatchOff;		// first pair of each query's records
-	if (keepAln)
-	{
-		qMatchOff.assign(nq + 1, 0);
-		for (u32 qi = 0; qi < nq; ++qi) qMatchOff[qi + 1] = qMatchOff[qi] + nMatch[qi];
-		own->reserveMatches(qMatchOff[nq]);
-		own->matchOff.assign(own->nRecs + 1, 0);
-		own->matchOff[own->nRecs] = qMatchOff[nq];
-	}
-	own->stats.clear();
-	own->stats.reserve(own->statOff[nq]);
-	for (unsigned t = 0; t < nThreads; ++t) own->stats.insert(own->stats.end(), statVals[t].begin(), statVals[t].end());
-	auto pass2 = [&](unsigned t)
-	{
-		const u32 q0 = (u32)((u64)nq * t / nThreads), q1 = (u32)((u64)nq * (t + 1) / nThreads);
-		for (u32 qi = q0; qi < q1; ++qi)
+		};
+		auto write = [&](u32 task, const uint64_t* base)
 		{
-			const i32 curLen = (c->hasQ ? c->hQLen : c->hLen)[hq[qi] >> 1];
-			fg_overlap_rec* dst = own->recs + own->queryOff[qi];
-			u64 mo = keepAln ? qMatchOff[qi] : 0;
-			const PrimRec* hPrim = primPtr[qi];
-			for (u64 j = hPrimOff[qi]; j < hPrimOff[qi + 1]; ++j)
+			const u32 q0 = task * TASK_Q, q1 = std::min(nq, q0 + TASK_Q);
+			const u64 j0 = hPrimOff[q0];
+			const float* div = S.div.data() - j0;
+			const uint8_t* keep = S.keep.data() - j0;
+			if (!S.stat.empty()) memcpy(own->stats.data() + base[SUM_STATS], S.stat.data(), S.stat.size() * sizeof(float));
+			u64 recAt = base[SUM_RECS], statAt = base[SUM_STATS], mo = base[SUM_MATCHES];
+			for (u32 qi = q0; qi < q1; ++qi)
 			{
-				if (!keep[j]) continue;
-				const PrimRec& r = hPrim[j];
-				if (partition) own->needsTrim[dst - own->recs] = keep[j] == 2;
-				if (keepAln)
+				const i32 curLen = (c->hasQ ? c->hQLen : c->hLen)[hq[qi] >> 1];
+				fg_overlap_rec* dst = own->recs + recAt;
+				recAt += S.nRec[qi - q0]; statAt += S.nStat[qi - q0];
+				own->queryOff[qi + 1] = recAt;
+				own->statOff[qi + 1] = statAt;
+				const PrimRec* hPrim = primPtr[qi];
+				for (u64 j = hPrimOff[qi]; j < hPrimOff[qi + 1]; ++j)
 				{
-					const u64 cnt = mOff[j + 1] - mOff[j];
-					own->matchOff[dst - own->recs] = mo;
-					memcpy(own->matches + 2 * mo, mData.data() + mOff[j], cnt * 8);	// (cur, ext) int32 pairs
-					mo += cnt;
-				}
-				fg_overlap_rec o;
-				o.cur_id = queryIds[qi]; o.ext_id = r.extId;
-				o.cur_begin = r.curBegin; o.cur_end = r.curEnd; o.cur_len = curLen;
-				o.ext_begin = r.extBegin; o.ext_end = r.extEnd; o.ext_len = r.extLen;
-				o.score = r.score; o.seq_divergence = div[j];
-				o.chain_length = r.chainLength; o.filtered_positions = r.filtered;
-				o.edit_distance = r.editDistance; o.hpc_len_cur = r.hpcLenCur; o.hpc_len_ext = r.hpcLenExt;
-				// the records are written once and not read again by this thread: streaming stores keep the
-				// read-for-ownership of every destination line off the memory bus
-				static_assert(sizeof(fg_overlap_rec) % 4 == 0, "record of 32-bit fields");
-				const int* src32 = (const int*)&o;
-				int* dst32 = (int*)dst;
+					if (!keep[j]) continue;
+					const PrimRec& r = hPrim[j];
+					if (partition) own->needsTrim[dst - own->recs] = keep[j] == 2;
+					if (keepAln)
+					{
+						const u64 cnt = mOff[j + 1] - mOff[j];
+						own->matchOff[dst - own->recs] = mo;
+						memcpy(own->matches + 2 * mo, mData.data() + mOff[j], cnt * 8);	// (cur, ext) int32 pairs
+						mo += cnt;
+					}
+					fg_overlap_rec o;
+					o.cur_id = queryIds[qi]; o.ext_id = r.extId;
+					o.cur_begin = r.curBegin; o.cur_end = r.curEnd; o.cur_len = curLen;
+					o.ext_begin = r.extBegin; o.ext_end = r.extEnd; o.ext_len = r.extLen;
+					o.score = r.score; o.seq_divergence = div[j];
+					o.chain_length = r.chainLength; o.filtered_positions = r.filtered;
+					o.edit_distance = r.editDistance; o.hpc_len_cur = r.hpcLenCur; o.hpc_len_ext = r.hpcLenExt;
+					// the records are written once and not read again by this thread: streaming stores keep the
+					// read-for-ownership of every destination line off the memory bus
+					static_assert(sizeof(fg_overlap_rec) % 4 == 0, "record of 32-bit fields");
+					const int* src32 = (const int*)&o;
+					int* dst32 = (int*)dst;
 #pragma unroll
-				for (unsigned w4 = 0; w4 < sizeof(fg_overlap_rec) / 4; ++w4) __builtin_nontemporal_store(src32[w4], dst32 + w4);
-				++dst;
+					for (unsigned w4 = 0; w4 < sizeof(fg_overlap_rec) / 4; ++w4) __builtin_nontemporal_store(src32[w4], dst32 + w4);
+					++dst;
+				}
 			}
-		}
-		__builtin_ia32_sfence();
+			__builtin_ia32_sfence();
+		};
+		chain.work(count, write);
 	};
-	runThreads(pass2);
+	if (!pieceWait) HIP_CHECK(hipStreamSynchronize(s));		// several sub-ranges: their copies are simply waited for
+	c->shimPool.run(nThreads, worker);
+	chain.rethrow();
+	HIP_CHECK(hipStreamSynchronize(s));		// everything has landed by now; also surfaces a failed copy
+	own->nRecs = chain.total(SUM_RECS);
+	own->stats.resize(chain.total(SUM_STATS));
+	if (partition) own->needsTrim.resize(own->nRecs);
+	if (keepAln) { own->matchOff.resize(own->nRecs + 1); own->matchOff[own->nRecs] = chain.total(SUM_MATCHES); }
 	out->n_recs = own->nRecs;
 	out->query_off = own->queryOff.data();
 	out->recs = own->recs;
