@@ -155,6 +155,7 @@ int fg_set_reads(fg_ctx* c, uint32_t n, const uint64_t* words, const uint64_t* w
 		HIP_CHECK(hipSetDevice(c->device));
 		if ((u64)first_seq_id + 2ULL * n > 0xFFFFFFFFULL) throw FgError{FG_ERR_ARG, "sequence ids overflow uint32"};
 		c->indexBuilt = false;
+		c->dMaybeBits.release();	// they number the positions of the reads that leave
 		c->hasQ = false; c->nQReads = 0; c->hQLen.clear();
 		c->nReads = n;
 		c->firstId = first_seq_id;
@@ -397,7 +398,7 @@ int fg_clear_index(fg_ctx* c)
 		c->shardWorld = 1; c->shardRank = 0;
 		c->gKeys.release(); c->gKeyOff.release(); c->gEntries.release(); c->gRepKeys.release();
 		c->dKeys.release(); c->dKeyOff.release(); c->dEntries.release(); c->dRepKeys.release();
-		c->dTable.release(); c->dIndexedBits.release();
+		c->dTable.release(); c->dIndexedBits.release(); c->dMaybeBits.release();
 		c->nKeys = c->nEntries = c->nRep = c->tableSlots = 0;
 	});
 }
@@ -556,6 +557,19 @@ int fg_debug_sort_pairs(fg_ctx* c, uint64_t* keys, uint32_t* vals, const uint64_
 	{
 		HIP_CHECK(hipSetDevice(c->device));
 		fgDebugSortPairs(c, keys, vals, seg_off, n_seg);
+	});
+}
+
+int fg_debug_probe_skip_check(fg_ctx* c, uint64_t* clear_bits, uint64_t* violations)
+{
+	if (!c || !clear_bits || !violations) return FG_ERR_ARG;
+	return guarded(c, [&]()
+	{
+		HIP_CHECK(hipSetDevice(c->device));
+		if (!c->indexBuilt) throw FgError{FG_ERR_STATE, "no index"};
+		u64 cb = 0, vi = 0;
+		fgDebugProbeSkipCheck(c, &cb, &vi);
+		*clear_bits = cb; *violations = vi;
 	});
 }
 

@@ -323,6 +323,12 @@ struct fg_ctx {
 	bool tableWide = false;
 	FgTable table{};
 	DevBuf<u32> dIndexedBits;	// one bit per forward k-mer position: contributes an entry
+	// one bit per forward k-mer position, same numbering: the k-mer's frequency over the whole read set reached the
+	// build's minFreq.  A CLEAR bit proves the lookup table has no slot for the k-mer (a key enters only through an
+	// accepted position, k_accept), so k_probe skips the probe.  Only a solid-k-mer build of this context leaves
+	// them (they outlive the gather of a sharded build and keep_targets: the table only ever holds keys of accepted
+	// positions); empty after a minimizer build, an import and the direct option-B scatter: every k-mer is probed
+	DevBuf<u32> dMaybeBits;
 	// option B (fg_index_keep_targets): the lists hold only the entries of target reads i with i % shardWorld ==
 	// shardRank; the indexed bits of the other reads are cleared.  1 / 0 = the whole index
 	u32 shardWorld = 1, shardRank = 0;
@@ -354,6 +360,7 @@ struct fg_ctx {
 	// probes partitioned by table region (tables beyond the caches): (region | k-mer, position) pairs, twice, + sort scratch
 	DevBuf<u64> dPartK0, dPartV0, dPartK1, dPartV1;
 	DevBuf<char> dPartScratch;
+	DevBuf<unsigned long long> dPartCount;	// pairs k_probe_emit appended
 	DevBuf<u64> dHitOff;		// per query hit offsets (nq+1)
 	DevBuf<u64> dFiltOff;		// per query repetitive-position offsets (nq+1)
 	DevBuf<i32> dFiltPos;
@@ -654,6 +661,7 @@ void fgEditDistances(fg_ctx* c, PrimRec* dPrims, u64 nPrim, int useHpc);
 void fgKswAlign(fg_ctx* c, u32 nPairs, const uint8_t* trg, const u64* trgOff, const uint8_t* qry, const u64* qryOff,
 				std::vector<u64>& runOff, std::vector<u32>& runs);
 void fgDebugSortPairs(fg_ctx* c, u64* keys, u32* vals, const u64* segOff, u32 nSeg);
+void fgDebugProbeSkipCheck(fg_ctx* c, u64* clearBits, u64* violations);
 void fgDebugEditDistances(fg_ctx* c, u32 nPairs, int useHpc, i32* outDist, i32* outLenA, i32* outLenB);
 // option B: seed hits gathered from index shards, as the overlap stage takes them in place of its own seed
 // expansion.  Per query qi of the call and source s: the run of hits[runStart[qi * nSrc + s] ..] of runLen[..]

@@ -268,6 +268,9 @@ __global__ void k_tandem_apply(u32 r0, const u64* __restrict__ words, const u64*
 }
 
 // bit0 := accepted for the index (selected, not tandem, freq >= minFreq)
+// bit1 := freq >= minFreq, whatever the selection said: every occurrence of a canonical k-mer has the same frequency and
+// a key enters the index only through an accepted position, so a clear bit 1 means "no slot in the lookup table" for
+// this position's k-mer, in this build's index, any key range or target shard of it included (k_probe skips the probe)
 __global__ void k_accept(u32 r0, const i32* __restrict__ len, const u64* __restrict__ kmerOff, int k,
 						 const u32* __restrict__ freq, i32 minFreq, uint8_t* __restrict__ flags,
 						 unsigned long long* __restrict__ nAcc)
@@ -282,8 +285,9 @@ __global__ void k_accept(u32 r0, const i32* __restrict__ len, const u64* __restr
 	u32 c = 0;
 	for (i32 p = threadIdx.x; p < nk; p += WG)
 	{
-		uint8_t b = (fl[p] & 1) && f[p] >= (u32)minFreq;
-		fl[p] = b;
+		const bool enough = f[p] >= (u32)minFreq;
+		const uint8_t b = (fl[p] & 1) && enough;
+		fl[p] = b | (enough ? 2 : 0);
 		c += b;
 	}
 	u32 tot = block_sum(c, sh);
@@ -291,8 +295,9 @@ __global__ void k_accept(u32 r0, const i32* __restrict__ len, const u64* __restr
 }
 
 // the batch's byte flags -> the read set's bit array: thread per 32-bit word touched by positions
-// [posBase, posBase + nPos) (a word at a batch boundary is shared with the neighbouring batch: atomicOr)
-__global__ void k_pack_bits(const uint8_t* __restrict__ flags, u64 posBase, u64 nPos, u32* __restrict__ bits)
+// [posBase, posBase + nPos) (a word at a batch boundary is shared with the neighbouring batch: atomicOr); `mask` picks
+// the flag bit
+__global__ void k_pack_bits(const uint8_t* __restrict__ flags, uint8_t mask, u64 posBase, u64 nPos, u32* __restrict__ bits)
 {
 	const u64 w = (posBase >> 5) + (u64)blockIdx.x * WG + threadIdx.x;
 	if (w > ((posBase + nPos - 1) >> 5)) return;
@@ -301,7 +306,7 @@ __global__ void k_pack_bits(const uint8_t* __restrict__ flags, u64 posBase, u64 
 	for (int j = 0; j < 32; ++j)
 	{
 		const u64 pos = w * 32 + j;
-		if (pos >= posBase && pos < posBase + nPos && flags[pos - posBase]) v |= 1u << j;
+		if (pos >= posBase && pos < posBase + nPos && (flags[pos - posBase] & mask)) v |= 1u << j;
 	}
 	if (v) atomicOr(&bits[w], v);
 }
@@ -770,6 +775,7 @@ struct IndexBuild {
 	float selectRate = 0;
 	// selection: one bit per k-mer position of the read set; scratch of the batch in work
 	DevBuf<u32> bits;
+	DevBuf<u32> maybe;				// solid mode: frequency >= minFreq per position (fg_ctx::dMaybeBits)
 	std::vector<u32> batchStart;	// first read of each batch; back() = number of reads
 	u64 batchCap = 0;				// k-mer positions of the largest batch
 	u32 batchReads = 0;				// reads of the largest batch
@@ -822,7 +828,7 @@ void clearIndex(fg_ctx* c)
 	c->sCounts.release(); c->sEntries.release();
 	c->gKeys.release(); c->gKeyOff.release(); c->gEntries.release(); c->gRepKeys.release();
 	c->dKeys.release(); c->dKeyOff.release(); c->dEntries.release(); c->dRepKeys.release();
-	c->dTable.release(); c->dIndexedBits.release();
+	c->dTable.release(); c->dIndexedBits.release(); c->dMaybeBits.release();
 	c->nKeys = c->nEntries = c->nRep = c->tableSlots = 0;
 }
 
@@ -887,7 +893,9 @@ void packBatch(fg_ctx* c, IndexBuild* B, u32 r0, u32 r1)
 	if (!nPos) return;
 	const u64 words = ((posBase + nPos - 1) >> 5) - (posBase >> 5) + 1;
 	ScopedK t(c->timer, "k_pack_bits");
-	hipLaunchKernelGGL(k_pack_bits, gridFor(words), WG, 0, c->stream, B->flags.p, posBase, nPos, B->bits.p);
+	hipLaunchKernelGGL(k_pack_bits, gridFor(words), WG, 0, c->stream, B->flags.p, (uint8_t)1, posBase, nPos, B->bits.p);
+	if (B->maybe.p)
+		hipLaunchKernelGGL(k_pack_bits, gridFor(words), WG, 0, c->stream, B->flags.p, (uint8_t)2, posBase, nPos, B->maybe.p);
 }
 
 // one slice of keys -> one part
@@ -1033,6 +1041,8 @@ void fgIndexCountSlice(fg_ctx* c, i32 minFreq, float selectRate, i32 tandemFreq,
 	}
 	B->totalDistinct = fetch(c, (const unsigned long long*)B->scal.p);
 	B->freq.alloc(B->batchCap); B->flags.alloc(B->batchCap); B->thr.alloc(std::max<u32>(1, B->batchReads));
+	B->maybe.alloc(B->bits.n);
+	HIP_CHECK(hipMemsetAsync(B->maybe.p, 0, B->maybe.bytes(), s));
 	if (distinctOut) *distinctOut = B->totalDistinct;
 	if (nBatchesOut) *nBatchesOut = (u32)(B->batchStart.size() - 1);
 	B->seconds = clock.stop();
@@ -1271,6 +1281,8 @@ void fgIndexFinish(fg_ctx* c, const unsigned long long* totalSums, fg_index_stat
 	c->nKeys = nKeep; c->nEntries = nEnt; c->nRep = nRep;
 	// the selection bits become the "owns an entry" bits, in place
 	c->dIndexedBits.swap(B->bits);
+	// solid mode: "frequent enough for a slot" per position (empty after a minimizer selection: clearIndex above freed it)
+	c->dMaybeBits.swap(B->maybe);
 	fgIndexLookupStructures(c, true);
 	st->selected_kmers = nKeep;
 	st->index_entries = nEnt;
@@ -1741,6 +1753,8 @@ void fgIndexPieceSplit(fg_ctx* c, u32 world, const u64** dCounts, const u64** dE
 	hipStream_t s = c->stream;
 	c->timer.reset();
 	c->splitWorld = 0;
+	// the direct build's peak has no term for a second bit array: the shard probes every k-mer
+	c->dMaybeBits.release();
 	const u64 nKeys = c->nKeys, nEnt = c->nEntries, nCnt = (u64)world * nKeys + 1;
 	if ((nKeys + 63) / 64 > 0x7fffffffULL) throw FgError{FG_ERR_UNSUPPORTED, "piece_split: too many keys"};
 	try

@@ -95,14 +95,16 @@ __global__ void k_exscan(const u64* __restrict__ in, u64* __restrict__ out, u32 
 // self-hit flags) so that the fill pass needs no second probe.
 // words/wordOff/len: the QUERY container; kmerOff/indexedBits: the indexed container's k-mer
 // numbering (indexedBits == nullptr when the queries live in their own container: no
-// query can then hit itself)
+// query can then hit itself).  maybeBits (same numbering; nullptr = none): a clear bit says the
+// index build counted the k-mer below minFreq, so the table has no slot for it (k_accept,
+// fg_index.hip) -- the position is a miss without the probe's random 64-byte line
 template <bool WIDE>
 __global__ void k_probe(const u32* __restrict__ query, const u64* __restrict__ words,
 						const u64* __restrict__ wordOff, const i32* __restrict__ len,
 						const u64* __restrict__ kmerOff, const u64* __restrict__ qKmerOff, int k,
 						FgTable table,
-						const u32* __restrict__ indexedBits, u64* __restrict__ probe,
-						u64* __restrict__ hitCnt, u64* __restrict__ filtCnt)
+						const u32* __restrict__ indexedBits, const u32* __restrict__ maybeBits,
+						u64* __restrict__ probe, u64* __restrict__ hitCnt, u64* __restrict__ filtCnt)
 {
 	__shared__ u32 shA[WG / 64], shB[WG / 64];
 	const u32 q = blockIdx.x;
@@ -113,20 +115,22 @@ __global__ void k_probe(const u32* __restrict__ query, const u64* __restrict__ w
 	const i32 nk = L - k;
 	const u64* w = words + wordOff[r];
 	u64* pr = probe + qKmerOff[q];
-	const u64 kbase = indexedBits ? kmerOff[r] : 0;
+	const u64 kbase = (indexedBits || maybeBits) ? kmerOff[r] : 0;
 	u32 hits = 0, filt = 0;
 	for (i32 p = threadIdx.x; p < nk; p += WG)
 	{
 		const i32 qf = rc ? nk - p : p;	// forward-strand position of the same k-mer (L-k-p)
+		// the "this position owns an entry" and "frequent enough for a slot" bits are fetched together and
+		// ahead of the probe (their addresses only depend on the position)
+		// forward position nk (= L-k) is never a forward k-mer position (kmer.h:193-198): it has no bits
+		const u64 bit = kbase + (u64)qf;
+		const u32 selfWord = (indexedBits && qf < nk) ? indexedBits[bit >> 5] : 0u;
+		const u32 maybeWord = (maybeBits && qf < nk) ? maybeBits[bit >> 5] : ~0u;
+		if (!((maybeWord >> (bit & 31)) & 1u)) { pr[p] = 0; continue; }
 		u64 a, b;
 		fg_kmer_pair(w, qf, k, a, b);
 		const u64 fw = rc ? b : a, rv = rc ? a : b;
 		const bool flip = rv < fw;
-		// the "this position owns an entry" bit is fetched alongside the probe (its address only
-		// depends on the position), not behind it
-		// forward position nk (= L-k) is never a forward k-mer position (kmer.h:193-198)
-		const u64 bit = kbase + (u64)qf;
-		const u32 selfWord = (indexedBits && qf < nk) ? indexedBits[bit >> 5] : 0u;
 		u64 v = fg_probe<WIDE>(table, flip ? rv : fw);
 		if (v != 0)
 		{
@@ -158,7 +162,8 @@ __global__ void k_probe(const u32* __restrict__ query, const u64* __restrict__ w
 // A table of tens of GB (D. melanogaster: 18 GB, 10 Gbp of reads: 46 GB) serves random 64-byte probes at a tenth of
 // the rate of one that sits in the Infinity Cache (4 against 40 G probes/s: every probe is a TLB miss and a DRAM
 // page of its own).  So the probes of a batch of queries are first ordered by the table region they fall into:
-//   k_probe_emit    per query k-mer: (region << 34 | canonical k-mer, position | flags)
+//   k_probe_emit    per query k-mer that can have a slot (maybeBits, see k_probe): (region << 34 | canonical k-mer,
+//                   position | flags), appended in any order (the sorted probes scatter by position)
 //   one pass of the onesweep radix sort (fg_devprim.h) on the region bits -- a stable partition into 256 regions
 //   k_probe_sorted  probes region by region (a region = 1/256 of the table: inside the Infinity Cache and the TLB
 //                   reach while it is worked on); a hit scatters its value to the position's slot of `probe`
@@ -170,7 +175,8 @@ __global__ void k_probe(const u32* __restrict__ query, const u64* __restrict__ w
 __global__ void k_probe_emit(u32 q0, const u32* __restrict__ query, const u64* __restrict__ words,
 							 const u64* __restrict__ wordOff, const i32* __restrict__ len,
 							 const u64* __restrict__ kmerOff, const u64* __restrict__ qKmerOff, int k, FgTable table,
-							 int regionShift, const u32* __restrict__ indexedBits, u64* __restrict__ keys, u64* __restrict__ vals)
+							 int regionShift, const u32* __restrict__ indexedBits, const u32* __restrict__ maybeBits,
+							 u64 cap, u64* __restrict__ keys, u64* __restrict__ vals, unsigned long long* __restrict__ nOut)
 {
 	const u32 q = q0 + blockIdx.x;
 	const u32 rec = query[q];
@@ -178,25 +184,43 @@ __global__ void k_probe_emit(u32 q0, const u32* __restrict__ query, const u64* _
 	const bool rc = rec & 1;
 	const i32 nk = len[r] - k;
 	const u64* w = words + wordOff[r];
-	const u64 out0 = qKmerOff[q] - qKmerOff[q0];
-	const u64 kbase = indexedBits ? kmerOff[r] : 0;
-	for (i32 p = threadIdx.x; p < nk; p += WG)
+	const u64 kbase = (indexedBits || maybeBits) ? kmerOff[r] : 0;
+	const u32 lane = threadIdx.x & 63;
+	// whole waves walk the read (the loop bound is wave-uniform): each wave takes one run of output slots per step
+	for (i32 p0 = (i32)(threadIdx.x - lane); p0 < nk; p0 += WG)
 	{
-		const i32 qf = rc ? nk - p : p;
-		u64 a, b;
-		fg_kmer_pair(w, qf, k, a, b);
-		const u64 fw = rc ? b : a, rv = rc ? a : b;
-		const bool flip = rv < fw;
-		const u64 key = flip ? rv : fw;
-		const u64 bit = kbase + (u64)qf;
-		const u32 self = (indexedBits && qf < nk) ? ((indexedBits[bit >> 5] >> (bit & 31)) & 1u) : 0u;
-		u32 part = 0;
-		if (table.nParts > 1)
-			while (part + 1 < table.nParts && key >= table.bound[part + 1]) ++part;
-		const u32 g = __umulhi((u32)(fg_mix(key) >> 32), table.groups[part]);
-		const u64 region = (table.slotBase[part] + (u64)g * 8u) >> regionShift;
-		keys[out0 + p] = (region << PART_KEY_BITS) | key;
-		vals[out0 + p] = (qKmerOff[q] + (u64)p) | (self ? FLAG_SELF : 0ULL) | (flip ? FLAG_FLIP : 0ULL);
+		const i32 p = p0 + (i32)lane;
+		bool emit = p < nk;
+		u64 key = 0, val = 0;
+		if (emit)
+		{
+			const i32 qf = rc ? nk - p : p;
+			const u64 bit = kbase + (u64)qf;
+			const u32 self = (indexedBits && qf < nk) ? ((indexedBits[bit >> 5] >> (bit & 31)) & 1u) : 0u;
+			emit = (maybeBits && qf < nk) ? ((maybeBits[bit >> 5] >> (bit & 31)) & 1u) : true;
+			if (emit)
+			{
+				u64 a, b;
+				fg_kmer_pair(w, qf, k, a, b);
+				const u64 fw = rc ? b : a, rv = rc ? a : b;
+				const bool flip = rv < fw;
+				const u64 km = flip ? rv : fw;
+				u32 part = 0;
+				if (table.nParts > 1)
+					while (part + 1 < table.nParts && km >= table.bound[part + 1]) ++part;
+				const u32 g = __umulhi((u32)(fg_mix(km) >> 32), table.groups[part]);
+				const u64 region = (table.slotBase[part] + (u64)g * 8u) >> regionShift;
+				key = (region << PART_KEY_BITS) | km;
+				val = (qKmerOff[q] + (u64)p) | (self ? FLAG_SELF : 0ULL) | (flip ? FLAG_FLIP : 0ULL);
+			}
+		}
+		const u64 m = __ballot(emit);
+		if (!m) continue;
+		unsigned long long base = 0;
+		if (lane == 0) base = atomicAdd(nOut, (unsigned long long)__popcll(m));
+		base = __shfl(base, 0);
+		const u64 o = base + (u64)__popcll(m & ((1ULL << lane) - 1ULL));
+		if (emit && o < cap) { keys[o] = key; vals[o] = val; }
 	}
 }
 
@@ -1087,6 +1111,55 @@ static void sortSegments(fg_ctx* c, const u64* dSegOff, u32 nSeg, KT* dK, u32* d
 	}
 }
 
+// fg_debug_probe_skip_check: block per indexed read; out[0] = positions with a clear "frequent enough" bit, out[1] =
+// those of them whose canonical k-mer has a slot in the lookup table all the same (never)
+template <bool WIDE>
+__global__ void k_probe_skip_check(const u64* __restrict__ words, const u64* __restrict__ wordOff, const i32* __restrict__ len,
+								   const u64* __restrict__ kmerOff, int k, FgTable table, const u32* __restrict__ maybeBits,
+								   unsigned long long* __restrict__ out)
+{
+	const u32 r = blockIdx.x;
+	const i32 nk = len[r] - k;
+	const u64* w = words + wordOff[r];
+	const u64 kbase = kmerOff[r];
+	u32 clear = 0, bad = 0;
+	for (i32 p = threadIdx.x; p < nk; p += WG)
+	{
+		const u64 bit = kbase + (u64)p;
+		if ((maybeBits[bit >> 5] >> (bit & 31)) & 1u) continue;
+		++clear;
+		u64 fw, rv;
+		fg_kmer_pair(w, p, k, fw, rv);
+		if (fg_probe<WIDE>(table, fw < rv ? fw : rv) != 0) ++bad;
+	}
+	for (int o = 32; o > 0; o >>= 1) { clear += __shfl_down(clear, o); bad += __shfl_down(bad, o); }
+	if ((threadIdx.x & 63) == 0)
+	{
+		if (clear) atomicAdd(&out[0], (unsigned long long)clear);
+		if (bad) atomicAdd(&out[1], (unsigned long long)bad);
+	}
+}
+
+void fgDebugProbeSkipCheck(fg_ctx* c, u64* clearBits, u64* violations)
+{
+	*clearBits = *violations = 0;
+	if (!c->dMaybeBits.p || !c->nReads) return;
+	hipStream_t s = c->stream;
+	DevBuf<unsigned long long> out;
+	out.alloc(2);
+	HIP_CHECK(hipMemsetAsync(out.p, 0, 16, s));
+	if (c->tableWide)
+		hipLaunchKernelGGL(k_probe_skip_check<true>, c->nReads, WG, 0, s, c->dWords.p, c->dWordOff.p, c->dLen.p, c->dKmerOff.p, c->k,
+						   c->table, c->dMaybeBits.p, out.p);
+	else
+		hipLaunchKernelGGL(k_probe_skip_check<false>, c->nReads, WG, 0, s, c->dWords.p, c->dWordOff.p, c->dLen.p, c->dKmerOff.p, c->k,
+						   c->table, c->dMaybeBits.p, out.p);
+	unsigned long long h[2] = {0, 0};
+	HIP_CHECK(hipMemcpyAsync(h, out.p, 16, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(hipStreamSynchronize(s));
+	*clearBits = h[0]; *violations = h[1];
+}
+
 void fgDebugSortPairs(fg_ctx* c, u64* keys, u32* vals, const u64* segOff, u32 nSeg)
 {
 	hipStream_t s = c->stream;
@@ -1100,6 +1173,15 @@ void fgDebugSortPairs(fg_ctx* c, u64* keys, u32* vals, const u64* segOff, u32 nS
 	HIP_CHECK(hipMemcpyAsync(keys, dK.p, n * 8, hipMemcpyDeviceToHost, s));
 	HIP_CHECK(hipMemcpyAsync(vals, dV.p, n * 4, hipMemcpyDeviceToHost, s));
 	HIP_CHECK(hipStreamSynchronize(s));
+}
+
+// the build's "frequent enough for a slot" bits where they hold for the queries (fg_ctx.h), or null: every k-mer is
+// probed.  FG_PROBE_SKIP=0 switches the skip off (A/B runs, parity tests)
+static const u32* probeSkipBits(const fg_ctx* c)
+{
+	if (c->hasQ || !c->dMaybeBits.p) return nullptr;
+	const char* e = getenv("FG_PROBE_SKIP");
+	return (e && atoi(e) == 0) ? nullptr : c->dMaybeBits.p;
 }
 
 // seed collection's probe step with the probes partitioned by table region (see k_probe_emit): fills c->dProbe,
@@ -1122,16 +1204,25 @@ static void probePartitioned(fg_ctx* c, u32 nq, const u64* localOff, const u64* 
 		{
 			c->dPartK0.reserve(n); c->dPartV0.reserve(n); c->dPartK1.reserve(n); c->dPartV1.reserve(n);
 			c->dPartScratch.reserve(fgprim::radixSortScratchBytes(n));
+			c->dPartCount.reserve(1);
+			HIP_CHECK(hipMemsetAsync(c->dPartCount.p, 0, 8, s));
 			{ ScopedK t(c->timer, "k_probe_emit");
 			  hipLaunchKernelGGL(k_probe_emit, q1 - q0, WG, 0, s, q0, c->dQuery.p, qWords, qWordOff, qLen, c->dKmerOff.p, c->dQKmerOff.p,
-								 c->k, c->table, regionShift, c->hasQ ? (const u32*)nullptr : c->dIndexedBits.p, c->dPartK0.p, c->dPartV0.p); }
+								 c->k, c->table, regionShift, c->hasQ ? (const u32*)nullptr : c->dIndexedBits.p, probeSkipBits(c),
+								 n, c->dPartK0.p, c->dPartV0.p, c->dPartCount.p); }
+			// what is left to sort and probe: the sub-range's k-mers without those the build counted as too rare
+			unsigned long long nEmit = 0;
+			HIP_CHECK(hipMemcpyAsync(&nEmit, c->dPartCount.p, 8, hipMemcpyDeviceToHost, s));
+			HIP_CHECK(hipStreamSynchronize(s));
+			if (nEmit > n) throw FgError{FG_ERR_HIP, "internal: more probe pairs than query k-mers"};
+			if (nEmit == 0) { q0 = q1; continue; }
 			int which;
 			{ ScopedK t(c->timer, "k_probe_partition");
-			  which = fgprim::radixSortPairs(s, c->dPartK0.p, c->dPartV0.p, c->dPartK1.p, c->dPartV1.p, n, PART_KEY_BITS,
+			  which = fgprim::radixSortPairs(s, c->dPartK0.p, c->dPartV0.p, c->dPartK1.p, c->dPartV1.p, nEmit, PART_KEY_BITS,
 											 PART_KEY_BITS + PROBE_REGION_BITS, c->dPartScratch.p); }
 			{ ScopedK t(c->timer, "k_probe");
-			  hipLaunchKernelGGL(k_probe_sorted, (unsigned)((n + WG - 1) / WG), WG, 0, s, which ? c->dPartK1.p : c->dPartK0.p,
-								 which ? c->dPartV1.p : c->dPartV0.p, n, c->table, c->dProbe.p,
+			  hipLaunchKernelGGL(k_probe_sorted, (unsigned)((nEmit + WG - 1) / WG), WG, 0, s, which ? c->dPartK1.p : c->dPartK0.p,
+								 which ? c->dPartV1.p : c->dPartV0.p, (u64)nEmit, c->table, c->dProbe.p,
 								 getenv("FG_ABLATE_PROBE") ? atoi(getenv("FG_ABLATE_PROBE")) : 0); }
 		}
 		q0 = q1;
@@ -1177,13 +1268,14 @@ static void probeChunk(fg_ctx* c, const u32* hq, const u64* hQKmerOff, u32 qa, u
 	if (partition) probePartitioned(c, nq, localOff.data(), qWords, qWordOff, qLen);
 	else
 	{ ScopedK t(c->timer, "k_probe");
+	  const u32* skipBits = probeSkipBits(c);
 	  if (c->tableWide)
 		hipLaunchKernelGGL(k_probe<true>, nq, WG, 0, s, c->dQuery.p, qWords, qWordOff, qLen, c->dKmerOff.p,
-						   c->dQKmerOff.p, k, c->table, c->hasQ ? (const u32*)nullptr : c->dIndexedBits.p,
+						   c->dQKmerOff.p, k, c->table, c->hasQ ? (const u32*)nullptr : c->dIndexedBits.p, skipBits,
 						   c->dProbe.p, c->dCntA.p, c->dCntB.p);
 	  else
 		hipLaunchKernelGGL(k_probe<false>, nq, WG, 0, s, c->dQuery.p, qWords, qWordOff, qLen, c->dKmerOff.p,
-						   c->dQKmerOff.p, k, c->table, c->hasQ ? (const u32*)nullptr : c->dIndexedBits.p,
+						   c->dQKmerOff.p, k, c->table, c->hasQ ? (const u32*)nullptr : c->dIndexedBits.p, skipBits,
 						   c->dProbe.p, c->dCntA.p, c->dCntB.p); }
 	hitsPerQuery.resize(nq);
 	HIP_CHECK(hipMemcpyAsync(hitsPerQuery.data(), c->dCntA.p, nq * 8ULL, hipMemcpyDeviceToHost, s));
@@ -1476,7 +1568,7 @@ static fg_ctx* laneTwo(fg_ctx* c)
 	l->timer.enabled = c->timer.enabled;
 	l->dWords.alias(c->dWords); l->dWordOff.alias(c->dWordOff); l->dLen.alias(c->dLen); l->dKmerOff.alias(c->dKmerOff);
 	l->dQWords.alias(c->dQWords); l->dQWordOff.alias(c->dQWordOff); l->dQLen.alias(c->dQLen);
-	l->dKeyOff.alias(c->dKeyOff); l->dEntries.alias(c->dEntries); l->dTable.alias(c->dTable); l->dIndexedBits.alias(c->dIndexedBits);
+	l->dKeyOff.alias(c->dKeyOff); l->dEntries.alias(c->dEntries); l->dTable.alias(c->dTable); l->dIndexedBits.alias(c->dIndexedBits); l->dMaybeBits.alias(c->dMaybeBits);
 	l->dQuery.alias(c->dQuery); l->dQKmerOff.alias(c->dQKmerOff); l->dProbe.alias(c->dProbe);
 	l->dCntA.alias(c->dCntA); l->dCntB.alias(c->dCntB);
 	return l;

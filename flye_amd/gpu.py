@@ -44,7 +44,7 @@ ABI_SYMBOLS = ["fg_abi_version", "fg_create", "fg_destroy", "fg_strerror", "fg_l
                "fg_import_index", "fg_index_device_arrays", "fg_clear_index", "fg_export_index", "fg_overlaps", "fg_release_batch",
                "fg_kernel_times", "fg_debug_sort_pairs", "fg_debug_edit_distances", "fg_align_cigar_ksw", "fg_release_cigars",
                "fg_index_keep_targets", "fg_index_shard", "fg_probe_hits", "fg_overlaps_from_hits",
-               "fg_index_piece_split", "fg_index_scatter_begin", "fg_index_scatter_end"]
+               "fg_index_piece_split", "fg_index_scatter_begin", "fg_index_scatter_end", "fg_debug_probe_skip_check"]
 
 # struct fg_seed_hit: KmerMatch{curPos, extPos, extId} (overlap.cpp:176-196)
 SEED_HIT_DTYPE = np.dtype([("cur_pos", "<i4"), ("ext_pos", "<i4"), ("ext_id", "<u4")])
@@ -164,6 +164,7 @@ def load_library():
                                             C.c_uint8, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(OverlapBatch)]
         L.fg_kernel_times.argtypes = [C.c_void_p, C.POINTER(KernelTime), C.c_int]
         L.fg_debug_sort_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+        L.fg_debug_probe_skip_check.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.fg_debug_edit_distances.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.fg_align_cigar_ksw.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.POINTER(CigarBatch)]
@@ -332,6 +333,14 @@ class Context:
         self._check(self.L.fg_debug_sort_pairs(self.h, k.ctypes.data, v.ctypes.data, off.ctypes.data,
                                                len(off) - 1))
         return k, v
+
+    def debug_probe_skip_check(self):
+        """The probe skip's invariant over all indexed reads: (positions whose "frequent enough for a slot" bit is
+        clear, those of them whose k-mer has a slot in the lookup table all the same -- always 0).  (0, 0) where the
+        context holds no such bits."""
+        clear, bad = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.L.fg_debug_probe_skip_check(self.h, C.byref(clear), C.byref(bad)))
+        return int(clear.value), int(bad.value)
 
     def debug_edit_distances(self, n_pairs, use_hpc=False):
         """Device edit-distance kernels on the pairs (read 2i, read 2i+1) of the container;

@@ -361,6 +361,16 @@ int fg_kernel_times(fg_ctx* ctx, struct fg_kernel_time* out, int max_entries);
 int fg_debug_sort_pairs(fg_ctx* ctx, uint64_t* keys, uint32_t* vals,
                         const uint64_t* seg_off, uint32_t n_seg);
 
+/* Test hook for the probe skip of the overlap stage: one pass over the forward k-mer positions of all indexed reads.
+ * A solid-k-mer build leaves one bit per position, "the k-mer's frequency over the whole read set reached min_freq";
+ * where it is clear the seed collection takes the position for a miss without looking the k-mer up (a key enters the
+ * index only through a position with that frequency).  In a build in steps the bits are taken from the arrays
+ * fg_index_batch_select reads, which the caller has made complete over the ranks.  clear_bits: positions whose bit is
+ * clear; violations: those among them whose k-mer does have a slot in the context's lookup table -- always 0.  Both
+ * are 0 where the context holds no such bits (minimizer index, imported index, after fg_index_piece_split): every
+ * k-mer is then looked up.  The environment switch FG_PROBE_SKIP=0 makes the overlap stage ignore the bits. */
+int fg_debug_probe_skip_check(fg_ctx* ctx, uint64_t* clear_bits, uint64_t* violations);
+
 /* Test hook: the exact global edit distance (what edlibAlign(NW, TASK_DISTANCE, k = -1) returns,
  * reference src/sequence/alignment.cpp:233-238, src/sequence/edlib.cpp:141-296) of n_pairs string
  * pairs through the device kernels of the base-level divergence step.  Pair i = the forward
