@@ -421,8 +421,9 @@ int fg_export_index(fg_ctx* c, uint64_t* n_keys, uint64_t* n_entries, uint64_t* 
 	});
 }
 
-static int checkOverlapArgs(const fg_ctx* c, const struct fg_detector_params* p, const uint32_t* query_ids, uint32_t n_queries,
-							int32_t max_overlaps)
+} // extern "C"
+
+int fgCheckOverlapArgs(const fg_ctx* c, const fg_detector_params* p, const u32* query_ids, u32 n_queries, i32 max_overlaps)
 {
 	if (p->partition_bad_mappings && max_overlaps != 0) return FG_ERR_UNSUPPORTED;
 	if (p->max_jump <= 0 || p->min_overlap <= 0 || max_overlaps < 0) return FG_ERR_ARG;
@@ -432,6 +433,8 @@ static int checkOverlapArgs(const fg_ctx* c, const struct fg_detector_params* p,
 		if (query_ids[i] < base || query_ids[i] - base >= 2 * cnt) return FG_ERR_ARG;
 	return FG_OK;
 }
+
+extern "C" {
 
 int fg_index_keep_targets(fg_ctx* c, uint32_t world, uint32_t rank, uint64_t* n_entries_kept)
 {
@@ -507,7 +510,7 @@ int fg_overlaps_from_hits(fg_ctx* c, const struct fg_detector_params* p, const u
 	if (!c || !p || !out || (n_queries && !query_ids) || n_src == 0 || (n_queries && !hit_counts)) return FG_ERR_ARG;
 	memset(out, 0, sizeof(*out));
 	if (!c->indexBuilt) return FG_ERR_STATE;
-	const int chk = checkOverlapArgs(c, p, query_ids, n_queries, max_overlaps);
+	const int chk = fgCheckOverlapArgs(c, p, query_ids, n_queries, max_overlaps);
 	if (chk != FG_OK) return chk;
 	const int rc = guarded(c, [&]()
 	{
@@ -535,7 +538,7 @@ int fg_overlaps(fg_ctx* c, const struct fg_detector_params* p, const uint32_t* q
 			"(fg_index_keep_targets): collect seed hits with fg_probe_hits and compute overlaps with fg_overlaps_from_hits";
 		return FG_ERR_STATE;
 	}
-	const int chk = checkOverlapArgs(c, p, query_ids, n_queries, max_overlaps);
+	const int chk = fgCheckOverlapArgs(c, p, query_ids, n_queries, max_overlaps);
 	if (chk != FG_OK) return chk;
 	const int rc = guarded(c, [&]()
 	{
@@ -557,6 +560,16 @@ int fg_debug_sort_pairs(fg_ctx* c, uint64_t* keys, uint32_t* vals, const uint64_
 	{
 		HIP_CHECK(hipSetDevice(c->device));
 		fgDebugSortPairs(c, keys, vals, seg_off, n_seg);
+	});
+}
+
+int fg_debug_freq_accumulate(fg_ctx* c, uint32_t* dst, const uint32_t* src, uint64_t n)
+{
+	if (!c || (n && (!dst || !src)) || ((uintptr_t)dst & 3u) || ((uintptr_t)src & 3u)) return FG_ERR_ARG;
+	return guarded(c, [&]()
+	{
+		HIP_CHECK(hipSetDevice(c->device));
+		fgDebugFreqAccumulate(c, dst, src, n);
 	});
 }
 

@@ -684,3 +684,9 @@ void fgIndexScatterEnd(fg_ctx* c, float sampleRate);
 void fgProbeHits(fg_ctx* c, const u32* queryIds, u32 nq, u64* hitCounts, const fg_seed_hit** dHits, u64* nHits);
 void fgOverlapsFromHits(fg_ctx* c, const fg_detector_params* p, const u32* queryIds, u32 nq, i32 maxOverlaps,
 						uint8_t forceLocal, u32 nSrc, const u64* hitCounts, const fg_seed_hit* dHits, fg_overlap_batch* out);
+// several contexts of one process behind one handle (fg_group.hip): the frequency sum of a build over the members
+// (k_freq_accumulate, on the context's stream; dst 16-byte aligned for the vector path), its test hook, and the
+// argument checks fg_overlaps makes before it touches the device
+void fgFreqAccumulate(fg_ctx* c, u32* dst, const u32* src, u64 n);
+void fgDebugFreqAccumulate(fg_ctx* c, u32* dst, const u32* src, u64 n);
+int fgCheckOverlapArgs(const fg_ctx* c, const fg_detector_params* p, const u32* queryIds, u32 nq, i32 maxOverlaps);

@@ -1866,3 +1866,75 @@ void fgIndexScatterEnd(fg_ctx* c, float sampleRate)
 	c->shardWorld = world; c->shardRank = rank;
 	c->timer.collect();
 }
+
+// ---- the frequency sum of a build over several contexts of one process (fg_group.hip) -----------------------------
+namespace {
+
+// dst[i] += src[i] over uint32 (the sum wraps like the counters do).  One 16-byte load of each side and one 16-byte
+// store per lane and step; the elements in front of dst's first 16-byte boundary and behind the last whole vector go
+// one by one.  The group's staging buffer and the slices it cuts keep both sides aligned; a src that is not aligned
+// where dst is (the test hook) is read with four 4-byte loads per vector instead.
+__global__ void k_freq_accumulate(u32* __restrict__ dst, const u32* __restrict__ src, u64 n)
+{
+	const u64 toBoundary = ((16u - (u32)((uintptr_t)dst & 15u)) & 15u) / 4u;
+	const u64 head = toBoundary < n ? toBoundary : n;
+	const u64 nVec = (n - head) / 4;
+	const u64 tid = (u64)blockIdx.x * WG + threadIdx.x, stride = (u64)gridDim.x * WG;
+	uint4* __restrict__ d4 = (uint4*)(dst + head);
+	const u32* __restrict__ sBody = src + head;
+	if ((((uintptr_t)sBody) & 15u) == 0)
+	{
+		const uint4* __restrict__ s4 = (const uint4*)sBody;
+		for (u64 i = tid; i < nVec; i += stride)
+		{
+			uint4 a = d4[i];
+			const uint4 b = s4[i];
+			a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
+			d4[i] = a;
+		}
+	}
+	else
+	{
+		for (u64 i = tid; i < nVec; i += stride)
+		{
+			uint4 a = d4[i];
+			a.x += sBody[4 * i]; a.y += sBody[4 * i + 1]; a.z += sBody[4 * i + 2]; a.w += sBody[4 * i + 3];
+			d4[i] = a;
+		}
+	}
+	// at most 3 elements in front and 3 behind
+	const u64 tail0 = head + 4 * nVec;
+	if (tid < head) dst[tid] += src[tid];
+	else if (tid - head < n - tail0) dst[tail0 + (tid - head)] += src[tail0 + (tid - head)];
+}
+
+} // namespace
+
+void fgFreqAccumulate(fg_ctx* c, u32* dst, const u32* src, u64 n)
+{
+	if (!n) return;
+	// 4 vectors per lane at least; the grid-stride loop takes the rest (2048 blocks = 8 per CU)
+	const unsigned blocks = (unsigned)std::max<u64>(1, std::min<u64>(2048, (n / 4 + 4ULL * WG - 1) / (4ULL * WG)));
+	ScopedK t(c->timer, "k_freq_accumulate");
+	hipLaunchKernelGGL(k_freq_accumulate, blocks, WG, 0, c->stream, dst, src, n);
+}
+
+// test hook: host arrays through device copies that keep each pointer's offset inside its 16 bytes
+void fgDebugFreqAccumulate(fg_ctx* c, u32* dst, const u32* src, u64 n)
+{
+	hipStream_t s = c->stream;
+	c->timer.reset();
+	const size_t dOff = ((uintptr_t)dst & 15u) / 4, sOff = ((uintptr_t)src & 15u) / 4;
+	DevBuf<u32> dd, ds;
+	dd.alloc(n + 8); ds.alloc(n + 8);
+	if (n)
+	{
+		HIP_CHECK(hipMemcpyAsync(dd.p + dOff, dst, n * 4, hipMemcpyHostToDevice, s));
+		HIP_CHECK(hipMemcpyAsync(ds.p + sOff, src, n * 4, hipMemcpyHostToDevice, s));
+	}
+	fgFreqAccumulate(c, dd.p + dOff, ds.p + sOff, n);
+	HIP_CHECK(hipGetLastError());
+	if (n) HIP_CHECK(hipMemcpyAsync(dst, dd.p + dOff, n * 4, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(hipStreamSynchronize(s));
+	c->timer.collect();
+}

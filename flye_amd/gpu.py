@@ -44,7 +44,11 @@ ABI_SYMBOLS = ["fg_abi_version", "fg_create", "fg_destroy", "fg_strerror", "fg_l
                "fg_import_index", "fg_index_device_arrays", "fg_clear_index", "fg_export_index", "fg_overlaps", "fg_release_batch",
                "fg_kernel_times", "fg_debug_sort_pairs", "fg_debug_edit_distances", "fg_align_cigar_ksw", "fg_release_cigars",
                "fg_index_keep_targets", "fg_index_shard", "fg_probe_hits", "fg_overlaps_from_hits",
-               "fg_index_piece_split", "fg_index_scatter_begin", "fg_index_scatter_end", "fg_debug_probe_skip_check"]
+               "fg_index_piece_split", "fg_index_scatter_begin", "fg_index_scatter_end", "fg_debug_probe_skip_check",
+               "fg_group_create", "fg_group_destroy", "fg_group_size", "fg_group_member", "fg_group_last_error",
+               "fg_group_set_reads", "fg_group_set_queries", "fg_group_build_index_solid",
+               "fg_group_build_index_minimizers", "fg_group_clear_index", "fg_group_overlaps", "fg_group_stats",
+               "fg_group_build_info", "fg_debug_freq_accumulate", "fg_debug_group_bin_cuts"]
 
 # struct fg_seed_hit: KmerMatch{curPos, extPos, extId} (overlap.cpp:176-196)
 SEED_HIT_DTYPE = np.dtype([("cur_pos", "<i4"), ("ext_pos", "<i4"), ("ext_id", "<u4")])
@@ -93,6 +97,16 @@ class BridgeStats(C.Structure):
     _fields_ = [("device_calls", C.c_uint64), ("reads_computed", C.c_uint64), ("requests", C.c_uint64),
                 ("cache_hits", C.c_uint64), ("cached_overlaps", C.c_uint64), ("reads_ahead", C.c_uint64),
                 ("ahead_hits", C.c_uint64)]
+
+
+class GroupStats(C.Structure):
+    _fields_ = [("hits_moved_bytes", C.c_uint64), ("hits_total", C.c_uint64), ("peer_copies", C.c_uint64),
+                ("exchange_seconds", C.c_double)]
+
+
+class GroupBuildInfo(C.Structure):
+    _fields_ = [("selection_batches", C.c_uint32), ("stage_pieces_max", C.c_uint32), ("stage_pieces", C.c_uint64),
+                ("freq_bytes", C.c_uint64), ("scatter_bytes", C.c_uint64)]
 
 
 class KernelTime(C.Structure):
@@ -169,6 +183,27 @@ def load_library():
         L.fg_align_cigar_ksw.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.POINTER(CigarBatch)]
         L.fg_release_cigars.argtypes = [C.POINTER(CigarBatch)]
+        L.fg_debug_group_bin_cuts.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        L.fg_debug_freq_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        # device group: several contexts of this process behind one handle
+        L.fg_group_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_uint32, C.c_int]
+        L.fg_group_destroy.argtypes = [C.c_void_p]
+        L.fg_group_destroy.restype = None
+        L.fg_group_size.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        L.fg_group_member.restype = C.c_void_p
+        L.fg_group_member.argtypes = [C.c_void_p, C.c_uint32]
+        L.fg_group_last_error.restype = C.c_char_p
+        L.fg_group_last_error.argtypes = [C.c_void_p]
+        L.fg_group_set_reads.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+        L.fg_group_set_queries.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+        L.fg_group_build_index_solid.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_float, C.c_float,
+                                                 C.POINTER(IndexStats)]
+        L.fg_group_build_index_minimizers.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.POINTER(IndexStats)]
+        L.fg_group_clear_index.argtypes = [C.c_void_p]
+        L.fg_group_overlaps.argtypes = [C.c_void_p, C.POINTER(DetectorParams), C.c_void_p, C.c_uint32, C.c_int32,
+                                        C.c_uint8, C.POINTER(OverlapBatch)]
+        L.fg_group_stats.argtypes = [C.c_void_p, C.POINTER(GroupStats)]
+        L.fg_group_build_info.argtypes = [C.c_void_p, C.POINTER(GroupBuildInfo)]
         # include/flye_gpu_bridge.h
         L.fgb_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(DetectorParams), C.c_uint32, C.c_uint32]
         L.fgb_destroy.argtypes = [C.c_void_p]
@@ -300,7 +335,8 @@ class Context:
 
     def close(self):
         if getattr(self, "h", None):
-            self.L.fg_destroy(self.h)
+            if not getattr(self, "_borrowed", False):     # a group's member belongs to the group
+                self.L.fg_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -333,6 +369,15 @@ class Context:
         self._check(self.L.fg_debug_sort_pairs(self.h, k.ctypes.data, v.ctypes.data, off.ctypes.data,
                                                len(off) - 1))
         return k, v
+
+    def debug_freq_accumulate(self, dst, src):
+        """k_freq_accumulate on the device: ``dst += src`` in place over uint32 (wrapping).  The device copies sit at
+        the same offset inside 16 bytes as the host arrays do: a view that starts off a boundary takes the unaligned
+        path."""
+        assert dst.dtype == np.uint32 and src.dtype == np.uint32 and len(dst) == len(src)
+        assert dst.flags.c_contiguous and src.flags.c_contiguous
+        self._check(self.L.fg_debug_freq_accumulate(self.h, dst.ctypes.data, src.ctypes.data, len(dst)))
+        return dst
 
     def debug_probe_skip_check(self):
         """The probe skip's invariant over all indexed reads: (positions whose "frequent enough for a slot" bit is
@@ -652,6 +697,118 @@ class OverlapDetector:
 
     def ctx_device(self) -> int:
         return getattr(self.ctx, "device", 0)
+
+
+class Group:
+    """One fg_group: several contexts of this process, possibly on different devices, behind one handle -- the
+    target-sharded index (option B) built directly and the overlap stage over it, without a process group.
+    ``devices`` may name a device more than once."""
+
+    def __init__(self, devices, kmer_size=17):
+        self.L = load_library()
+        self.devices = [int(d) for d in devices]
+        self.k = kmer_size
+        self.h = None
+        h = C.c_void_p()
+        arr = (C.c_int * max(1, len(self.devices)))(*self.devices)
+        rc = self.L.fg_group_create(C.byref(h), arr, len(self.devices), kmer_size)
+        if rc != 0:
+            raise FlyeGpuError(rc, self.L.fg_strerror(rc).decode())
+        self.h = h
+        self.first_id = 0
+        self.n_reads = 0
+        self.stats_index = None
+
+    def _check(self, rc):
+        if rc != 0:
+            raise FlyeGpuError(rc, f"{self.L.fg_strerror(rc).decode()}: {self.L.fg_group_last_error(self.h).decode()}")
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.fg_group_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        n = C.c_uint32()
+        self._check(self.L.fg_group_size(self.h, C.byref(n)))
+        return n.value
+
+    def set_reads(self, rs, first_seq_id=0):
+        self.rs = rs
+        self.first_id = first_seq_id
+        self.n_reads = rs.n
+        self._check(self.L.fg_group_set_reads(self.h, rs.n, rs.words.ctypes.data, rs.word_off.ctypes.data,
+                                              rs.length.ctypes.data, first_seq_id))
+
+    def set_queries(self, rs, first_seq_id):
+        self.qrs = rs
+        self._check(self.L.fg_group_set_queries(self.h, rs.n, rs.words.ctypes.data, rs.word_off.ctypes.data,
+                                                rs.length.ctypes.data, first_seq_id))
+
+    def build(self, cfg: dict, sample_rate=None):
+        """The build main_assemble.cpp:195-223 selects (as ``VertexIndex.build``), every member ending with its
+        target shard; returns the statistics of the whole index."""
+        st = IndexStats()
+        if cfg["use_minimizers"]:
+            rc = self.L.fg_group_build_index_minimizers(self.h, 1, int(cfg["minimizer_window"]), cfg["repeat_kmer_rate"],
+                                                        C.byref(st))
+        else:
+            if self.k > 17:
+                raise FlyeGpuError(-6, "Can't use flat counter for k-mer size > 17")
+            rate = float(int(cfg["assemble_kmer_sample"])) if sample_rate is None else float(sample_rate)
+            rc = self.L.fg_group_build_index_solid(self.h, 2, cfg["meta_read_top_kmer_rate"],
+                                                   int(cfg["meta_read_filter_kmer_freq"]), cfg["repeat_kmer_rate"],
+                                                   rate, C.byref(st))
+        self._check(rc)
+        self.stats_index = st.as_dict()
+        return self.stats_index
+
+    def build_info(self) -> dict:
+        bi = GroupBuildInfo()
+        self._check(self.L.fg_group_build_info(self.h, C.byref(bi)))
+        return {k: int(getattr(bi, k)) for k, _ in bi._fields_}
+
+    def clear(self):
+        self._check(self.L.fg_group_clear_index(self.h))
+
+    def getSampleRate(self) -> float:
+        return self.stats_index["sample_rate"]
+
+    def overlaps(self, params, query_ids, forceLocal=False, maxOverlaps=0) -> OverlapResult:
+        """fg_group_overlaps: what ``OverlapDetector.getSeqOverlapsBatch`` gives on one context with the full index.
+        ``params``: a ``DetectorParams`` or a detector (its ``.p``)."""
+        p = getattr(params, "p", params)
+        q = np.ascontiguousarray(query_ids, dtype=np.uint32)
+        b = OverlapBatch()
+        self._check(self.L.fg_group_overlaps(self.h, C.byref(p), q.ctypes.data, len(q), maxOverlaps,
+                                             int(bool(forceLocal)), C.byref(b)))
+        return OverlapResult(self.L, q, b)
+
+    def stats(self) -> dict:
+        """of the last ``overlaps``"""
+        st = GroupStats()
+        self._check(self.L.fg_group_stats(self.h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in st._fields_}
+
+    def member(self, i: int) -> Context:
+        """Member i as a borrowed ``Context`` (kernel_times, ``VertexIndex(ctx, rate).export()`` / ``.shard()``, the
+        step calls of option B); the group keeps owning it."""
+        ptr = self.L.fg_group_member(self.h, int(i))
+        if not ptr:
+            raise FlyeGpuError(-3, f"no member {i}")
+        c = Context.__new__(Context)
+        c.L, c.h, c.k, c.device, c._borrowed = self.L, C.c_void_p(ptr), self.k, self.devices[int(i)], True
+        c.first_id, c.n_reads = self.first_id, self.n_reads
+        if hasattr(self, "rs"):
+            c.rs = self.rs
+        c._group = self                                # the handle outlives the view
+        return c
 
 
 def seed_hits_to_host(ptr: int, n: int, device: int = 0) -> np.ndarray:

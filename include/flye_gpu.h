@@ -350,6 +350,74 @@ int fg_overlaps_from_hits(fg_ctx* ctx, const struct fg_detector_params* p, const
                           const uint64_t* hit_counts, const struct fg_seed_hit* d_hits,
                           struct fg_overlap_batch* out);
 
+/* A DEVICE GROUP: several contexts of ONE process, possibly on different devices, behind one handle -- option B for a
+ * caller that is one multi-threaded process (Flye) and has no process group.  devices[i] is the HIP device of member
+ * i; a device may be named more than once (its members then share the chip).  A group of two or more members runs one
+ * host thread of its own per member, and a member is only ever touched by its thread (the caller's current device is
+ * left alone); a group of one member runs on the caller's thread and, like the plain fg_* calls, makes the member's
+ * device current there.  Between group calls fg_group_member(i) lends member i
+ * to the caller for the read-only calls of this header (fg_kernel_times, fg_index_shard, fg_export_index, ...).
+ * n_members == 0 or > 128 (the limit of fg_index_piece_split) is FG_ERR_ARG.  A group call that fails on a member
+ * returns that member's code, and fg_group_last_error names the member and carries its text.  The first
+ * fg_group_create of a process is subject to the note at fg_create.
+ *
+ * A group of ONE member is the plain context: fg_build_index_* and fg_overlaps, no split, no exchange.
+ *
+ * set_reads / set_queries give every member the same containers (replicated, as the one-process-per-GPU path does).
+ *
+ * fg_group_build_index_*: the index sharded by target read (member r keeps the entries of the reads i with
+ * i % n_members == r, exactly the shard of fg_index_keep_targets(n_members, r)), built directly from key-range pieces:
+ * key ranges balanced on fg_index_kmer_hist (solid) / the accepted positions (minimizers), per member count_slice,
+ * per batch of reads {batch_freq, the frequencies summed over the members, batch_select}, build_range, the two sums
+ * added up, finish, piece_split, scatter_begin, the pieces copied member to member (hipMemcpyPeerAsync), scatter_end.
+ * The frequency sum moves every member's share of the array through a staging buffer of at most FG_GROUP_STAGE_BYTES
+ * (environment, default 1 GiB) on the receiving member and adds it there (the one kernel of the group); then the
+ * complete shares are copied back.  No member maps another member's memory.  *out = the statistics of the WHOLE
+ * index, field for field what fg_build_index_* gives on one context (build_seconds: wall time of the call).
+ * fg_group_build_info: how the last build ran.
+ *
+ * fg_group_overlaps = fg_overlaps on the full index, field for field, counters included (device_seconds: the largest
+ * sum over a member of the kernel time of its fg_probe_hits calls and the device_seconds of its
+ * fg_overlaps_from_hits calls; the member-to-member copies between the two are NOT in it, their wall time is
+ * fg_group_stats.exchange_seconds).  The list is cut into batches of FG_GROUP_BATCH_READS queries
+ * (environment, default 4096); inside a batch the queries are listed grouped by owner (read i -> member
+ * i % n_members, both strands), caller's order inside an owner; every member probes that list against its shard
+ * (fg_probe_hits), so its hits for one owner are one contiguous segment; the segments go, sources in member order,
+ * into a receive buffer of the owner (grow-only, counted by fg_memory_stats), and the owner runs
+ * fg_overlaps_from_hits.  The result comes back in the CALLER's query order; release it with fg_release_batch.
+ * Before a build (or after fg_group_clear_index) every query call is FG_ERR_STATE. */
+typedef struct fg_group fg_group;
+int  fg_group_create(fg_group** out, const int* devices, uint32_t n_members, int kmer_size);
+void fg_group_destroy(fg_group* g);
+int  fg_group_size(const fg_group* g, uint32_t* n_members);
+fg_ctx* fg_group_member(fg_group* g, uint32_t i);   /* borrowed; NULL when i is out of range */
+const char* fg_group_last_error(const fg_group* g);
+int fg_group_set_reads(fg_group* g, uint32_t n_fwd, const uint64_t* words, const uint64_t* word_off,
+                       const int32_t* len, uint32_t first_seq_id);
+int fg_group_set_queries(fg_group* g, uint32_t n_fwd, const uint64_t* words, const uint64_t* word_off,
+                         const int32_t* len, uint32_t first_seq_id);
+int fg_group_build_index_solid(fg_group* g, int32_t min_freq, float select_rate, int32_t tandem_freq,
+                               float repeat_rate, float sample_rate_init, struct fg_index_stats* out);
+int fg_group_build_index_minimizers(fg_group* g, int32_t min_coverage, int32_t window, float repeat_rate,
+                                    struct fg_index_stats* out);
+int fg_group_clear_index(fg_group* g);
+int fg_group_overlaps(fg_group* g, const struct fg_detector_params* p, const uint32_t* query_ids,
+                      uint32_t n_queries, int32_t max_overlaps, uint8_t force_local,
+                      struct fg_overlap_batch* out);
+/* of the last fg_group_overlaps: bytes of seed hits copied to a member other than the one that produced them, seed
+ * hits in total, member-to-member copies issued (own segments included), wall time of the copies (per batch the
+ * slowest member's, added up) */
+struct fg_group_stats { uint64_t hits_moved_bytes, hits_total, peer_copies; double exchange_seconds; };
+int fg_group_stats(const fg_group* g, struct fg_group_stats* out);
+/* of the last fg_group_build_index_*: batches of reads of the solid selection (0 in minimizer mode), pieces that
+ * went through the staging buffers in total and the most that one member took from one other member in one batch,
+ * bytes the frequency sum and the scatter copied between members */
+struct fg_group_build_info {
+	uint32_t selection_batches, stage_pieces_max;
+	uint64_t stage_pieces, freq_bytes, scatter_bytes;
+};
+int fg_group_build_info(const fg_group* g, struct fg_group_build_info* out);
+
 /* Per-kernel device time of the most recent fg_overlaps / build call, measured
  * with hipEvents on the library's own stream.  names[i] are static strings. */
 struct fg_kernel_time { const char* name; double seconds; uint64_t launches; };
@@ -360,6 +428,15 @@ int fg_kernel_times(fg_ctx* ctx, struct fg_kernel_time* out, int max_entries);
  * pairs, in place in the caller's host arrays; seg_off has n_seg + 1 entries. */
 int fg_debug_sort_pairs(fg_ctx* ctx, uint64_t* keys, uint32_t* vals,
                         const uint64_t* seg_off, uint32_t n_seg);
+
+/* Test hook (host only): the key ranges a group build of `world` members cuts from hist[FG_INDEX_BINS]; member r
+ * gets the bins [cuts[r], cuts[r + 1]); cuts has world + 1 entries.  They equal dist.balanced_bin_ranges. */
+int fg_debug_group_bin_cuts(const uint64_t* hist, uint32_t world, uint32_t* cuts);
+
+/* Test hook: dst[i] += src[i] (uint32, wrapping) over n elements of the caller's host arrays through the device kernel
+ * of the group's frequency sum (k_freq_accumulate).  The device copies keep each pointer's offset inside its 16 bytes:
+ * an array that starts off a 16-byte boundary takes the kernel's unaligned path. */
+int fg_debug_freq_accumulate(fg_ctx* ctx, uint32_t* dst, const uint32_t* src, uint64_t n);
 
 /* Test hook for the probe skip of the overlap stage: one pass over the forward k-mer positions of all indexed reads.
  * A solid-k-mer build leaves one bit per position, "the k-mer's frequency over the whole read set reached min_freq";
