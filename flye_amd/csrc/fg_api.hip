@@ -573,6 +573,32 @@ int fg_debug_freq_accumulate(fg_ctx* c, uint32_t* dst, const uint32_t* src, uint
 	});
 }
 
+int fg_debug_scan(fg_ctx* c, void* data, uint64_t n, int elem_bytes, int inclusive, int in_place)
+{
+	if (!c || (n && !data) || (elem_bytes != 4 && elem_bytes != 8) || ((uintptr_t)data & (uintptr_t)(elem_bytes - 1)) ||
+		n > (1ULL << 40))
+		return FG_ERR_ARG;
+	return guarded(c, [&]()
+	{
+		HIP_CHECK(hipSetDevice(c->device));
+		fgDebugScan(c, data, n, elem_bytes, inclusive != 0, in_place != 0);
+	});
+}
+
+int fg_debug_radix_sort_pairs(fg_ctx* c, uint64_t* keys, uint64_t* vals, uint64_t n, int begin_bit, int end_bit,
+							  int* passes_run)
+{
+	if (!c || (n && (!keys || !vals)) || begin_bit < 0 || end_bit > 64 || begin_bit > end_bit || n > (1ULL << 30) - 1 ||
+		((uintptr_t)keys & 7u) || ((uintptr_t)vals & 7u))
+		return FG_ERR_ARG;
+	if (passes_run) *passes_run = 0;
+	return guarded(c, [&]()
+	{
+		HIP_CHECK(hipSetDevice(c->device));
+		fgDebugRadixSortPairs(c, keys, vals, n, begin_bit, end_bit, passes_run);
+	});
+}
+
 int fg_debug_probe_skip_check(fg_ctx* c, uint64_t* clear_bits, uint64_t* violations)
 {
 	if (!c || !clear_bits || !violations) return FG_ERR_ARG;

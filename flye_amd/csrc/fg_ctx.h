@@ -690,3 +690,6 @@ void fgOverlapsFromHits(fg_ctx* c, const fg_detector_params* p, const u32* query
 void fgFreqAccumulate(fg_ctx* c, u32* dst, const u32* src, u64 n);
 void fgDebugFreqAccumulate(fg_ctx* c, u32* dst, const u32* src, u64 n);
 int fgCheckOverlapArgs(const fg_ctx* c, const fg_detector_params* p, const u32* queryIds, u32 nq, i32 maxOverlaps);
+// test hooks of the device primitives (fg_devprim.h) on host arrays, every device buffer followed by a guard
+void fgDebugScan(fg_ctx* c, void* data, u64 n, int elemBytes, bool inclusive, bool inPlace);
+void fgDebugRadixSortPairs(fg_ctx* c, u64* keys, u64* vals, u64 n, int beginBit, int endBit, int* passesRun);

@@ -125,9 +125,10 @@ constexpr u64 RS_MAX_N = (1ULL << 30) - 1;		// a status word carries a 30-bit ru
 
 namespace {		// kernels of a header shared by several translation units: one internal copy each
 
-// digit counts of every pass in one sweep over the keys: hist[pass * 256 + digit]
+// digit counts of every pass in one sweep over the keys: hist[pass * 256 + digit]; lastMask = the bits of the last
+// pass's digit that lie below endBit (255 where the range ends on a digit boundary)
 __global__ void __launch_bounds__(RS_THREADS) k_rs_hist(const u64* __restrict__ keys, u64 n, int beginBit, int nPasses,
-														 unsigned long long* __restrict__ hist)
+														 u32 lastMask, unsigned long long* __restrict__ hist)
 {
 	__shared__ u32 sh[RS_MAX_PASSES * RS_RADIX];
 	for (int i = threadIdx.x; i < nPasses * RS_RADIX; i += RS_THREADS) sh[i] = 0;
@@ -137,7 +138,8 @@ __global__ void __launch_bounds__(RS_THREADS) k_rs_hist(const u64* __restrict__ 
 	for (u64 i = a + threadIdx.x; i < b; i += RS_THREADS)
 	{
 		const u64 k = keys[i] >> beginBit;
-		for (int p = 0; p < nPasses; ++p) atomicAdd(&sh[p * RS_RADIX + (int)((k >> (8 * p)) & 255)], 1u);
+		for (int p = 0; p < nPasses; ++p)
+			atomicAdd(&sh[p * RS_RADIX + (int)((u32)(k >> (8 * p)) & (p == nPasses - 1 ? lastMask : 255u))], 1u);
 	}
 	__syncthreads();
 	for (int i = threadIdx.x; i < nPasses * RS_RADIX; i += RS_THREADS)
@@ -146,10 +148,10 @@ __global__ void __launch_bounds__(RS_THREADS) k_rs_hist(const u64* __restrict__ 
 
 // One pass.  Tiles take their number from a ticket counter, so every tile a tile waits for in the look-back has
 // started before it and never waits for a later one: the waits end.  A spin bound turns a protocol bug into an
-// error flag instead of a hung GPU.
+// error flag instead of a hung GPU.  digitMask: 255, or the bits of the digit below endBit in the range's last pass.
 __global__ void __launch_bounds__(RS_THREADS)
 k_rs_onesweep(const u64* __restrict__ keysIn, const u64* __restrict__ valsIn, u64* __restrict__ keysOut,
-			  u64* __restrict__ valsOut, u64 n, int shift, const u64* __restrict__ digitStart /* 256: exclusive counts */,
+			  u64* __restrict__ valsOut, u64 n, int shift, u32 digitMask, const u64* __restrict__ digitStart /* 256: exclusive counts */,
 			  u32* status /* tiles * 256 */, u32* ticket, u32* err)
 {
 	__shared__ u64 sKey[RS_TILE];
@@ -182,7 +184,7 @@ k_rs_onesweep(const u64* __restrict__ keysIn, const u64* __restrict__ valsIn, u6
 	for (int i = 0; i < RS_ITEMS; ++i)
 	{
 		const bool valid = base + (u64)i * 64 + lane < n;
-		const u32 d = (u32)(k[i] >> shift) & 255u;
+		const u32 d = (u32)(k[i] >> shift) & digitMask;
 		// lanes of this item holding the same digit
 		u64 peers = __ballot(valid);
 #pragma unroll
@@ -244,7 +246,7 @@ k_rs_onesweep(const u64* __restrict__ keysIn, const u64* __restrict__ valsIn, u6
 	for (int i = 0; i < RS_ITEMS; ++i)
 	{
 		const bool valid = base + (u64)i * 64 + lane < n;
-		const u32 dg = (u32)(k[i] >> shift) & 255u;
+		const u32 dg = (u32)(k[i] >> shift) & digitMask;
 		if (valid)
 		{
 			const u32 slot = sTileStart[dg] + waveHist[wv][dg] + rk[i];
@@ -260,7 +262,7 @@ k_rs_onesweep(const u64* __restrict__ keysIn, const u64* __restrict__ valsIn, u6
 		if (j < tot)
 		{
 			const u64 kk = sKey[j];
-			const long long dst = sOffs[(u32)(kk >> shift) & 255u] + (long long)j;
+			const long long dst = sOffs[(u32)(kk >> shift) & digitMask] + (long long)j;
 			keysOut[dst] = kk;
 			valsOut[dst] = sVal[j];
 		}
@@ -279,15 +281,19 @@ inline size_t radixSortScratchBytes(u64 n)
 }
 
 #if defined(__HIPCC__)
-// Sorts n (key, value) pairs by bits [beginBit, endBit) of the key, stable.  (k0, v0) hold the input, (k1, v1) are
-// buffers of the same size; returns 0 when the result is in (k0, v0), 1 when it is in (k1, v1).
-inline int radixSortPairs(hipStream_t s, u64* k0, u64* v0, u64* k1, u64* v1, u64 n, int beginBit, int endBit, char* scratch)
+// Sorts n (key, value) pairs by bits [beginBit, endBit) of the key, stable; key bits outside the range take no part.
+// (k0, v0) hold the input, (k1, v1) are buffers of the same size; returns 0 when the result is in (k0, v0), 1 when
+// it is in (k1, v1).  *passesRun (optional) = the onesweep passes launched.
+inline int radixSortPairs(hipStream_t s, u64* k0, u64* v0, u64* k1, u64* v1, u64 n, int beginBit, int endBit, char* scratch,
+						  int* passesRun = nullptr)
 {
+	if (passesRun) *passesRun = 0;
 	if (n <= 1 || endBit <= beginBit) return 0;
 	if (n > RS_MAX_N) throw FgError{FG_ERR_ARG, "radix sort: more than 2^30 - 1 pairs in one call"};
 	const int nPasses = (endBit - beginBit + 7) / 8;
 	if (nPasses > RS_MAX_PASSES) throw FgError{FG_ERR_ARG, "radix sort: more than 64 key bits"};
 	const u64 nTiles = (n + RS_TILE - 1) / RS_TILE;
+	const u32 lastMask = (endBit - beginBit) % 8 ? (1u << ((endBit - beginBit) % 8)) - 1u : 255u;
 	u32* status = (u32*)scratch;
 	unsigned long long* hist = (unsigned long long*)(scratch + nTiles * RS_RADIX * 4);
 	u64* digitStart = (u64*)(hist + RS_MAX_PASSES * RS_RADIX);
@@ -296,7 +302,7 @@ inline int radixSortPairs(hipStream_t s, u64* k0, u64* v0, u64* k1, u64* v1, u64
 	HIP_CHECK(hipMemsetAsync(hist, 0, RS_MAX_PASSES * RS_RADIX * 8, s));
 	HIP_CHECK(hipMemsetAsync(ticket, 0, 8, s));
 	const unsigned histBlocks = (unsigned)std::min<u64>(2048, (n + RS_THREADS * 16 - 1) / (RS_THREADS * 16));
-	hipLaunchKernelGGL(k_rs_hist, histBlocks, RS_THREADS, 0, s, k0, n, beginBit, nPasses, hist);
+	hipLaunchKernelGGL(k_rs_hist, histBlocks, RS_THREADS, 0, s, k0, n, beginBit, nPasses, lastMask, hist);
 	std::vector<unsigned long long> h((size_t)nPasses * RS_RADIX);
 	HIP_CHECK(hipMemcpyAsync(h.data(), hist, h.size() * 8, hipMemcpyDeviceToHost, s));
 	HIP_CHECK(hipStreamSynchronize(s));
@@ -320,8 +326,10 @@ inline int radixSortPairs(hipStream_t s, u64* k0, u64* v0, u64* k1, u64* v1, u64
 		HIP_CHECK(hipMemsetAsync(status, 0, nTiles * RS_RADIX * 4, s));
 		HIP_CHECK(hipMemsetAsync(ticket, 0, 4, s));
 		hipLaunchKernelGGL(k_rs_onesweep, (unsigned)nTiles, RS_THREADS, 0, s, cur ? k1 : k0, cur ? v1 : v0, cur ? k0 : k1,
-						   cur ? v0 : v1, n, beginBit + 8 * p, digitStart + (size_t)p * RS_RADIX, status, ticket, err);
+						   cur ? v0 : v1, n, beginBit + 8 * p, p == nPasses - 1 ? lastMask : 255u, digitStart + (size_t)p * RS_RADIX,
+						   status, ticket, err);
 		cur ^= 1;
+		if (passesRun) ++*passesRun;
 	}
 	u32 herr = 0;
 	HIP_CHECK(hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, s));

@@ -1938,3 +1938,89 @@ void fgDebugFreqAccumulate(fg_ctx* c, u32* dst, const u32* src, u64 n)
 	HIP_CHECK(hipStreamSynchronize(s));
 	c->timer.collect();
 }
+
+// ---- test hooks of the device primitives (fg_devprim.h) --------------------------------------------------------------
+// Every device buffer holds exactly what the primitive is promised, followed in the same allocation by a guard of
+// fixed bytes: a primitive that writes past a buffer (or needs more scratch than its size function says) changes the
+// guard, which is an error of the call.
+namespace {
+
+constexpr size_t PRIM_GUARD_BYTES = 256;
+constexpr int PRIM_GUARD_FILL = 0xC3;
+
+struct GuardedBuf {
+	DevBuf<unsigned char> b;
+	size_t payload = 0;
+	const char* what = "";
+	void alloc(size_t bytes, const char* name, hipStream_t s)
+	{
+		payload = bytes; what = name;
+		b.alloc(bytes + PRIM_GUARD_BYTES);
+		HIP_CHECK(hipMemsetAsync(b.p + bytes, PRIM_GUARD_FILL, PRIM_GUARD_BYTES, s));
+	}
+	template <class T> T* as() { return (T*)b.p; }
+	// after a stream sync
+	void check(const char* prim)
+	{
+		unsigned char g[PRIM_GUARD_BYTES];
+		HIP_CHECK(hipMemcpy(g, b.p + payload, PRIM_GUARD_BYTES, hipMemcpyDeviceToHost));
+		for (size_t i = 0; i < PRIM_GUARD_BYTES; ++i)
+			if (g[i] != (unsigned char)PRIM_GUARD_FILL)
+				throw FgError{FG_ERR_HIP, std::string("internal: ") + prim + " wrote past " + what + " (guard byte " +
+										  std::to_string(i) + ")"};
+	}
+};
+
+template <class T>
+void debugScan(fg_ctx* c, T* data, u64 n, bool inclusive, bool inPlace)
+{
+	hipStream_t s = c->stream;
+	GuardedBuf in, out, scratch;
+	in.alloc(n * sizeof(T), "the input", s);
+	if (!inPlace) out.alloc(n * sizeof(T), "the output", s);
+	scratch.alloc(fgprim::scanScratchElems(n) * sizeof(T), "the scratch", s);
+	if (n) HIP_CHECK(hipMemcpyAsync(in.b.p, data, n * sizeof(T), hipMemcpyHostToDevice, s));
+	T* res = inPlace ? in.as<T>() : out.as<T>();
+	fgprim::scan<T>(s, in.as<T>(), res, n, inclusive, scratch.as<T>());
+	HIP_CHECK(hipGetLastError());
+	if (n) HIP_CHECK(hipMemcpyAsync(data, res, n * sizeof(T), hipMemcpyDeviceToHost, s));
+	HIP_CHECK(hipStreamSynchronize(s));
+	in.check("scan");
+	if (!inPlace) out.check("scan");
+	scratch.check("scan");
+}
+
+} // namespace
+
+void fgDebugScan(fg_ctx* c, void* data, u64 n, int elemBytes, bool inclusive, bool inPlace)
+{
+	if (elemBytes == 4) debugScan<u32>(c, (u32*)data, n, inclusive, inPlace);
+	else debugScan<u64>(c, (u64*)data, n, inclusive, inPlace);
+}
+
+void fgDebugRadixSortPairs(fg_ctx* c, u64* keys, u64* vals, u64 n, int beginBit, int endBit, int* passesRun)
+{
+	hipStream_t s = c->stream;
+	GuardedBuf k[2], v[2], scratch;
+	k[0].alloc(n * 8, "the keys", s); v[0].alloc(n * 8, "the values", s);
+	k[1].alloc(n * 8, "the second key buffer", s); v[1].alloc(n * 8, "the second value buffer", s);
+	scratch.alloc(fgprim::radixSortScratchBytes(n), "the scratch", s);
+	if (n)
+	{
+		HIP_CHECK(hipMemcpyAsync(k[0].b.p, keys, n * 8, hipMemcpyHostToDevice, s));
+		HIP_CHECK(hipMemcpyAsync(v[0].b.p, vals, n * 8, hipMemcpyHostToDevice, s));
+	}
+	int passes = 0;
+	const int which = fgprim::radixSortPairs(s, k[0].as<u64>(), v[0].as<u64>(), k[1].as<u64>(), v[1].as<u64>(), n, beginBit,
+											 endBit, (char*)scratch.b.p, &passes);
+	HIP_CHECK(hipGetLastError());
+	if (n)
+	{
+		HIP_CHECK(hipMemcpyAsync(keys, k[which].b.p, n * 8, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(hipMemcpyAsync(vals, v[which].b.p, n * 8, hipMemcpyDeviceToHost, s));
+	}
+	HIP_CHECK(hipStreamSynchronize(s));
+	for (int i = 0; i < 2; ++i) { k[i].check("radix sort"); v[i].check("radix sort"); }
+	scratch.check("radix sort");
+	if (passesRun) *passesRun = passes;
+}

@@ -1322,7 +1322,8 @@ static void recvFill(fg_ctx* c, const RecvHits* recv, u32 callQ0, u32 sub0, u32 
 	HIP_CHECK(hipStreamSynchronize(s));		// also keeps `run` alive until its copy has run
 	while ((1ULL << gBits) < hQK[1] - hQK[0]) ++gBits;
 	const int storedBits = recBits + posBits;
-	const bool onePass = gBits + storedBits <= 64;
+	// FG_RECV_TWO_PASS=1 (tests): the two-pass form at any size
+	const bool onePass = gBits + storedBits <= 64 && !(getenv("FG_RECV_TWO_PASS") && atoi(getenv("FG_RECV_TWO_PASS")) != 0);
 	const bool qs = c->hasQ;
 	{ ScopedK t(c->timer, "k_recv_keys");
 	  hipLaunchKernelGGL(k_recv_keys, nq, WG, 0, s, dQuery, dQKmerOff, qs ? c->dQWords.p : c->dWords.p, qs ? c->dQWordOff.p : c->dWordOff.p,

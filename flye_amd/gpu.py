@@ -48,7 +48,8 @@ ABI_SYMBOLS = ["fg_abi_version", "fg_create", "fg_destroy", "fg_strerror", "fg_l
                "fg_group_create", "fg_group_destroy", "fg_group_size", "fg_group_member", "fg_group_last_error",
                "fg_group_set_reads", "fg_group_set_queries", "fg_group_build_index_solid",
                "fg_group_build_index_minimizers", "fg_group_clear_index", "fg_group_overlaps", "fg_group_stats",
-               "fg_group_build_info", "fg_debug_freq_accumulate", "fg_debug_group_bin_cuts"]
+               "fg_group_build_info", "fg_debug_freq_accumulate", "fg_debug_group_bin_cuts", "fg_debug_scan",
+               "fg_debug_radix_sort_pairs"]
 
 # struct fg_seed_hit: KmerMatch{curPos, extPos, extId} (overlap.cpp:176-196)
 SEED_HIT_DTYPE = np.dtype([("cur_pos", "<i4"), ("ext_pos", "<i4"), ("ext_id", "<u4")])
@@ -185,6 +186,9 @@ def load_library():
         L.fg_release_cigars.argtypes = [C.POINTER(CigarBatch)]
         L.fg_debug_group_bin_cuts.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         L.fg_debug_freq_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        L.fg_debug_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int]
+        L.fg_debug_radix_sort_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int,
+                                                C.POINTER(C.c_int)]
         # device group: several contexts of this process behind one handle
         L.fg_group_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_uint32, C.c_int]
         L.fg_group_destroy.argtypes = [C.c_void_p]
@@ -378,6 +382,26 @@ class Context:
         assert dst.flags.c_contiguous and src.flags.c_contiguous
         self._check(self.L.fg_debug_freq_accumulate(self.h, dst.ctypes.data, src.ctypes.data, len(dst)))
         return dst
+
+    def debug_scan(self, data, inclusive=False, in_place=True):
+        """fgprim::scan on the device over a uint32 / uint64 array (sums modulo 2^width); returns a new array."""
+        assert data.dtype in (np.uint32, np.uint64)
+        out = np.ascontiguousarray(data).copy()
+        self._check(self.L.fg_debug_scan(self.h, out.ctypes.data if len(out) else None, len(out), out.dtype.itemsize,
+                                         int(bool(inclusive)), int(bool(in_place))))
+        return out
+
+    def debug_radix_sort_pairs(self, keys, vals, begin_bit, end_bit):
+        """fgprim::radixSortPairs on the device: stable by bits [begin_bit, end_bit) of the uint64 keys; returns
+        (keys, values, onesweep passes launched)."""
+        k = np.ascontiguousarray(keys, np.uint64).copy()
+        v = np.ascontiguousarray(vals, np.uint64).copy()
+        assert len(k) == len(v)
+        passes = C.c_int(-1)
+        self._check(self.L.fg_debug_radix_sort_pairs(self.h, k.ctypes.data if len(k) else None,
+                                                     v.ctypes.data if len(v) else None, len(k), begin_bit, end_bit,
+                                                     C.byref(passes)))
+        return k, v, int(passes.value)
 
     def debug_probe_skip_check(self):
         """The probe skip's invariant over all indexed reads: (positions whose "frequent enough for a slot" bit is

@@ -438,6 +438,22 @@ int fg_debug_group_bin_cuts(const uint64_t* hist, uint32_t world, uint32_t* cuts
  * an array that starts off a 16-byte boundary takes the kernel's unaligned path. */
 int fg_debug_freq_accumulate(fg_ctx* ctx, uint32_t* dst, const uint32_t* src, uint64_t n);
 
+/* Test hook: the device-wide prefix sum of the index build (fgprim::scan) over n elements of elem_bytes (4 or 8) bytes
+ * in the caller's host array, in place: data[i] becomes the sum of data[0 .. i), or of data[0 .. i] when inclusive;
+ * sums are modulo 2^(8 elem_bytes).  in_place != 0 runs the device scan with its output on its input, as the index
+ * build does; otherwise on separate buffers.  Every device buffer has exactly the size the primitive is promised (the
+ * scratch what its size function says) with a guard region behind it: a write past one is an FG_ERR_HIP.
+ * n <= 2^40. */
+int fg_debug_scan(fg_ctx* ctx, void* data, uint64_t n, int elem_bytes, int inclusive, int in_place);
+
+/* Test hook: the stable radix sort of the index build and of the seed-hit exchange (fgprim::radixSortPairs) on n
+ * (key, value) pairs of the caller's host arrays, in place: ordered by bits [begin_bit, end_bit) of the key alone,
+ * pairs equal in those bits in their input order.  0 <= begin_bit <= end_bit <= 64, n <= 2^30 - 1; an empty bit
+ * range leaves the arrays as they are.  passes_run (may be null): the 8-bit passes launched -- a pass in which every
+ * key has the same digit is skipped.  Buffers are guarded as for fg_debug_scan. */
+int fg_debug_radix_sort_pairs(fg_ctx* ctx, uint64_t* keys, uint64_t* vals, uint64_t n, int begin_bit, int end_bit,
+                              int* passes_run);
+
 /* Test hook for the probe skip of the overlap stage: one pass over the forward k-mer positions of all indexed reads.
  * A solid-k-mer build leaves one bit per position, "the k-mer's frequency over the whole read set reached min_freq";
  * where it is clear the seed collection takes the position for a miss without looking the k-mer up (a key enters the

@@ -197,11 +197,17 @@ def test_group_build_gives_the_keep_targets_shards(built, monkeypatch, world, pr
 # ---- 2. + 3. the overlap stage and its accounting ------------------------------------------------------------------------
 @pytest.mark.gpu
 @pytest.mark.parametrize("preset,kind", PRESETS)
-@pytest.mark.parametrize("world", [2, 3])
-def test_group_overlaps_assemble_flags_and_accounting(built, monkeypatch, world, preset, kind):
+@pytest.mark.parametrize("world,two_pass", [pytest.param(2, False, id="2"), pytest.param(3, False, id="3"),
+                                            pytest.param(2, True, id="2-two_pass")])
+def test_group_overlaps_assemble_flags_and_accounting(built, monkeypatch, world, two_pass, preset, kind):
     """every forward read, then a mixed list; >= 3 batches, one of them without a query for some owner; moved bytes
-    and hit totals against the members' own fg_probe_hits"""
+    and hit totals against the members' own fg_probe_hits.  two_pass: the members restore the emission order of the
+    received hits with two stable sorts (FG_RECV_TWO_PASS=1), the form of read sets far beyond test size."""
     from flye_amd import gpu
+    if two_pass:
+        monkeypatch.setenv("FG_RECV_TWO_PASS", "1")
+    else:
+        monkeypatch.delenv("FG_RECV_TWO_PASS", raising=False)
     cfg, rs, _, ctx, vi = _single(preset, kind)
     g = _group(world, preset, kind)
     p = _params(cfg)

@@ -177,11 +177,25 @@ def _tagged(counts, hits):
     return rows[np.lexsort(rows.T[::-1])]
 
 
+# FG_RECV_TWO_PASS=1: the receiver restores the emission order with two stable sorts (stored side, then query k-mer),
+# the form a read set takes whose full key exceeds 64 bits
+TWO_PASS = [pytest.param(False, id="auto"), pytest.param(True, id="two_pass")]
+
+
+def _recv_form(monkeypatch, two_pass):
+    if two_pass:
+        monkeypatch.setenv("FG_RECV_TWO_PASS", "1")
+    else:
+        monkeypatch.delenv("FG_RECV_TWO_PASS", raising=False)
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("world", [2, 3])
+@pytest.mark.parametrize("world,two_pass", [pytest.param(2, False, id="2"), pytest.param(3, False, id="3"),
+                                            pytest.param(2, True, id="2-two_pass"), pytest.param(3, True, id="3-two_pass")])
 @pytest.mark.parametrize("preset,kind", [("raw", "pb_raw"), ("hifi", "hifi")])
-def test_option_b_equals_full_index(built, preset, kind, world):
+def test_option_b_equals_full_index(built, monkeypatch, preset, kind, world, two_pass):
     from flye_amd import config
+    _recv_form(monkeypatch, two_pass)
     cfg = config.preset(preset)
     rs = _reads(kind)
     ctx, vi = _index(rs, cfg)
@@ -205,10 +219,12 @@ def test_option_b_equals_full_index(built, preset, kind, world):
 
 
 @pytest.mark.gpu
-def test_option_b_repeat_stage_flags_rc_queries_first_id(built):
+@pytest.mark.parametrize("two_pass", TWO_PASS)
+def test_option_b_repeat_stage_flags_rc_queries_first_id(built, monkeypatch, two_pass):
     """only_max_ext = 0, keep_alignment, partition_bad_mappings; max_overlaps > 0; reverse-complement query ids;
     first_seq_id != 0"""
     from flye_amd import config
+    _recv_form(monkeypatch, two_pass)
     cfg = config.preset("raw")
     rs = _reads("pb_raw", seed=77)
     first, world = 10, 2
