@@ -397,6 +397,17 @@ struct fg_ctx {
 	DevBuf<u32> dEditList;		// pairs queued for the bit-vector kernel (two lists)
 	DevBuf<char> dEditCnt;
 	DevBuf<u64> dEditSlab;		// per-block string planes + delta planes of the bit-vector kernel
+	// fg_align_ranges (fg_ksw.hip): the (pair, side) table, the compressed lengths, the byte strings the ksw kernels
+	// read and where each one starts, and what the decoding of a sub-batch leaves (counts, offsets, '=' / 'X' / 'I' /
+	// 'D' runs)
+	DevBuf<char> dRangeSides;
+	DevBuf<i32> dRangeLen;
+	DevBuf<u64> dRangeOff;
+	DevBuf<uint8_t> dRangeTrg, dRangeQry;
+	DevBuf<u32> dDecCnt;
+	DevBuf<u64> dDecOff;
+	DevBuf<uint8_t> dDecOps;
+	DevBuf<i32> dDecLens;
 	PinnedBuf<char> hPrim;
 	PinnedBuf<u64> hOff;
 	PinnedBuf<u64> hScalar;		// staging of the counts the host reads between kernels (pinned: no bounce buffer)
@@ -487,6 +498,32 @@ __device__ __forceinline__ u64 fg_mix(u64 x)
 	x ^= x >> 33; x *= 0xff51afd7ed558ccdULL; x ^= x >> 33;
 	x *= 0xc4ceb9fe1a85ec53ULL; x ^= x >> 33;
 	return x;
+}
+
+// base `pos` of a record on the strand asked for (reference sequence.h:120-129); w = the record's forward words
+__device__ __forceinline__ u32 fg_base_at(const u64* __restrict__ w, i32 L, bool rc, i32 pos)
+{
+	const i32 p = rc ? L - 1 - pos : pos;
+	const u32 b = (u32)((w[p >> 5] >> ((p & 31) * 2)) & 3);
+	return rc ? (~b & 3) : b;
+}
+
+// One 64-base step of a walk over [start, start + len) of a record, all 64 lanes: lane l takes base t0 + l of the
+// range.  b = its base (0 behind the range), keep = inside the range and, with hpc, not a repeat of the base before
+// it (homopolymerCompression, alignment.cpp:52-70); carry = the last base of the previous step (4 before the first
+// one: the first base of a range is always kept), updated for the next.  Returns the ballot of keep.
+__device__ __forceinline__ u64 fg_range_step(const u64* __restrict__ w, i32 L, bool rc, i32 start, i32 len, bool hpc,
+											 i32 t0, u32& carry, u32& b, bool& keep)
+{
+	const int lane = threadIdx.x & 63;
+	const i32 t = t0 + lane;
+	const bool valid = t < len;
+	b = valid ? fg_base_at(w, L, rc, start + t) : 0u;
+	u32 prev = __shfl_up(b, 1);
+	if (lane == 0) prev = carry;
+	keep = valid && (!hpc || prev != b);
+	carry = __shfl(b, 63);
+	return __builtin_amdgcn_ballot_w64(keep);
 }
 
 // splitmix64 finaliser = Kmer::hash() (reference src/sequence/kmer.h:91-98)
@@ -660,6 +697,13 @@ void fgChainStage(fg_ctx* c, const fg_detector_params* p, uint8_t forceLocal, u6
 void fgEditDistances(fg_ctx* c, PrimRec* dPrims, u64 nPrim, int useHpc);
 void fgKswAlign(fg_ctx* c, u32 nPairs, const uint8_t* trg, const u64* trgOff, const uint8_t* qry, const u64* qryOff,
 				std::vector<u64>& runOff, std::vector<u32>& runs);
+// fg_align_ranges behind its argument checks: sides = 2 nPairs entries (target, query of pair 0, ...); runs of pair i
+// at ops / lens[runOff[i] ..), errBases = its mismatches + indel bases, lenCur / lenExt = the aligned lengths
+struct FgRangeSide { u32 rec; u32 flags; i32 start, len; };		// rec: index in its container; flags: 1 = reverse
+																// complement, 2 = the fg_set_queries container
+void fgAlignRanges(fg_ctx* c, const std::vector<FgRangeSide>& sides, bool useHpc, std::vector<u64>& runOff,
+				   std::vector<uint8_t>& ops, std::vector<i32>& lens, std::vector<u32>& errBases, std::vector<i32>& lenCur,
+				   std::vector<i32>& lenExt);
 void fgDebugSortPairs(fg_ctx* c, u64* keys, u32* vals, const u64* segOff, u32 nSeg);
 void fgDebugProbeSkipCheck(fg_ctx* c, u64* clearBits, u64* violations);
 void fgDebugEditDistances(fg_ctx* c, u32 nPairs, int useHpc, i32* outDist, i32* outLenA, i32* outLenB);

@@ -43,14 +43,6 @@ namespace {
 
 struct EdCounters { u32 nSmall, nBig; unsigned long long maxWordsSmall, maxWordsBig; };
 
-// base t of record `rec` (strand-aware, reference sequence.h:120-129)
-__device__ __forceinline__ u32 base_at(const u64* __restrict__ w, i32 L, bool rc, i32 pos)
-{
-	const i32 p = rc ? L - 1 - pos : pos;
-	const u32 b = (u32)((w[p >> 5] >> ((p & 31) * 2)) & 3);
-	return rc ? (~b & 3) : b;
-}
-
 // u64 words a pair needs in the bit-vector kernel's slab: both strings as planes (+ 2 zero
 // blocks each) and the two delta planes of the text
 __host__ __device__ __forceinline__ u64 ed_words_a(i32 curRange) { return 2ULL * ((u64)(curRange + 63) / 64 + 2); }
@@ -71,13 +63,9 @@ __device__ int extract_planes(const u64* __restrict__ w, i32 L, bool rc, i32 sta
 	u32 carry = 4;	// base before the current chunk (4 = none)
 	for (i32 t0 = 0; t0 < len; t0 += 64)
 	{
-		const i32 t = t0 + lane;
-		const bool valid = t < len;
-		const u32 b = valid ? base_at(w, L, rc, start + t) : 0u;
-		u32 prev = __shfl_up(b, 1);
-		if (lane == 0) prev = carry;
-		const bool keep = valid && (!hpc || prev != b);
-		const u64 m = __builtin_amdgcn_ballot_w64(keep);
+		u32 b;
+		bool keep;
+		const u64 m = fg_range_step(w, L, rc, start, len, hpc, t0, carry, b, keep);
 		const int cnt = __popcll(m);
 		const int rank = __builtin_amdgcn_mbcnt_hi((u32)(m >> 32), __builtin_amdgcn_mbcnt_lo((u32)m, 0));
 		// kept lanes push their base to lane `rank`; the others to lane 63 + (never read: cnt <= 64
@@ -100,7 +88,6 @@ __device__ int extract_planes(const u64* __restrict__ w, i32 L, bool rc, i32 sta
 			else fill += cnt;
 		}
 		outLen += cnt;
-		carry = __shfl(b, 63);
 	}
 	if (lane == 0)
 	{

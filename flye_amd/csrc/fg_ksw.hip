@@ -699,18 +699,159 @@ bool bandFeasible(int qlen, int tlen, int w)
 	return st <= en;
 }
 
+// ---- strings cut out of the resident reads (fg_align_ranges) ---------------------------------------------------------
+// the two containers a side can name
+struct RangeSeqs {
+	const u64* qWords; const u64* qWordOff; const i32* qLen;
+	const u64* words; const u64* wordOff; const i32* len;
+};
+
+// compressed length of every (pair, side): one wave per side, 64 bases per step, the kept bases counted from the ballot
+__global__ void __launch_bounds__(64)
+k_range_lengths(const FgRangeSide* __restrict__ sides, u32 nSides, RangeSeqs S, i32* __restrict__ outLen)
+{
+	for (u32 i = blockIdx.x; i < nSides; i += gridDim.x)
+	{
+		const FgRangeSide R = sides[i];
+		const bool q = R.flags & 2u;
+		const u64* w = (q ? S.qWords : S.words) + (q ? S.qWordOff : S.wordOff)[R.rec];
+		const i32 L = (q ? S.qLen : S.len)[R.rec];
+		u32 carry = 4;
+		int n = 0;
+		for (i32 t0 = 0; t0 < R.len; t0 += 64)
+		{
+			u32 b; bool keep;
+			n += __popcll(fg_range_step(w, L, R.flags & 1u, R.start, R.len, true, t0, carry, b, keep));
+		}
+		if (threadIdx.x == 0) outLen[i] = n;
+	}
+}
+
+// the byte strings (0..3) of every (pair, side) at dstOff[side] of the targets' (even sides) or queries' (odd sides)
+// buffer: the kept bases of a step go to consecutive bytes by their rank in the ballot.  dstLen[side] = the length the
+// buffer has room for (what k_range_lengths counted, or the range itself).
+__global__ void __launch_bounds__(64)
+k_range_extract(const FgRangeSide* __restrict__ sides, u32 nSides, RangeSeqs S, int hpc, const u64* __restrict__ dstOff,
+				const i32* __restrict__ dstLen, uint8_t* __restrict__ trgAll, uint8_t* __restrict__ qryAll)
+{
+	for (u32 i = blockIdx.x; i < nSides; i += gridDim.x)
+	{
+		const FgRangeSide R = sides[i];
+		const bool q = R.flags & 2u;
+		const u64* w = (q ? S.qWords : S.words) + (q ? S.qWordOff : S.wordOff)[R.rec];
+		const i32 L = (q ? S.qLen : S.len)[R.rec];
+		uint8_t* dst = ((i & 1u) ? qryAll : trgAll) + dstOff[i];
+		const i32 room = dstLen[i];
+		u32 carry = 4;
+		i32 at = 0;
+		for (i32 t0 = 0; t0 < R.len; t0 += 64)
+		{
+			u32 b; bool keep;
+			const u64 m = fg_range_step(w, L, R.flags & 1u, R.start, R.len, hpc, t0, carry, b, keep);
+			const i32 rank = (i32)__builtin_amdgcn_mbcnt_hi((u32)(m >> 32), __builtin_amdgcn_mbcnt_lo((u32)m, 0));
+			if (keep && at + rank < room) dst[at + rank] = (uint8_t)b;
+			at += __popcll(m);
+		}
+	}
+}
+
+// ---- M runs -> '=' / 'X' runs on the device (the loop of alignment.cpp:172-211) ----------------------------------------
+// One wave per pair walks the pair's ksw runs; an M run is compared 64 columns per step, the ballot of "equal" against
+// itself shifted by one column (the last column of the step before carried in) marks where an output run starts; the
+// first column of every ksw run starts one (alignment.cpp:184).  WRITE = false: cnt[2 jb] = output runs, cnt[2 jb + 1]
+// = mismatches + indel bases.  WRITE = true: the runs at outOff[jb] .. outOff[jb + 1].  A run that is still open at
+// the end of a step is closed by lane 0 once its end is known.
+template <bool WRITE>
+__global__ void __launch_bounds__(64)
+k_ksw_decode(const KswJob* __restrict__ jobs, u32 nJobs, const uint8_t* __restrict__ trgAll, const uint8_t* __restrict__ qryAll,
+			 const u32* __restrict__ nCigar, const u32* __restrict__ runBase, const u32* __restrict__ dense,
+			 u32* __restrict__ cnt, const u64* __restrict__ outOff, uint8_t* __restrict__ ops, i32* __restrict__ lens)
+{
+	const int lane = threadIdx.x;
+	for (u32 jb = blockIdx.x; jb < nJobs; jb += gridDim.x)
+	{
+		const KswJob J = jobs[jb];
+		const uint8_t* t = trgAll + J.trgOff;
+		const uint8_t* q = qryAll + J.qryOff;
+		const u32 n = fg_uni(nCigar[jb]);
+		const u32* runs = dense + fg_uni(runBase[jb]);
+		u64 o = 0, oEnd = 0;		// next output run, end of this pair's runs
+		if (WRITE) { o = fg_uni(outOff[jb]); oEnd = fg_uni(outOff[jb + 1]); }
+		u32 nOut = 0, err = 0;
+		i32 posT = 0, posQ = 0;
+		for (u32 k = 0; k < n; ++k)
+		{
+			const u32 run = fg_uni(runs[k]);
+			const i32 size = (i32)(run >> 4);
+			const u32 op = run & 0xf;
+			if (op != 0)
+			{
+				if (WRITE && lane == 0 && o < oEnd) { ops[o] = op == 1 ? 'I' : 'D'; lens[o] = size; }
+				++o; ++nOut; err += (u32)size;
+				if (op == 1) posQ += size; else posT += size;
+				continue;
+			}
+			u64 openAt = 0;		// the output run that is open, and the column it started at
+			i32 openX = 0;
+			u32 lastEq = 0;
+			for (i32 x0 = 0; x0 < size; x0 += 64)
+			{
+				const i32 x = x0 + lane;
+				// (a CIGAR consumes both strings exactly: the two length tests only keep a read inside the buffers)
+				const bool valid = x < size && posT + x < J.tlen && posQ + x < J.qlen;
+				const bool eq = valid && t[posT + x] == q[posQ + x];
+				const u64 vm = __builtin_amdgcn_ballot_w64(valid), em = __builtin_amdgcn_ballot_w64(eq);
+				// a column starts a run when it differs from the one before it; column 0 always does
+				u64 st = (em ^ (em << 1 | lastEq)) & vm;
+				if (x0 == 0) st |= vm & 1ULL;
+				lastEq = (u32)(em >> 63);
+				err += (u32)__popcll(vm & ~em);
+				const int ns = __popcll(st);
+				if (WRITE && ns)
+				{
+					// the open run ends where the first new one starts
+					const int first = __builtin_ctzll(st);
+					if (x0 && lane == 0 && openAt < oEnd) lens[openAt] = x0 + first - openX;
+					const bool mine = (st >> lane) & 1ULL;
+					const u64 above = lane == 63 ? 0ULL : st & ~((2ULL << lane) - 1ULL);
+					const u64 idx = o + (u64)__popcll(st & ((1ULL << lane) - 1ULL));
+					if (mine && idx < oEnd)
+					{
+						ops[idx] = eq ? '=' : 'X';
+						if (above) lens[idx] = __builtin_ctzll(above) - lane;
+					}
+					const int last = 63 - __builtin_clzll(st);
+					openAt = o + (u64)ns - 1; openX = x0 + last;
+				}
+				o += (u64)ns; nOut += (u32)ns;
+			}
+			if (WRITE && size > 0 && lane == 0 && openAt < oEnd) lens[openAt] = size - openX;
+			posT += size; posQ += size;
+		}
+		if (!WRITE && lane == 0) { cnt[2 * jb] = nOut; cnt[2 * jb + 1] = err; }
+	}
+}
+
 } // namespace
 
-// ksw-form CIGARs (len << 4 | op, op 0 = M, 1 = I, 2 = D, first run first) of nPairs (target, query) byte-string
-// pairs; run counts in nRuns, runs of pair i at runs[runOff[i] ..)
-void fgKswAlign(fg_ctx* c, u32 nPairs, const uint8_t* trg, const u64* trgOff, const uint8_t* qry, const u64* qryOff,
-				std::vector<u64>& runOff, std::vector<u32>& runs)
+namespace {
+
+// what the kernels of one sub-batch left on the device: pairs [first, first + count) of the call; ksw-form runs (len << 4
+// | op, op 0 = M, 1 = I, 2 = D, first run first) of pair first + i = dDense[dBase[i] .. + dN[i]), *dTotal runs in all
+struct KswSubBatch {
+	u32 first, count;
+	const KswJob* dJobs;
+	const u32* dN; const u32* dBase; const u32* dDense; const u32* dTotal;
+};
+
+// Aligns nPairs (target, query) byte-string pairs that are on the device (pair i at dTrg + trgOff[i], dQry + qryOff[i];
+// the offsets are host arrays): job setup, sub-batches bounded by scratch memory, one kernel per band class.  sink
+// takes each sub-batch's runs off the device before the next one reuses the buffers.
+template <class Sink>
+void kswAlignDevice(fg_ctx* c, u32 nPairs, const uint8_t* dTrgP, const u64* trgOff, const uint8_t* dQryP, const u64* qryOff,
+					Sink&& sink)
 {
 	hipStream_t s = c->stream;
-	runOff.assign(nPairs + 1, 0);
-	runs.clear();
-	if (!nPairs) return;
-	c->timer.reset();
 	const bool trace = getenv("FG_KSW_TRACE") != nullptr;
 	auto now = [] { return std::chrono::steady_clock::now(); };
 	auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
@@ -739,21 +880,13 @@ void fgKswAlign(fg_ctx* c, u32 nPairs, const uint8_t* trg, const u64* trgOff, co
 		J.w = w; J.feasible = ok ? 1 : 0;
 		cigCap[i] = ok ? (u64)J.tlen + J.qlen + 2 : 0;
 	}
-	const u64 nTrg = trgOff[nPairs], nQry = qryOff[nPairs];
-	DevBuf<uint8_t> dTrg, dQry;
-	dTrg.alloc(nTrg + 64); dQry.alloc(nQry + 64);
-	if (nTrg) HIP_CHECK(hipMemcpyAsync(dTrg.p, trg, nTrg, hipMemcpyHostToDevice, s));
-	if (nQry) HIP_CHECK(hipMemcpyAsync(dQry.p, qry, nQry, hipMemcpyHostToDevice, s));
 	// sub-batches bounded by scratch memory (state buffer + backtrack matrix per alignment)
 	const u64 budget = getenv("FG_KSW_SCRATCH_BYTES") ? strtoull(getenv("FG_KSW_SCRATCH_BYTES"), nullptr, 10) : (8ULL << 30);
-	std::vector<u32> nRunsAll(nPairs, 0);
-	std::vector<std::vector<u32>> parts;
 	u32 a = 0;
 	DevBuf<uint8_t> dScratch;
 	DevBuf<KswJob> dJobs;
 	DevBuf<u32> dCig, dN, dOrder, dDense, dBase, dTotal;
 	dTotal.alloc(1);
-	std::vector<u64> partOff(nPairs, 0);
 	while (a < nPairs)
 	{
 		u32 b = a;
@@ -809,7 +942,7 @@ void fgKswAlign(fg_ctx* c, u32 nPairs, const uint8_t* trg, const u64* trgOff, co
 				ScopedK t(c->timer, cls == 0 ? "k_ksw_extz2" : "k_ksw_extz2_lds");
 				const unsigned g = std::min<unsigned>(cnt, 8192u);
 				const u32* ord = dOrder.p + at;
-#define KSW_ARGS dJobs.p, ord, cnt, dTrg.p, dQry.p, dScratch.p, dCig.p, dN.p, dDense.p, dTotal.p, dBase.p
+#define KSW_ARGS dJobs.p, ord, cnt, dTrgP, dQryP, dScratch.p, dCig.p, dN.p, dDense.p, dTotal.p, dBase.p
 				const u32 dbg = getenv("FG_KSW_DEBUG") ? (u32)atoi(getenv("FG_KSW_DEBUG")) : 0u;
 				// state in registers (FG_KSW_REG=0: in LDS rings, the round-2 form)
 				const bool regForm = !(getenv("FG_KSW_REG") && atoi(getenv("FG_KSW_REG")) == 0);
@@ -826,24 +959,138 @@ void fgKswAlign(fg_ctx* c, u32 nPairs, const uint8_t* trg, const u64* trgOff, co
 				at += cnt;
 			}
 		}
-		std::vector<u32> hN(sub.size()), hBase(sub.size());
 		u32 total = 0;
-		HIP_CHECK(hipMemcpyAsync(hN.data(), dN.p, sub.size() * 4, hipMemcpyDeviceToHost, s));
-		HIP_CHECK(hipMemcpyAsync(hBase.data(), dBase.p, sub.size() * 4, hipMemcpyDeviceToHost, s));
-		HIP_CHECK(hipMemcpyAsync(&total, dTotal.p, 4, hipMemcpyDeviceToHost, s));
-		HIP_CHECK(hipStreamSynchronize(s));
-		std::vector<u32> hRuns(total + 1);
-		if (total) HIP_CHECK(hipMemcpy(hRuns.data(), dDense.p, (size_t)total * 4, hipMemcpyDeviceToHost));
+		sink(KswSubBatch{a, (u32)sub.size(), dJobs.p, dN.p, dBase.p, dDense.p, dTotal.p}, total);
 		auto t2 = now();
 		if (trace) fprintf(stderr, "[ksw] sub-batch of %zu: setup %.1f ms, alloc+kernels+D2H %.1f ms (scratch %.2f GB, %u runs)\n",
 						   sub.size(), ms(t0, t1), ms(t1, t2), (memTotal + pTotal) / 1e9, total);
-		for (u32 i = 0; i < sub.size(); ++i)
-		{
-			runOff[a + i + 1] = runOff[a + i] + hN[i];
-			runs.insert(runs.end(), hRuns.begin() + hBase[i], hRuns.begin() + hBase[i] + hN[i]);
-		}
 		a = b;
 	}
-	c->timer.collect();
 	if (trace) fprintf(stderr, "[ksw] total %.1f ms\n", ms(t0, now()));
+}
+
+} // namespace
+
+// ksw-form CIGARs (len << 4 | op, op 0 = M, 1 = I, 2 = D, first run first) of nPairs (target, query) byte-string
+// pairs of the host; run counts in nRuns, runs of pair i at runs[runOff[i] ..): the strings go up, kswAlignDevice
+// aligns them, the runs come back as they are
+void fgKswAlign(fg_ctx* c, u32 nPairs, const uint8_t* trg, const u64* trgOff, const uint8_t* qry, const u64* qryOff,
+				std::vector<u64>& runOff, std::vector<u32>& runs)
+{
+	hipStream_t s = c->stream;
+	runOff.assign(nPairs + 1, 0);
+	runs.clear();
+	if (!nPairs) return;
+	c->timer.reset();
+	const u64 nTrg = trgOff[nPairs], nQry = qryOff[nPairs];
+	DevBuf<uint8_t> dTrg, dQry;
+	dTrg.alloc(nTrg + 64); dQry.alloc(nQry + 64);
+	if (nTrg) HIP_CHECK(hipMemcpyAsync(dTrg.p, trg, nTrg, hipMemcpyHostToDevice, s));
+	if (nQry) HIP_CHECK(hipMemcpyAsync(dQry.p, qry, nQry, hipMemcpyHostToDevice, s));
+	kswAlignDevice(c, nPairs, dTrg.p, trgOff, dQry.p, qryOff, [&](const KswSubBatch& B, u32& total)
+	{
+		std::vector<u32> hN(B.count), hBase(B.count);
+		HIP_CHECK(hipMemcpyAsync(hN.data(), B.dN, B.count * 4, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(hipMemcpyAsync(hBase.data(), B.dBase, B.count * 4, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(hipMemcpyAsync(&total, B.dTotal, 4, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(hipStreamSynchronize(s));
+		std::vector<u32> hRuns(total + 1);
+		if (total) HIP_CHECK(hipMemcpy(hRuns.data(), B.dDense, (size_t)total * 4, hipMemcpyDeviceToHost));
+		for (u32 i = 0; i < B.count; ++i)
+		{
+			runOff[B.first + i + 1] = runOff[B.first + i] + hN[i];
+			runs.insert(runs.end(), hRuns.begin() + hBase[i], hRuns.begin() + hBase[i] + hN[i]);
+		}
+	});
+	c->timer.collect();
+}
+
+// fg_align_ranges: the strings are cut out of the resident 2-bit reads into the buffers the ksw kernels read, and the M
+// runs are decoded on the device -- only the side table and the lengths go up, only runs and counts come back
+void fgAlignRanges(fg_ctx* c, const std::vector<FgRangeSide>& sides, bool useHpc, std::vector<u64>& runOff,
+				   std::vector<uint8_t>& ops, std::vector<i32>& lens, std::vector<u32>& errBases, std::vector<i32>& lenCur,
+				   std::vector<i32>& lenExt)
+{
+	hipStream_t s = c->stream;
+	const u32 nSides = (u32)sides.size(), nPairs = nSides / 2;
+	runOff.assign(nPairs + 1, 0);
+	ops.clear(); lens.clear();
+	errBases.assign(nPairs, 0); lenCur.assign(nPairs, 0); lenExt.assign(nPairs, 0);
+	if (!nPairs) return;
+	c->timer.reset();
+	const RangeSeqs S{c->dQWords.p, c->dQWordOff.p, c->dQLen.p, c->dWords.p, c->dWordOff.p, c->dLen.p};
+	c->dRangeSides.reserve((size_t)nSides * sizeof(FgRangeSide));
+	c->dRangeLen.reserve(nSides); c->dRangeOff.reserve(nSides);
+	FgRangeSide* dSides = (FgRangeSide*)c->dRangeSides.p;
+	HIP_CHECK(hipMemcpyAsync(dSides, sides.data(), (size_t)nSides * sizeof(FgRangeSide), hipMemcpyHostToDevice, s));
+	const unsigned g = std::min<unsigned>(nSides, 8192u);
+	std::vector<i32> hLen(nSides);
+	if (useHpc)
+	{
+		{
+			ScopedK t(c->timer, "k_range_lengths");
+			hipLaunchKernelGGL(k_range_lengths, g, 64, 0, s, dSides, nSides, S, c->dRangeLen.p);
+		}
+		HIP_CHECK(hipMemcpyAsync(hLen.data(), c->dRangeLen.p, (size_t)nSides * 4, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(hipStreamSynchronize(s));
+	}
+	else
+	{
+		for (u32 i = 0; i < nSides; ++i) hLen[i] = sides[i].len;
+		HIP_CHECK(hipMemcpyAsync(c->dRangeLen.p, hLen.data(), (size_t)nSides * 4, hipMemcpyHostToDevice, s));
+	}
+	// where each string starts: targets (even sides) and queries (odd sides) in buffers of their own
+	std::vector<u64> trgOff(nPairs + 1, 0), qryOff(nPairs + 1, 0), sideOff(nSides);
+	for (u32 i = 0; i < nPairs; ++i)
+	{
+		lenCur[i] = hLen[2 * i]; lenExt[i] = hLen[2 * i + 1];
+		sideOff[2 * i] = trgOff[i]; sideOff[2 * i + 1] = qryOff[i];
+		trgOff[i + 1] = trgOff[i] + (u64)hLen[2 * i]; qryOff[i + 1] = qryOff[i] + (u64)hLen[2 * i + 1];
+	}
+	c->dRangeTrg.reserve(trgOff[nPairs] + 64); c->dRangeQry.reserve(qryOff[nPairs] + 64);
+	HIP_CHECK(hipMemcpyAsync(c->dRangeOff.p, sideOff.data(), (size_t)nSides * 8, hipMemcpyHostToDevice, s));
+	{
+		ScopedK t(c->timer, "k_range_extract");
+		hipLaunchKernelGGL(k_range_extract, g, 64, 0, s, dSides, nSides, S, useHpc ? 1 : 0, c->dRangeOff.p, c->dRangeLen.p,
+						   c->dRangeTrg.p, c->dRangeQry.p);
+	}
+	HIP_CHECK(hipStreamSynchronize(s));		// sideOff, hLen go out of use
+	const uint8_t* dTrg = c->dRangeTrg.p;
+	const uint8_t* dQry = c->dRangeQry.p;
+	kswAlignDevice(c, nPairs, dTrg, trgOff.data(), dQry, qryOff.data(), [&](const KswSubBatch& B, u32& total)
+	{
+		const unsigned gd = std::min<unsigned>(B.count, 8192u);
+		c->dDecCnt.reserve(2 * (size_t)B.count); c->dDecOff.reserve((size_t)B.count + 1);
+		{
+			ScopedK t(c->timer, "k_ksw_decode");
+			hipLaunchKernelGGL(k_ksw_decode<false>, gd, 64, 0, s, B.dJobs, B.count, dTrg, dQry, B.dN, B.dBase, B.dDense,
+							   c->dDecCnt.p, (const u64*)nullptr, (uint8_t*)nullptr, (i32*)nullptr);
+		}
+		std::vector<u32> hCnt(2 * (size_t)B.count);
+		HIP_CHECK(hipMemcpyAsync(hCnt.data(), c->dDecCnt.p, hCnt.size() * 4, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(hipMemcpyAsync(&total, B.dTotal, 4, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(hipStreamSynchronize(s));
+		std::vector<u64> off(B.count + 1, 0);
+		for (u32 i = 0; i < B.count; ++i)
+		{
+			off[i + 1] = off[i] + hCnt[2 * i];
+			errBases[B.first + i] = hCnt[2 * i + 1];
+			runOff[B.first + i + 1] = runOff[B.first + i] + hCnt[2 * i];
+		}
+		const u64 nOut = off[B.count];
+		if (!nOut) return;
+		c->dDecOps.reserve(nOut); c->dDecLens.reserve(nOut);
+		HIP_CHECK(hipMemcpyAsync(c->dDecOff.p, off.data(), off.size() * 8, hipMemcpyHostToDevice, s));
+		{
+			ScopedK t(c->timer, "k_ksw_decode");
+			hipLaunchKernelGGL(k_ksw_decode<true>, gd, 64, 0, s, B.dJobs, B.count, dTrg, dQry, B.dN, B.dBase, B.dDense,
+							   (u32*)nullptr, c->dDecOff.p, c->dDecOps.p, c->dDecLens.p);
+		}
+		const size_t at = ops.size();
+		ops.resize(at + nOut); lens.resize(at + nOut);
+		HIP_CHECK(hipMemcpyAsync(ops.data() + at, c->dDecOps.p, nOut, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(hipMemcpyAsync(lens.data() + at, c->dDecLens.p, nOut * 4, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(hipStreamSynchronize(s));
+	});
+	c->timer.collect();
 }

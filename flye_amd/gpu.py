@@ -43,6 +43,7 @@ ABI_SYMBOLS = ["fg_abi_version", "fg_create", "fg_destroy", "fg_strerror", "fg_l
                "fg_index_selection_done", "fg_index_gather_begin", "fg_index_gather_end", "fg_memory_stats",
                "fg_import_index", "fg_index_device_arrays", "fg_clear_index", "fg_export_index", "fg_overlaps", "fg_release_batch",
                "fg_kernel_times", "fg_debug_sort_pairs", "fg_debug_edit_distances", "fg_align_cigar_ksw", "fg_release_cigars",
+               "fg_align_ranges",
                "fg_index_keep_targets", "fg_index_shard", "fg_probe_hits", "fg_overlaps_from_hits",
                "fg_index_piece_split", "fg_index_scatter_begin", "fg_index_scatter_end", "fg_debug_probe_skip_check",
                "fg_group_create", "fg_group_destroy", "fg_group_size", "fg_group_member", "fg_group_last_error",
@@ -50,6 +51,10 @@ ABI_SYMBOLS = ["fg_abi_version", "fg_create", "fg_destroy", "fg_strerror", "fg_l
                "fg_group_build_index_minimizers", "fg_group_clear_index", "fg_group_overlaps", "fg_group_stats",
                "fg_group_build_info", "fg_debug_freq_accumulate", "fg_debug_group_bin_cuts", "fg_debug_scan",
                "fg_debug_radix_sort_pairs"]
+
+# struct fg_range_pair: one pair of fg_align_ranges
+RANGE_PAIR_DTYPE = np.dtype([("cur_id", "<u4"), ("ext_id", "<u4"), ("cur_begin", "<i4"), ("cur_end", "<i4"),
+                             ("ext_begin", "<i4"), ("ext_end", "<i4")])
 
 # struct fg_seed_hit: KmerMatch{curPos, extPos, extId} (overlap.cpp:176-196)
 SEED_HIT_DTYPE = np.dtype([("cur_pos", "<i4"), ("ext_pos", "<i4"), ("ext_id", "<u4")])
@@ -184,6 +189,8 @@ def load_library():
         L.fg_align_cigar_ksw.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.POINTER(CigarBatch)]
         L.fg_release_cigars.argtypes = [C.POINTER(CigarBatch)]
+        L.fg_align_ranges.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint8, C.POINTER(CigarBatch), C.c_void_p,
+                                      C.c_void_p]
         L.fg_debug_group_bin_cuts.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         L.fg_debug_freq_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
         L.fg_debug_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int]
@@ -421,9 +428,10 @@ class Context:
                                                    la.ctypes.data, lb.ctypes.data))
         return d, la, lb
 
-    def align_cigar_ksw(self, pairs):
+    def align_cigar_ksw(self, pairs, arrays=False):
         """getAlignmentCigarKsw (alignment.cpp:102-216) of (target, query) pairs of 0..3 arrays on the device:
-        list of (error-rate bit pattern as hex, CIGAR text "<len><op> ...")."""
+        list of (error-rate bit pattern as hex, CIGAR text "<len><op> ..."); arrays = True: the batch's arrays instead
+        (run offsets, ops, lens, error-rate bit patterns)."""
         n = len(pairs)
         trg = np.concatenate([np.asarray(a, np.uint8) for a, _ in pairs]) if n else np.empty(0, np.uint8)
         qry = np.concatenate([np.asarray(b, np.uint8) for _, b in pairs]) if n else np.empty(0, np.uint8)
@@ -438,13 +446,55 @@ class Context:
         self._check(self.L.fg_align_cigar_ksw(self.h, n, trg.ctypes.data, toff.ctypes.data, qry.ctypes.data,
                                               qoff.ctypes.data, C.byref(b)))
         self.last_align_seconds = time.perf_counter() - t0      # the C call alone (the text below is test harness)
-        out = []
-        for i in range(n):
-            a0, a1 = int(b.run_off[i]), int(b.run_off[i + 1])
-            bits = int(np.array([b.err_rate[i]], np.float32).view(np.uint32)[0])
-            out.append((f"{bits:08x}", " ".join(f"{b.lens[k]}{chr(b.ops[k])}" for k in range(a0, a1))))
+        out = self._cigar_result(b, n, arrays)
         self.L.fg_release_cigars(C.byref(b))
         return out
+
+    @staticmethod
+    def _cigar_result(b, n, arrays):
+        """Copies of a fg_cigar_batch: (run_off, ops, lens, error-rate bit patterns) as arrays, or the list of
+        (error-rate bit pattern as hex, CIGAR text) per pair."""
+        run_off = np.ctypeslib.as_array(b.run_off, (n + 1,)).copy() if n else np.zeros(1, np.uint64)
+        total = int(run_off[n])
+        ops = np.ctypeslib.as_array(b.ops, (total,)).copy() if total else np.empty(0, np.uint8)
+        lens = np.ctypeslib.as_array(b.lens, (total,)).copy() if total else np.empty(0, np.int32)
+        bits = np.ctypeslib.as_array(b.err_rate, (n,)).copy().view(np.uint32) if n else np.empty(0, np.uint32)
+        if arrays:
+            return run_off, ops, lens, bits
+        out = []
+        for i in range(n):
+            a0, a1 = int(run_off[i]), int(run_off[i + 1])
+            out.append((f"{int(bits[i]):08x}", " ".join(f"{lens[k]}{chr(ops[k])}" for k in range(a0, a1))))
+        return out
+
+    def align_ranges(self, pairs, use_hpc=False, arrays=False):
+        """fg_align_ranges: getAlignmentCigarKsw of ranges of the resident sequences, cut out (and, with use_hpc,
+        homopolymer-compressed) on the device.  pairs: (n, 6) integers (cur_id, ext_id, cur_begin, cur_end, ext_begin,
+        ext_end) or a record array with those fields (the records of an OverlapResult).  Returns (what align_cigar_ksw
+        returns for those strings, aligned lengths of the cur side, of the ext side)."""
+        pairs = np.asarray(pairs)
+        tab = np.zeros(len(pairs), RANGE_PAIR_DTYPE)
+        if pairs.dtype.names:
+            for f in RANGE_PAIR_DTYPE.names:
+                tab[f] = pairs[f]
+        elif len(pairs):
+            if pairs.ndim != 2 or pairs.shape[1] != 6 or pairs.dtype.kind not in "iu":
+                raise ValueError("pairs: an (n, 6) integer array or a record array")
+            if (pairs[:, :2] < 0).any() or (pairs[:, :2] > 0xFFFFFFFF).any() or (abs(pairs[:, 2:]) > 0x7FFFFFFF).any():
+                raise ValueError("pairs: ids are uint32, positions int32")
+            for j, f in enumerate(RANGE_PAIR_DTYPE.names):
+                tab[f] = pairs[:, j]
+        n = len(tab)
+        len_cur = np.zeros(n, np.int32)
+        len_ext = np.zeros(n, np.int32)
+        b = CigarBatch()
+        t0 = time.perf_counter()
+        self._check(self.L.fg_align_ranges(self.h, tab.ctypes.data if n else None, n, int(bool(use_hpc)), C.byref(b),
+                                           len_cur.ctypes.data if n else None, len_ext.ctypes.data if n else None))
+        self.last_align_seconds = time.perf_counter() - t0
+        out = self._cigar_result(b, n, arrays)
+        self.L.fg_release_cigars(C.byref(b))
+        return out, len_cur, len_ext
 
     def kernel_times(self):
         arr = (KernelTime * 64)()

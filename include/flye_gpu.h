@@ -492,6 +492,21 @@ int fg_align_cigar_ksw(fg_ctx* ctx, uint32_t n_pairs, const uint8_t* trg, const 
                        const uint8_t* qry, const uint64_t* qry_off, struct fg_cigar_batch* out);
 void fg_release_cigars(struct fg_cigar_batch* b);
 
+/* The same alignment for ranges of the sequences that are resident on the device: the first half of checkIdyAndTrim
+ * (alignment.cpp:306-495) for the records fg_overlaps marks in needs_trim.  Pair i: target = [cur_begin, cur_end) of
+ * sequence cur_id, query = [ext_begin, ext_end) of sequence ext_id (the roles of alignment.cpp:319-321).  Ids are
+ * FastaRecord ids (odd = reverse-complement strand); cur_id names a sequence of the fg_set_queries container when one
+ * is set, otherwise of the indexed container; ext_id always one of the indexed container.  use_hpc != 0: both strings
+ * go through homopolymerCompression (alignment.cpp:52-70) first.  out (released with fg_release_cigars) equals, field
+ * for field, what fg_align_cigar_ksw returns for those byte strings; len_cur / len_ext (may be NULL) receive the
+ * aligned (compressed) lengths.  The strings are cut out of the 2-bit reads, aligned and decoded on the device: no
+ * string crosses the bus.  Empty ranges are legal and behave as empty strings do.  FG_ERR_STATE without reads;
+ * FG_ERR_ARG for an unknown id, begin < 0, end < begin, end > length, or NULL pairs / out with n_pairs > 0 -- found
+ * before any device work.  The interval search of checkIdyAndTrim stays with the caller. */
+struct fg_range_pair { uint32_t cur_id, ext_id; int32_t cur_begin, cur_end, ext_begin, ext_end; };
+int fg_align_ranges(fg_ctx* ctx, const struct fg_range_pair* pairs, uint32_t n_pairs, uint8_t use_hpc,
+                    struct fg_cigar_batch* out, int32_t* len_cur, int32_t* len_ext);
+
 #ifdef __cplusplus
 }
 #endif
