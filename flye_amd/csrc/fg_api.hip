@@ -729,6 +729,42 @@ int fg_align_cigar_ksw(fg_ctx* c, uint32_t n_pairs, const uint8_t* trg, const ui
 	return FG_OK;
 }
 
+namespace {
+// the argument checks fg_align_ranges and fg_trim_ranges share (before any device work) and the (pair, side) table
+std::vector<FgRangeSide> rangeSides(fg_ctx* c, const char* fn, const struct fg_range_pair* pairs, uint32_t n_pairs, const void* out)
+{
+	const std::string name = fn;
+	if (n_pairs && (!pairs || !out)) throw FgError{FG_ERR_ARG, name + ": pairs and out must not be NULL"};
+	if (!c->nReads) throw FgError{FG_ERR_STATE, name + ": no reads (fg_set_reads first)"};
+	std::vector<FgRangeSide> sides(2 * (size_t)n_pairs);
+	for (u32 i = 0; i < n_pairs; ++i)
+	{
+		const fg_range_pair& P = pairs[i];
+		auto side = [&](const char* what, u32 id, i32 begin, i32 end, bool mayBeQuery)
+		{
+			const bool inQ = mayBeQuery && c->hasQ;
+			const u32 first = inQ ? c->qFirstId : c->firstId, n = inQ ? c->nQReads : c->nReads;
+			if (id < first || (u64)id - first >= 2ULL * n)
+				throw FgError{FG_ERR_ARG, name + ": pair " + std::to_string(i) + ": unknown " + what + " id " + std::to_string(id)};
+			const u32 rec = (id - first) >> 1;
+			const i32 L = inQ ? c->hQLen[rec] : c->hLen[rec];
+			if (begin < 0 || end < begin || end > L)
+				throw FgError{FG_ERR_ARG, name + ": pair " + std::to_string(i) + ": " + what + " range [" + std::to_string(begin) +
+										  ", " + std::to_string(end) + ") is not inside the sequence of length " + std::to_string(L)};
+			return FgRangeSide{rec, ((id - first) & 1u) | (inQ ? 2u : 0u), begin, end - begin};
+		};
+		sides[2 * (size_t)i] = side("cur", P.cur_id, P.cur_begin, P.cur_end, true);
+		sides[2 * (size_t)i + 1] = side("ext", P.ext_id, P.ext_begin, P.ext_end, false);
+	}
+	return sides;
+}
+
+struct TrimOwner {
+	std::vector<uint64_t> recOff;
+	std::vector<fg_trim_rec> recs;
+};
+}
+
 int fg_align_ranges(fg_ctx* c, const struct fg_range_pair* pairs, uint32_t n_pairs, uint8_t use_hpc,
 					struct fg_cigar_batch* out, int32_t* len_cur, int32_t* len_ext)
 {
@@ -737,29 +773,7 @@ int fg_align_ranges(fg_ctx* c, const struct fg_range_pair* pairs, uint32_t n_pai
 	CigarOwner* own = nullptr;
 	const int rc = guarded(c, [&]()
 	{
-		// the argument checks come before any device work
-		if (n_pairs && (!pairs || !out)) throw FgError{FG_ERR_ARG, "fg_align_ranges: pairs and out must not be NULL"};
-		if (!c->nReads) throw FgError{FG_ERR_STATE, "fg_align_ranges: no reads (fg_set_reads first)"};
-		std::vector<FgRangeSide> sides(2 * (size_t)n_pairs);
-		for (u32 i = 0; i < n_pairs; ++i)
-		{
-			const fg_range_pair& P = pairs[i];
-			auto side = [&](const char* what, u32 id, i32 begin, i32 end, bool mayBeQuery)
-			{
-				const bool inQ = mayBeQuery && c->hasQ;
-				const u32 first = inQ ? c->qFirstId : c->firstId, n = inQ ? c->nQReads : c->nReads;
-				if (id < first || (u64)id - first >= 2ULL * n)
-					throw FgError{FG_ERR_ARG, "fg_align_ranges: pair " + std::to_string(i) + ": unknown " + what + " id " + std::to_string(id)};
-				const u32 rec = (id - first) >> 1;
-				const i32 L = inQ ? c->hQLen[rec] : c->hLen[rec];
-				if (begin < 0 || end < begin || end > L)
-					throw FgError{FG_ERR_ARG, "fg_align_ranges: pair " + std::to_string(i) + ": " + what + " range [" + std::to_string(begin) +
-											  ", " + std::to_string(end) + ") is not inside the sequence of length " + std::to_string(L)};
-				return FgRangeSide{rec, ((id - first) & 1u) | (inQ ? 2u : 0u), begin, end - begin};
-			};
-			sides[2 * (size_t)i] = side("cur", P.cur_id, P.cur_begin, P.cur_end, true);
-			sides[2 * (size_t)i + 1] = side("ext", P.ext_id, P.ext_begin, P.ext_end, false);
-		}
+		const std::vector<FgRangeSide> sides = rangeSides(c, "fg_align_ranges", pairs, n_pairs, out);
 		if (!out) return;		// n_pairs == 0 and nowhere to put the empty batch
 		HIP_CHECK(hipSetDevice(c->device));
 		own = new CigarOwner;
@@ -782,6 +796,39 @@ int fg_align_ranges(fg_ctx* c, const struct fg_range_pair* pairs, uint32_t n_pai
 	out->err_rate = own->err.data();
 	out->owner_ = own;
 	return FG_OK;
+}
+
+int fg_trim_ranges(fg_ctx* c, const struct fg_range_pair* pairs, uint32_t n_pairs, uint8_t use_hpc, float max_divergence,
+				   int32_t min_overlap, struct fg_trim_batch* out)
+{
+	if (!c) return FG_ERR_ARG;
+	if (out) memset(out, 0, sizeof(*out));
+	TrimOwner* own = nullptr;
+	const int rc = guarded(c, [&]()
+	{
+		const std::vector<FgRangeSide> sides = rangeSides(c, "fg_trim_ranges", pairs, n_pairs, out);
+		if (!out) return;
+		HIP_CHECK(hipSetDevice(c->device));
+		own = new TrimOwner;
+		fgTrimRanges(c, sides, use_hpc != 0, max_divergence, min_overlap, own->recOff, own->recs);
+		// the float of alignment.cpp:379, from the two integers
+		for (auto& r : own->recs) r.seq_divergence = float(r.range_err) / r.range_len;
+		if (own->recs.empty()) own->recs.reserve(1);
+	});
+	if (rc != FG_OK) { delete own; return rc; }
+	if (!out) return FG_OK;
+	out->n_pairs = n_pairs;
+	out->rec_off = own->recOff.data();
+	out->recs = own->recs.data();
+	out->owner_ = own;
+	return FG_OK;
+}
+
+void fg_release_trims(struct fg_trim_batch* b)
+{
+	if (!b) return;
+	delete (TrimOwner*)b->owner_;
+	memset(b, 0, sizeof(*b));
 }
 
 void fg_release_cigars(struct fg_cigar_batch* b)

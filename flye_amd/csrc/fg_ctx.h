@@ -408,6 +408,14 @@ struct fg_ctx {
 	DevBuf<u64> dDecOff;
 	DevBuf<uint8_t> dDecOps;
 	DevBuf<i32> dDecLens;
+	// fg_trim_ranges (fg_trim.hip): prefix sums over a sub-batch's runs, candidate counts per (pair, interval length)
+	// and their scan, the good intervals of a trim sub-batch (sort key, rank, (start, end)) with their segment
+	// offsets, the accepted intervals and the records made of them
+	DevBuf<i32> dTrimPre;
+	DevBuf<u64> dTrimRowCnt, dTrimRowOff, dTrimScan, dTrimKeys, dTrimIvl, dTrimSeg, dTrimAcc, dTrimAccOff;
+	DevBuf<unsigned long long> dTrimPairCnt;
+	DevBuf<u32> dTrimVals, dTrimAccCnt, dTrimKept;
+	DevBuf<char> dTrimRaw, dTrimOut;
 	PinnedBuf<char> hPrim;
 	PinnedBuf<u64> hOff;
 	PinnedBuf<u64> hScalar;		// staging of the counts the host reads between kernels (pinned: no bounce buffer)
@@ -704,6 +712,20 @@ struct FgRangeSide { u32 rec; u32 flags; i32 start, len; };		// rec: index in it
 void fgAlignRanges(fg_ctx* c, const std::vector<FgRangeSide>& sides, bool useHpc, std::vector<u64>& runOff,
 				   std::vector<uint8_t>& ops, std::vector<i32>& lens, std::vector<u32>& errBases, std::vector<i32>& lenCur,
 				   std::vector<i32>& lenExt);
+// the device part of fgAlignRanges: after the decoding of each ksw sub-batch (pairs [first, first + count) of the
+// call) `sink` is called while the runs are on the device: run k of pair first + i at c->dDecOps / c->dDecLens
+// [off[i] + k], off (count + 1 entries, also in c->dDecOff) ending at nOut.  The caller resets and collects the timer.
+struct FgDecodedRuns { u32 first, count; const u64* off; u64 nOut; };
+void fgAlignRangesDevice(fg_ctx* c, const std::vector<FgRangeSide>& sides, bool useHpc, std::vector<u64>& runOff,
+						 std::vector<u32>& errBases, std::vector<i32>& lenCur, std::vector<i32>& lenExt,
+						 const std::function<void(const FgDecodedRuns&)>& sink);
+// fg_trim_ranges behind its argument checks (fg_trim.hip): the second half of checkIdyAndTrim on the runs of
+// fgAlignRangesDevice; recs of pair i at recs[recOff[i] ..), seq_divergence left for the caller
+void fgTrimRanges(fg_ctx* c, const std::vector<FgRangeSide>& sides, bool useHpc, float maxDivergence, i32 minOverlap,
+				  std::vector<u64>& recOff, std::vector<fg_trim_rec>& recs);
+// std::sort order (ascending keys, the permutation libstdc++ produces) of each segment [segOff[i], segOff[i + 1]) of
+// the device arrays keys / vals; dSegOff on the device
+void fgSortSegments(fg_ctx* c, const u64* dSegOff, u32 nSeg, u64* dKeys, u32* dVals, u64 n);
 void fgDebugSortPairs(fg_ctx* c, u64* keys, u32* vals, const u64* segOff, u32 nSeg);
 void fgDebugProbeSkipCheck(fg_ctx* c, u64* clearBits, u64* violations);
 void fgDebugEditDistances(fg_ctx* c, u32 nPairs, int useHpc, i32* outDist, i32* outLenA, i32* outLenB);

@@ -1006,18 +1006,17 @@ void fgKswAlign(fg_ctx* c, u32 nPairs, const uint8_t* trg, const u64* trgOff, co
 }
 
 // fg_align_ranges: the strings are cut out of the resident 2-bit reads into the buffers the ksw kernels read, and the M
-// runs are decoded on the device -- only the side table and the lengths go up, only runs and counts come back
-void fgAlignRanges(fg_ctx* c, const std::vector<FgRangeSide>& sides, bool useHpc, std::vector<u64>& runOff,
-				   std::vector<uint8_t>& ops, std::vector<i32>& lens, std::vector<u32>& errBases, std::vector<i32>& lenCur,
-				   std::vector<i32>& lenExt)
+// runs are decoded on the device -- only the side table and the lengths go up, only runs and counts come back (through
+// fgAlignRanges' sink; fg_trim_ranges' sink works on the runs where they are)
+void fgAlignRangesDevice(fg_ctx* c, const std::vector<FgRangeSide>& sides, bool useHpc, std::vector<u64>& runOff,
+						 std::vector<u32>& errBases, std::vector<i32>& lenCur, std::vector<i32>& lenExt,
+						 const std::function<void(const FgDecodedRuns&)>& sink)
 {
 	hipStream_t s = c->stream;
 	const u32 nSides = (u32)sides.size(), nPairs = nSides / 2;
 	runOff.assign(nPairs + 1, 0);
-	ops.clear(); lens.clear();
 	errBases.assign(nPairs, 0); lenCur.assign(nPairs, 0); lenExt.assign(nPairs, 0);
 	if (!nPairs) return;
-	c->timer.reset();
 	const RangeSeqs S{c->dQWords.p, c->dQWordOff.p, c->dQLen.p, c->dWords.p, c->dWordOff.p, c->dLen.p};
 	c->dRangeSides.reserve((size_t)nSides * sizeof(FgRangeSide));
 	c->dRangeLen.reserve(nSides); c->dRangeOff.reserve(nSides);
@@ -1086,11 +1085,24 @@ void fgAlignRanges(fg_ctx* c, const std::vector<FgRangeSide>& sides, bool useHpc
 			hipLaunchKernelGGL(k_ksw_decode<true>, gd, 64, 0, s, B.dJobs, B.count, dTrg, dQry, B.dN, B.dBase, B.dDense,
 							   (u32*)nullptr, c->dDecOff.p, c->dDecOps.p, c->dDecLens.p);
 		}
+		sink(FgDecodedRuns{B.first, B.count, off.data(), nOut});	// (synchronises before off goes out of scope)
+	});
+}
+
+void fgAlignRanges(fg_ctx* c, const std::vector<FgRangeSide>& sides, bool useHpc, std::vector<u64>& runOff,
+				   std::vector<uint8_t>& ops, std::vector<i32>& lens, std::vector<u32>& errBases, std::vector<i32>& lenCur,
+				   std::vector<i32>& lenExt)
+{
+	hipStream_t s = c->stream;
+	ops.clear(); lens.clear();
+	if (!sides.empty()) c->timer.reset();
+	fgAlignRangesDevice(c, sides, useHpc, runOff, errBases, lenCur, lenExt, [&](const FgDecodedRuns& D)
+	{
 		const size_t at = ops.size();
-		ops.resize(at + nOut); lens.resize(at + nOut);
-		HIP_CHECK(hipMemcpyAsync(ops.data() + at, c->dDecOps.p, nOut, hipMemcpyDeviceToHost, s));
-		HIP_CHECK(hipMemcpyAsync(lens.data() + at, c->dDecLens.p, nOut * 4, hipMemcpyDeviceToHost, s));
+		ops.resize(at + D.nOut); lens.resize(at + D.nOut);
+		HIP_CHECK(hipMemcpyAsync(ops.data() + at, c->dDecOps.p, D.nOut, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(hipMemcpyAsync(lens.data() + at, c->dDecLens.p, D.nOut * 4, hipMemcpyDeviceToHost, s));
 		HIP_CHECK(hipStreamSynchronize(s));
 	});
-	c->timer.collect();
+	if (!sides.empty()) c->timer.collect();
 }

@@ -1160,6 +1160,11 @@ void fgDebugProbeSkipCheck(fg_ctx* c, u64* clearBits, u64* violations)
 	*clearBits = h[0]; *violations = h[1];
 }
 
+void fgSortSegments(fg_ctx* c, const u64* dSegOff, u32 nSeg, u64* dKeys, u32* dVals, u64 n)
+{
+	if (nSeg && n) sortSegments<u64>(c, dSegOff, nSeg, dKeys, dVals, n);
+}
+
 void fgDebugSortPairs(fg_ctx* c, u64* keys, u32* vals, const u64* segOff, u32 nSeg)
 {
 	hipStream_t s = c->stream;

@@ -43,7 +43,7 @@ ABI_SYMBOLS = ["fg_abi_version", "fg_create", "fg_destroy", "fg_strerror", "fg_l
                "fg_index_selection_done", "fg_index_gather_begin", "fg_index_gather_end", "fg_memory_stats",
                "fg_import_index", "fg_index_device_arrays", "fg_clear_index", "fg_export_index", "fg_overlaps", "fg_release_batch",
                "fg_kernel_times", "fg_debug_sort_pairs", "fg_debug_edit_distances", "fg_align_cigar_ksw", "fg_release_cigars",
-               "fg_align_ranges",
+               "fg_align_ranges", "fg_trim_ranges", "fg_release_trims",
                "fg_index_keep_targets", "fg_index_shard", "fg_probe_hits", "fg_overlaps_from_hits",
                "fg_index_piece_split", "fg_index_scatter_begin", "fg_index_scatter_end", "fg_debug_probe_skip_check",
                "fg_group_create", "fg_group_destroy", "fg_group_size", "fg_group_member", "fg_group_last_error",
@@ -55,6 +55,11 @@ ABI_SYMBOLS = ["fg_abi_version", "fg_create", "fg_destroy", "fg_strerror", "fg_l
 # struct fg_range_pair: one pair of fg_align_ranges
 RANGE_PAIR_DTYPE = np.dtype([("cur_id", "<u4"), ("ext_id", "<u4"), ("cur_begin", "<i4"), ("cur_end", "<i4"),
                              ("ext_begin", "<i4"), ("ext_end", "<i4")])
+
+# struct fg_trim_rec: one piece checkIdyAndTrim keeps of a pair (fg_trim_ranges)
+TRIM_REC_DTYPE = np.dtype([("cur_begin", "<i4"), ("cur_end", "<i4"), ("ext_begin", "<i4"), ("ext_end", "<i4"),
+                           ("run_start", "<i4"), ("run_end", "<i4"), ("range_err", "<i4"), ("range_len", "<i4"),
+                           ("seq_divergence", "<f4")])
 
 # struct fg_seed_hit: KmerMatch{curPos, extPos, extId} (overlap.cpp:176-196)
 SEED_HIT_DTYPE = np.dtype([("cur_pos", "<i4"), ("ext_pos", "<i4"), ("ext_id", "<u4")])
@@ -97,6 +102,10 @@ class OverlapBatch(C.Structure):
 class CigarBatch(C.Structure):
     _fields_ = [("n_pairs", C.c_uint32), ("run_off", C.POINTER(C.c_uint64)), ("ops", C.POINTER(C.c_uint8)),
                 ("lens", C.POINTER(C.c_int32)), ("err_rate", C.POINTER(C.c_float)), ("owner_", C.c_void_p)]
+
+
+class TrimBatch(C.Structure):
+    _fields_ = [("n_pairs", C.c_uint32), ("rec_off", C.POINTER(C.c_uint64)), ("recs", C.c_void_p), ("owner_", C.c_void_p)]
 
 
 class BridgeStats(C.Structure):
@@ -191,6 +200,9 @@ def load_library():
         L.fg_release_cigars.argtypes = [C.POINTER(CigarBatch)]
         L.fg_align_ranges.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint8, C.POINTER(CigarBatch), C.c_void_p,
                                       C.c_void_p]
+        L.fg_trim_ranges.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint8, C.c_float, C.c_int32, C.POINTER(TrimBatch)]
+        L.fg_release_trims.argtypes = [C.POINTER(TrimBatch)]
+        L.fg_release_trims.restype = None
         L.fg_debug_group_bin_cuts.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         L.fg_debug_freq_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
         L.fg_debug_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int]
@@ -305,6 +317,41 @@ class OverlapResult:
             j = np.arange(len(m), dtype=np.int64) - np.repeat(off[:-1], np.diff(off)) + 1
             cs = np.concatenate([[np.uint64(0)], np.cumsum(v * j.astype(np.uint64), dtype=np.uint64)])
             return np.diff(off), cs[off[1:]] - cs[off[:-1]]
+
+    def spliced(self, trims):
+        """The records with each one marked in needs_trim replaced, in place and in order, by the pieces checkIdyAndTrim
+        keeps of it (overlap.cpp:474-485).  trims = Context.trim_ranges(self.recs[self.needs_trim != 0], ...).  A
+        piece is its parent record with the four coordinates and seq_divergence replaced (alignment.cpp:416-417; the
+        score, the lengths and kmerMatches are the parent's).  Returns a result of host arrays with lines(), of(),
+        kmerMatches(): records, per-query offsets, kmerMatches; no record of it is marked."""
+        if self.needs_trim is None:
+            raise ValueError("spliced: the result has no needs_trim marks (partition_bad_mappings)")
+        rec_off, pieces = trims
+        marked = np.flatnonzero(np.asarray(self.needs_trim) != 0)
+        if len(rec_off) != len(marked) + 1:
+            raise ValueError("spliced: trims must hold one entry per marked record")
+        n = len(self.recs)
+        mult = np.ones(n, np.int64)
+        mult[marked] = np.diff(rec_off.astype(np.int64))
+        src = np.repeat(np.arange(n, dtype=np.int64), mult)
+        recs = np.asarray(self.recs)[src].copy()
+        from_piece = np.repeat(np.asarray(self.needs_trim) != 0, mult)
+        assert int(from_piece.sum()) == len(pieces)
+        for f in ("cur_begin", "cur_end", "ext_begin", "ext_end", "seq_divergence"):
+            recs[f][from_piece] = pieces[f]
+        out = object.__new__(OverlapResult)
+        out.__dict__.update(self.__dict__)
+        out.recs = recs
+        out.needs_trim = np.zeros(len(recs), np.uint8)
+        new_off = np.concatenate([[0], np.cumsum(mult)])
+        out.query_off = new_off[np.asarray(self.query_off).astype(np.int64)].astype(np.uint64)
+        if self.match_off is not None:
+            off = np.asarray(self.match_off).astype(np.int64)
+            cnt = np.diff(off)[src]
+            out.match_off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.uint64)
+            idx = np.repeat(off[:-1][src] - out.match_off[:-1].astype(np.int64), cnt) + np.arange(int(cnt.sum()), dtype=np.int64)
+            out.matches = np.asarray(self.matches)[idx]
+        return out
 
     def lines(self):
         r = self.recs
@@ -467,11 +514,9 @@ class Context:
             out.append((f"{int(bits[i]):08x}", " ".join(f"{lens[k]}{chr(ops[k])}" for k in range(a0, a1))))
         return out
 
-    def align_ranges(self, pairs, use_hpc=False, arrays=False):
-        """fg_align_ranges: getAlignmentCigarKsw of ranges of the resident sequences, cut out (and, with use_hpc,
-        homopolymer-compressed) on the device.  pairs: (n, 6) integers (cur_id, ext_id, cur_begin, cur_end, ext_begin,
-        ext_end) or a record array with those fields (the records of an OverlapResult).  Returns (what align_cigar_ksw
-        returns for those strings, aligned lengths of the cur side, of the ext side)."""
+    @staticmethod
+    def _range_pairs(pairs):
+        """The fg_range_pair table of (n, 6) integers or of a record array with those fields."""
         pairs = np.asarray(pairs)
         tab = np.zeros(len(pairs), RANGE_PAIR_DTYPE)
         if pairs.dtype.names:
@@ -484,6 +529,14 @@ class Context:
                 raise ValueError("pairs: ids are uint32, positions int32")
             for j, f in enumerate(RANGE_PAIR_DTYPE.names):
                 tab[f] = pairs[:, j]
+        return tab
+
+    def align_ranges(self, pairs, use_hpc=False, arrays=False):
+        """fg_align_ranges: getAlignmentCigarKsw of ranges of the resident sequences, cut out (and, with use_hpc,
+        homopolymer-compressed) on the device.  pairs: (n, 6) integers (cur_id, ext_id, cur_begin, cur_end, ext_begin,
+        ext_end) or a record array with those fields (the records of an OverlapResult).  Returns (what align_cigar_ksw
+        returns for those strings, aligned lengths of the cur side, of the ext side)."""
+        tab = self._range_pairs(pairs)
         n = len(tab)
         len_cur = np.zeros(n, np.int32)
         len_ext = np.zeros(n, np.int32)
@@ -495,6 +548,25 @@ class Context:
         out = self._cigar_result(b, n, arrays)
         self.L.fg_release_cigars(C.byref(b))
         return out, len_cur, len_ext
+
+    def trim_ranges(self, pairs_or_recs, use_hpc, max_divergence, min_overlap):
+        """fg_trim_ranges: checkIdyAndTrim (alignment.cpp:306-495) of ranges of the resident sequences, on the device.
+        pairs_or_recs as for align_ranges.  Returns (rec_off, recs): the pieces of pair i are recs[rec_off[i]:
+        rec_off[i + 1]] (TRIM_REC_DTYPE), in the order the reference returns them."""
+        tab = self._range_pairs(pairs_or_recs)
+        n = len(tab)
+        b = TrimBatch()
+        t0 = time.perf_counter()
+        self._check(self.L.fg_trim_ranges(self.h, tab.ctypes.data if n else None, n, int(bool(use_hpc)),
+                                          float(np.float32(max_divergence)), int(min_overlap), C.byref(b)))
+        self.last_trim_seconds = time.perf_counter() - t0
+        rec_off = np.ctypeslib.as_array(b.rec_off, (n + 1,)).copy() if b.rec_off else np.zeros(n + 1, np.uint64)
+        total = int(rec_off[n])
+        recs = np.empty(total, TRIM_REC_DTYPE)
+        if total:
+            C.memmove(recs.ctypes.data, b.recs, total * TRIM_REC_DTYPE.itemsize)
+        self.L.fg_release_trims(C.byref(b))
+        return rec_off, recs
 
     def kernel_times(self):
         arr = (KernelTime * 64)()

@@ -218,9 +218,9 @@ struct fg_detector_params {
 	uint8_t nucl_alignment;        /* base-level divergence (alignment.cpp:218-247) */
 	uint8_t partition_bad_mappings;/* 1: primaries that FAIL the divergence gate are returned too,
 	                                  marked in fg_overlap_batch.needs_trim, in the position
-	                                  where the caller splices in the result of its own
-	                                  checkIdyAndTrim (overlap.cpp:474-485; the ksw2 alignment
-	                                  stays on the host).  Only with max_overlaps = 0, as every
+	                                  where the caller splices in the pieces checkIdyAndTrim
+	                                  keeps (overlap.cpp:474-485): fg_trim_ranges computes them
+	                                  on the device for these records.  Only with max_overlaps = 0, as every
 	                                  caller in the reference uses it (overlap.h:323);
 	                                  FG_ERR_UNSUPPORTED otherwise */
 	uint8_t use_hpc;
@@ -502,10 +502,34 @@ void fg_release_cigars(struct fg_cigar_batch* b);
  * aligned (compressed) lengths.  The strings are cut out of the 2-bit reads, aligned and decoded on the device: no
  * string crosses the bus.  Empty ranges are legal and behave as empty strings do.  FG_ERR_STATE without reads;
  * FG_ERR_ARG for an unknown id, begin < 0, end < begin, end > length, or NULL pairs / out with n_pairs > 0 -- found
- * before any device work.  The interval search of checkIdyAndTrim stays with the caller. */
+ * before any device work.  The second half of checkIdyAndTrim is fg_trim_ranges below. */
 struct fg_range_pair { uint32_t cur_id, ext_id; int32_t cur_begin, cur_end, ext_begin, ext_end; };
 int fg_align_ranges(fg_ctx* ctx, const struct fg_range_pair* pairs, uint32_t n_pairs, uint8_t use_hpc,
                     struct fg_cigar_batch* out, int32_t* len_cur, int32_t* len_ext);
+
+/* checkIdyAndTrim (alignment.cpp:306-495) as a whole for the same pairs: the alignment of fg_align_ranges, then, on the
+ * runs while they are on the device, the search for the intervals of runs that begin and end on a '=' run with
+ * float(errors) / max(cur span, ext span) < max_divergence (:366-385), their std::sort by that length (:389; the
+ * permutation libstdc++ produces, ties included), the greedy non-intersecting selection (:393-409), the mapping back
+ * through the homopolymer offset tables and the filter "both ranges > min_overlap" (:414-456).  No run list crosses
+ * the bus.  Records of pair i: recs[rec_off[i] .. rec_off[i + 1]) in the order checkIdyAndTrim returns them.
+ * cur_end / ext_end are what the reference leaves there: begin of the pair's range + the offset of the LAST aligned
+ * base (:444-445), not one past it.  run_start / run_end: the chosen interval, inclusive indices into the pair's runs
+ * as fg_align_ranges returns them; seq_divergence = float(range_err) / range_len, computed on the host.  An
+ * OverlapRange piece is the parent record with the four coordinates and seq_divergence replaced (:416-417).
+ * Arguments, ids and errors as fg_align_ranges; empty ranges give no records, n_pairs = 0 an empty batch.  Sub-batches
+ * of pairs whose interval lists fit FG_TRIM_SCRATCH_BYTES (environment, default 1 GiB) are worked on at a time; a pair
+ * beyond it runs alone, FG_ERR_NOMEM when the device cannot hold it (or a pair has more than 131072 runs). */
+struct fg_trim_rec {
+	int32_t cur_begin, cur_end, ext_begin, ext_end;
+	int32_t run_start, run_end;
+	int32_t range_err, range_len;
+	float   seq_divergence;
+};
+struct fg_trim_batch { uint32_t n_pairs; uint64_t* rec_off; struct fg_trim_rec* recs; void* owner_; };
+int fg_trim_ranges(fg_ctx* ctx, const struct fg_range_pair* pairs, uint32_t n_pairs, uint8_t use_hpc,
+                   float max_divergence, int32_t min_overlap, struct fg_trim_batch* out);
+void fg_release_trims(struct fg_trim_batch* b);
 
 #ifdef __cplusplus
 }
