@@ -824,6 +824,58 @@ int fg_trim_ranges(fg_ctx* c, const struct fg_range_pair* pairs, uint32_t n_pair
 	return FG_OK;
 }
 
+int fg_edit_ranges(fg_ctx* c, const struct fg_range_pair* pairs, uint32_t n_pairs, uint8_t use_hpc, int32_t* dist,
+				   int32_t* len_cur, int32_t* len_ext, float* divergence)
+{
+	if (!c) return FG_ERR_ARG;
+	return guarded(c, [&]()
+	{
+		const std::vector<FgRangeSide> sides = rangeSides(c, "fg_edit_ranges", pairs, n_pairs, dist);
+		if (!n_pairs) return;
+		HIP_CHECK(hipSetDevice(c->device));
+		// the float needs both lengths, whether the caller wants them or not
+		std::vector<i32> ownCur, ownExt;
+		if (divergence && !len_cur) { ownCur.resize(n_pairs); len_cur = ownCur.data(); }
+		if (divergence && !len_ext) { ownExt.resize(n_pairs); len_ext = ownExt.data(); }
+		fgEditRanges(c, sides, use_hpc != 0, dist, len_cur, len_ext);
+		// the float of alignment.cpp:244, from the integers, as the host shim computes it for nucl_alignment records
+		// (0 / 0 = NaN for two empty strings, as that expression gives)
+		if (divergence)
+			for (u32 i = 0; i < n_pairs; ++i)
+				divergence[i] = (float)dist[i] / std::max((size_t)len_ext[i], (size_t)len_cur[i]);
+	});
+}
+
+int fg_chain_divergence(const int32_t* cur_range, const float* divergence, const uint64_t* chain_off, uint32_t n_chains,
+						float* out)
+{
+	if (!n_chains) return FG_OK;
+	if (!chain_off || !out) return FG_ERR_ARG;
+	for (u32 ch = 0; ch < n_chains; ++ch)
+		if (chain_off[ch + 1] < chain_off[ch]) return FG_ERR_ARG;
+	if (chain_off[n_chains] > chain_off[0] && (!cur_range || !divergence)) return FG_ERR_ARG;
+	// read_aligner.cpp:418-431 in single precision, every operation rounded on its own: the reference is built without
+	// fused multiply-add, so none may be formed here
+	{
+#pragma clang fp contract(off)
+		for (u32 ch = 0; ch < n_chains; ++ch)
+		{
+			float sum = 0.0f;
+			int len = 0;
+			for (u64 i = chain_off[ch]; i < chain_off[ch + 1]; ++i)
+			{
+				const float keep = 1.0f - divergence[i];
+				const float matched = (float)cur_range[i] * keep;
+				sum = sum + matched;
+				len += cur_range[i];
+			}
+			const float q = sum / (float)len;
+			out[ch] = 1.0f - q;
+		}
+	}
+	return FG_OK;
+}
+
 void fg_release_trims(struct fg_trim_batch* b)
 {
 	if (!b) return;

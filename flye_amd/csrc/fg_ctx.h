@@ -397,6 +397,11 @@ struct fg_ctx {
 	DevBuf<u32> dEditList;		// pairs queued for the bit-vector kernel (two lists)
 	DevBuf<char> dEditCnt;
 	DevBuf<u64> dEditSlab;		// per-block string planes + delta planes of the bit-vector kernel
+	// fg_edit_ranges (fg_editranges.hip): the primaries and the query array k_edit_range_prims makes of a sub-batch's
+	// side table (in dRangeSides), and the three dense arrays k_edit_range_collect leaves for the download
+	DevBuf<char> dEditPrims;
+	DevBuf<u32> dEditQuery;
+	DevBuf<i32> dEditOut;
 	// fg_align_ranges (fg_ksw.hip): the (pair, side) table, the compressed lengths, the byte strings the ksw kernels
 	// read and where each one starts, and what the decoding of a sub-batch leaves (counts, offsets, '=' / 'X' / 'I' /
 	// 'D' runs)
@@ -726,6 +731,10 @@ void fgTrimRanges(fg_ctx* c, const std::vector<FgRangeSide>& sides, bool useHpc,
 // std::sort order (ascending keys, the permutation libstdc++ produces) of each segment [segOff[i], segOff[i + 1]) of
 // the device arrays keys / vals; dSegOff on the device
 void fgSortSegments(fg_ctx* c, const u64* dSegOff, u32 nSeg, u64* dKeys, u32* dVals, u64 n);
+// fg_edit_ranges behind its argument checks (fg_editranges.hip): fgEditDistances on the ranges of `sides` (cur, ext of
+// pair 0, ...), in sub-batches of FG_EDIT_BATCH_PAIRS; dist / lenCur / lenExt: host arrays of sides.size() / 2 entries,
+// the two lengths may be null.  Resets and collects the timer; c->curQuery is as before on return.
+void fgEditRanges(fg_ctx* c, const std::vector<FgRangeSide>& sides, bool useHpc, i32* dist, i32* lenCur, i32* lenExt);
 void fgDebugSortPairs(fg_ctx* c, u64* keys, u32* vals, const u64* segOff, u32 nSeg);
 void fgDebugProbeSkipCheck(fg_ctx* c, u64* clearBits, u64* violations);
 void fgDebugEditDistances(fg_ctx* c, u32 nPairs, int useHpc, i32* outDist, i32* outLenA, i32* outLenB);

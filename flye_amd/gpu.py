@@ -43,7 +43,7 @@ ABI_SYMBOLS = ["fg_abi_version", "fg_create", "fg_destroy", "fg_strerror", "fg_l
                "fg_index_selection_done", "fg_index_gather_begin", "fg_index_gather_end", "fg_memory_stats",
                "fg_import_index", "fg_index_device_arrays", "fg_clear_index", "fg_export_index", "fg_overlaps", "fg_release_batch",
                "fg_kernel_times", "fg_debug_sort_pairs", "fg_debug_edit_distances", "fg_align_cigar_ksw", "fg_release_cigars",
-               "fg_align_ranges", "fg_trim_ranges", "fg_release_trims",
+               "fg_align_ranges", "fg_trim_ranges", "fg_release_trims", "fg_edit_ranges", "fg_chain_divergence",
                "fg_index_keep_targets", "fg_index_shard", "fg_probe_hits", "fg_overlaps_from_hits",
                "fg_index_piece_split", "fg_index_scatter_begin", "fg_index_scatter_end", "fg_debug_probe_skip_check",
                "fg_group_create", "fg_group_destroy", "fg_group_size", "fg_group_member", "fg_group_last_error",
@@ -203,6 +203,9 @@ def load_library():
         L.fg_trim_ranges.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint8, C.c_float, C.c_int32, C.POINTER(TrimBatch)]
         L.fg_release_trims.argtypes = [C.POINTER(TrimBatch)]
         L.fg_release_trims.restype = None
+        L.fg_edit_ranges.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint8, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]
+        L.fg_chain_divergence.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.fg_debug_group_bin_cuts.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         L.fg_debug_freq_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
         L.fg_debug_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int]
@@ -370,6 +373,25 @@ def memory_stats(reset_peak=False):
     now, peak = C.c_uint64(), C.c_uint64()
     load_library().fg_memory_stats(C.byref(now), C.byref(peak), 1 if reset_peak else 0)
     return now.value, peak.value
+
+
+def chain_divergence(cur_range, divergence, chain_off):
+    """fg_chain_divergence: ReadAligner::getChainBaseDivergence (read_aligner.cpp:410-434) of the chains
+    [chain_off[c], chain_off[c + 1]) over per-alignment cur ranges and divergences, in the reference's single-precision
+    operation order; float32 array of len(chain_off) - 1 values (NaN for an empty or zero-length chain)."""
+    cr = np.ascontiguousarray(cur_range, np.int32)
+    dv = np.ascontiguousarray(divergence, np.float32)
+    off = np.ascontiguousarray(chain_off, np.uint64)
+    if len(cr) != len(dv) or len(off) < 1 or (len(off) > 1 and int(off.max()) > len(cr)):
+        raise ValueError("chain_divergence: one divergence per cur_range, offsets inside them")
+    n = len(off) - 1
+    out = np.zeros(n, np.float32)
+    L = load_library()
+    rc = L.fg_chain_divergence(cr.ctypes.data if len(cr) else None, dv.ctypes.data if len(dv) else None,
+                               off.ctypes.data, n, out.ctypes.data if n else None)
+    if rc != 0:
+        raise FlyeGpuError(rc, L.fg_strerror(rc).decode())
+    return out
 
 
 class Context:
@@ -567,6 +589,22 @@ class Context:
             C.memmove(recs.ctypes.data, b.recs, total * TRIM_REC_DTYPE.itemsize)
         self.L.fg_release_trims(C.byref(b))
         return rec_off, recs
+
+    def edit_ranges(self, pairs_or_recs, use_hpc=False):
+        """fg_edit_ranges: getAlignmentErrEdlib (alignment.cpp:218-247) of ranges of the resident sequences, on the
+        device.  pairs_or_recs as for align_ranges.  Returns (edit distances, compared lengths of the cur side, of the
+        ext side, divergence = float32(dist) / float32(max(lengths)); NaN for two empty strings)."""
+        tab = self._range_pairs(pairs_or_recs)
+        n = len(tab)
+        dist = np.zeros(n, np.int32)
+        len_cur = np.zeros(n, np.int32)
+        len_ext = np.zeros(n, np.int32)
+        div = np.zeros(n, np.float32)
+        t0 = time.perf_counter()
+        self._check(self.L.fg_edit_ranges(self.h, tab.ctypes.data if n else None, n, int(bool(use_hpc)),
+                                          *(a.ctypes.data if n else None for a in (dist, len_cur, len_ext, div))))
+        self.last_edit_seconds = time.perf_counter() - t0
+        return dist, len_cur, len_ext, div
 
     def kernel_times(self):
         arr = (KernelTime * 64)()

@@ -531,6 +531,34 @@ int fg_trim_ranges(fg_ctx* ctx, const struct fg_range_pair* pairs, uint32_t n_pa
                    float max_divergence, int32_t min_overlap, struct fg_trim_batch* out);
 void fg_release_trims(struct fg_trim_batch* b);
 
+/* getAlignmentErrEdlib (src/sequence/alignment.cpp:218-247) for ranges of the resident sequences: what
+ * ReadAligner::getChainBaseDivergence (src/repeat_graph/read_aligner.cpp:410-434) computes for every alignment of a
+ * chain when reads_base_alignment is set.  Pairs, ids, containers and errors are those of fg_align_ranges: cur_id names
+ * a sequence of the fg_set_queries container when one is set (the reads), otherwise of the indexed container; ext_id
+ * always one of the indexed container (the graph edges); odd ids are the reverse-complement strand; empty ranges are
+ * legal.  dist[i] = what edlibAlign(NW, TASK_DISTANCE, k = -1) returns for the two strings (alignment.cpp:233-238),
+ * homopolymer-compressed first (alignment.cpp:52-70) when use_hpc != 0; an empty side gives the other side's length
+ * (edlib.cpp:160-164).  len_cur / len_ext = the compared (compressed) lengths; divergence[i] = (float)dist /
+ * (float)max(len_cur, len_ext), computed on the host from the integers (alignment.cpp:244), NaN for two empty
+ * strings as the reference's expression gives.  dist is required with n_pairs > 0, the other three may be NULL;
+ * n_pairs = 0 is FG_OK.  The strings are cut out of the 2-bit reads on the device by the kernels behind
+ * nucl_alignment; only the side table (32 B per pair) goes up and 12 B per pair come back.  Pairs are worked on in
+ * sub-batches of FG_EDIT_BATCH_PAIRS (environment, default 2^20); fg_kernel_times afterwards reports the sums over
+ * them.  FG_ERR_STATE without reads; FG_ERR_ARG for an unknown id, begin < 0, end < begin, end > length, or NULL
+ * pairs / dist with n_pairs > 0 -- found before any device work.  The context is left as fg_overlaps expects it. */
+int fg_edit_ranges(fg_ctx* ctx, const struct fg_range_pair* pairs, uint32_t n_pairs, uint8_t use_hpc,
+                   int32_t* dist, int32_t* len_cur, int32_t* len_ext, float* divergence);
+
+/* ReadAligner::getChainBaseDivergence (read_aligner.cpp:410-434) from per-alignment values; host only, no context.
+ * Chain c = the entries [chain_off[c], chain_off[c + 1]) of cur_range (the alignment's curRange()) and divergence
+ * (the record's own seq_divergence for a caller that does not realign, fg_edit_ranges' divergence for one that does).
+ * The reference's float sequence, every operation rounded to single precision on its own (no fused multiply-add):
+ * sum = 0.0f, len = 0; per entry sum = sum + (float)cur_range[i] * (1.0f - divergence[i]), len += cur_range[i];
+ * out[c] = 1.0f - sum / (float)len -- NaN for an empty chain or one of total length 0, as in the reference.
+ * FG_ERR_ARG for NULL arrays with n_chains > 0 or decreasing offsets. */
+int fg_chain_divergence(const int32_t* cur_range, const float* divergence, const uint64_t* chain_off,
+                        uint32_t n_chains, float* out);
+
 #ifdef __cplusplus
 }
 #endif
