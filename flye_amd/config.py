@@ -21,6 +21,7 @@ _COMMON = {
     "meta_read_filter_kmer_freq": 100,
     "repeat_kmer_rate": 100,
     "maximum_jump": 1500,
+    "max_separation": 500,      # asm_defaults.cfg:16 (ReadAligner::chainReadAlignments, read_aligner.cpp:30)
 }
 
 # what the callers of the path in the assemble stage read besides the presets: Extender / ChimeraDetector

@@ -763,6 +763,11 @@ struct TrimOwner {
 	std::vector<uint64_t> recOff;
 	std::vector<fg_trim_rec> recs;
 };
+
+struct ChainOwner {
+	std::vector<uint64_t> chainOff, alnOff, aln;
+	std::vector<int32_t> score;
+};
 }
 
 int fg_align_ranges(fg_ctx* c, const struct fg_range_pair* pairs, uint32_t n_pairs, uint8_t use_hpc,
@@ -874,6 +879,71 @@ int fg_chain_divergence(const int32_t* cur_range, const float* divergence, const
 		}
 	}
 	return FG_OK;
+}
+
+int fg_chain_alignments(fg_ctx* c, const struct fg_chain_params* p, const struct fg_overlap_rec* recs,
+						const uint64_t* query_off, uint32_t n_queries, uint32_t first_ext_id, uint32_t n_ext_ids,
+						const uint32_t* node_left, const uint32_t* node_right, struct fg_chain_batch* out)
+{
+	if (!c) return FG_ERR_ARG;
+	if (out) memset(out, 0, sizeof(*out));
+	ChainOwner* own = nullptr;
+	const int rc = guarded(c, [&]()
+	{
+		const std::string name = "fg_chain_alignments";
+		if (!p || !out) throw FgError{FG_ERR_ARG, name + ": null parameters or result"};
+		if (p->max_jump <= 0 || p->max_read_overlap < 0 || p->min_alignment < 0 || p->max_separation < 0 || p->long_edge < 0 ||
+			p->big_alignment < 0)
+			throw FgError{FG_ERR_ARG, name + ": max_jump must be positive, the other parameters not negative"};
+		if (n_queries && !query_off) throw FgError{FG_ERR_ARG, name + ": null query_off"};
+		for (u32 q = 0; q < n_queries; ++q)
+		{
+			if (query_off[q + 1] < query_off[q]) throw FgError{FG_ERR_ARG, name + ": query_off decreases at query " + std::to_string(q)};
+			if (query_off[q + 1] - query_off[q] > (u64)FG_CHAIN_MAX_RECS)
+				throw FgError{FG_ERR_ARG, name + ": query " + std::to_string(q) + " has " + std::to_string(query_off[q + 1] - query_off[q]) +
+										  " records, more than FG_CHAIN_MAX_RECS"};
+		}
+		const u64 r0 = n_queries ? query_off[0] : 0, nRec = n_queries ? query_off[n_queries] - r0 : 0;
+		if (nRec && (!recs || !node_left || !node_right)) throw FgError{FG_ERR_ARG, name + ": null records or node tables"};
+		// the seven integers the step reads of a record
+		std::vector<FgChainAln> tab(nRec);
+		for (u64 i = 0; i < nRec; ++i)
+		{
+			const fg_overlap_rec& r = recs[r0 + i];
+			if (r.ext_id < first_ext_id || r.ext_id - first_ext_id >= n_ext_ids)
+				throw FgError{FG_ERR_ARG, name + ": record " + std::to_string(r0 + i) + ": ext_id " + std::to_string(r.ext_id) +
+										  " has no entry in the node tables"};
+			if (r.cur_begin < 0 || r.cur_end < r.cur_begin || r.ext_begin < 0 || r.ext_end < r.ext_begin || r.ext_end > r.ext_len)
+				throw FgError{FG_ERR_ARG, name + ": record " + std::to_string(r0 + i) + ": ranges [" + std::to_string(r.cur_begin) + ", " +
+										  std::to_string(r.cur_end) + ") / [" + std::to_string(r.ext_begin) + ", " + std::to_string(r.ext_end) +
+										  ") of " + std::to_string(r.ext_len)};
+			tab[i] = FgChainAln{r.cur_begin, r.cur_end, r.ext_begin, r.ext_end, r.ext_len, r.score, r.ext_id - first_ext_id};
+		}
+		own = new ChainOwner;
+		std::vector<u64> qOff((size_t)n_queries + 1, 0);
+		for (u32 q = 0; q <= n_queries && n_queries; ++q) qOff[q] = query_off[q] - r0;
+		if (nRec) HIP_CHECK(hipSetDevice(c->device));
+		fgChainAlignments(c, *p, tab, qOff, r0, node_left, node_right, n_ext_ids, own->chainOff, own->alnOff, own->aln, own->score);
+		if (own->aln.empty()) own->aln.reserve(1);
+		if (own->score.empty()) own->score.reserve(1);
+	});
+	if (rc != FG_OK) { delete own; return rc; }
+	out->n_queries = n_queries;
+	out->n_chains = own->score.size();
+	out->n_alns = own->aln.size();
+	out->chain_off = own->chainOff.data();
+	out->aln_off = own->alnOff.data();
+	out->aln = own->aln.data();
+	out->score = own->score.data();
+	out->owner_ = own;
+	return FG_OK;
+}
+
+void fg_release_chains(struct fg_chain_batch* b)
+{
+	if (!b) return;
+	delete (ChainOwner*)b->owner_;
+	memset(b, 0, sizeof(*b));
 }
 
 void fg_release_trims(struct fg_trim_batch* b)

@@ -421,6 +421,13 @@ struct fg_ctx {
 	DevBuf<unsigned long long> dTrimPairCnt;
 	DevBuf<u32> dTrimVals, dTrimAccCnt, dTrimKept;
 	DevBuf<char> dTrimRaw, dTrimOut;
+	// fg_chain_alignments (fg_readchain.hip): the node tables, a sub-batch's side table and per-query offsets, the keys
+	// and values of its two sorts, the sorted alignments, the per-alignment state of the DP and of the selection (one
+	// pool of 32-bit arrays) and the chains that go back
+	DevBuf<u32> dRcNodes, dRcVals, dRcU32;
+	DevBuf<char> dRcTab, dRcAln;
+	DevBuf<u64> dRcOff, dRcKeys, dRcOut;
+	DevBuf<i32> dRcOutScore;
 	PinnedBuf<char> hPrim;
 	PinnedBuf<u64> hOff;
 	PinnedBuf<u64> hScalar;		// staging of the counts the host reads between kernels (pinned: no bounce buffer)
@@ -735,6 +742,14 @@ void fgSortSegments(fg_ctx* c, const u64* dSegOff, u32 nSeg, u64* dKeys, u32* dV
 // pair 0, ...), in sub-batches of FG_EDIT_BATCH_PAIRS; dist / lenCur / lenExt: host arrays of sides.size() / 2 entries,
 // the two lengths may be null.  Resets and collects the timer; c->curQuery is as before on return.
 void fgEditRanges(fg_ctx* c, const std::vector<FgRangeSide>& sides, bool useHpc, i32* dist, i32* lenCur, i32* lenExt);
+// fg_chain_alignments behind its argument checks (fg_readchain.hip).  tab: what the step reads of every record, in the
+// caller's order (ext = ext_id - first_ext_id); qOff: n_queries + 1 offsets into it; recBase: the caller's query_off[0];
+// nodeLeft / nodeRight: nExt entries.  Queries are worked on in sub-batches of FG_READCHAIN_BATCH_RECS records.  Resets
+// and collects the timer.
+struct FgChainAln { i32 curBegin, curEnd, extBegin, extEnd, extLen, score; u32 ext; };
+void fgChainAlignments(fg_ctx* c, const fg_chain_params& p, const std::vector<FgChainAln>& tab, const std::vector<u64>& qOff,
+					   u64 recBase, const u32* nodeLeft, const u32* nodeRight, u32 nExt, std::vector<u64>& chainOff,
+					   std::vector<u64>& alnOff, std::vector<u64>& aln, std::vector<i32>& score);
 void fgDebugSortPairs(fg_ctx* c, u64* keys, u32* vals, const u64* segOff, u32 nSeg);
 void fgDebugProbeSkipCheck(fg_ctx* c, u64* clearBits, u64* violations);
 void fgDebugEditDistances(fg_ctx* c, u32 nPairs, int useHpc, i32* outDist, i32* outLenA, i32* outLenB);

@@ -44,6 +44,7 @@ ABI_SYMBOLS = ["fg_abi_version", "fg_create", "fg_destroy", "fg_strerror", "fg_l
                "fg_import_index", "fg_index_device_arrays", "fg_clear_index", "fg_export_index", "fg_overlaps", "fg_release_batch",
                "fg_kernel_times", "fg_debug_sort_pairs", "fg_debug_edit_distances", "fg_align_cigar_ksw", "fg_release_cigars",
                "fg_align_ranges", "fg_trim_ranges", "fg_release_trims", "fg_edit_ranges", "fg_chain_divergence",
+               "fg_chain_alignments", "fg_release_chains",
                "fg_index_keep_targets", "fg_index_shard", "fg_probe_hits", "fg_overlaps_from_hits",
                "fg_index_piece_split", "fg_index_scatter_begin", "fg_index_scatter_end", "fg_debug_probe_skip_check",
                "fg_group_create", "fg_group_destroy", "fg_group_size", "fg_group_member", "fg_group_last_error",
@@ -106,6 +107,26 @@ class CigarBatch(C.Structure):
 
 class TrimBatch(C.Structure):
     _fields_ = [("n_pairs", C.c_uint32), ("rec_off", C.POINTER(C.c_uint64)), ("recs", C.c_void_p), ("owner_", C.c_void_p)]
+
+
+class ChainParams(C.Structure):
+    """struct fg_chain_params: the constants of ReadAligner::chainReadAlignments and of the alignRead lambda's filter
+    (read_aligner.cpp:27-30, :158-160)."""
+    _fields_ = [("max_jump", C.c_int32), ("max_read_overlap", C.c_int32), ("min_alignment", C.c_int32),
+                ("max_separation", C.c_int32), ("long_edge", C.c_int32), ("big_alignment", C.c_int32)]
+
+    @classmethod
+    def from_config(cls, cfg: dict, min_overlap: int):
+        """MAX_JUMP and MAX_SEP from the configuration, MIN_ALN = Parameters::minimumOverlap, the rest the reference's
+        literals."""
+        return cls(max_jump=int(cfg["maximum_jump"]), max_read_overlap=50, min_alignment=int(min_overlap),
+                   max_separation=int(cfg["max_separation"]), long_edge=900, big_alignment=500)
+
+
+class ChainBatch(C.Structure):
+    _fields_ = [("n_queries", C.c_uint32), ("n_chains", C.c_uint64), ("n_alns", C.c_uint64),
+                ("chain_off", C.POINTER(C.c_uint64)), ("aln_off", C.POINTER(C.c_uint64)), ("aln", C.POINTER(C.c_uint64)),
+                ("score", C.POINTER(C.c_int32)), ("owner_", C.c_void_p)]
 
 
 class BridgeStats(C.Structure):
@@ -206,6 +227,10 @@ def load_library():
         L.fg_edit_ranges.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint8, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p]
         L.fg_chain_divergence.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.fg_chain_alignments.argtypes = [C.c_void_p, C.POINTER(ChainParams), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                          C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(ChainBatch)]
+        L.fg_release_chains.argtypes = [C.POINTER(ChainBatch)]
+        L.fg_release_chains.restype = None
         L.fg_debug_group_bin_cuts.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         L.fg_debug_freq_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
         L.fg_debug_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int]
@@ -606,10 +631,92 @@ class Context:
         self.last_edit_seconds = time.perf_counter() - t0
         return dist, len_cur, len_ext, div
 
+    def chain_alignments(self, recs, query_off, params, first_ext_id, node_left, node_right):
+        """fg_chain_alignments: the filter, the std::sort by curBegin and chainReadAlignments (read_aligner.cpp:24-154,
+        :219-236) for the per-read lists recs[query_off[q]:query_off[q + 1]] (REC_DTYPE, any order).  node_left /
+        node_right: the nodes of the edge that owns indexed sequence first_ext_id + i.  Returns (chain_off, aln_off, aln,
+        score): the chains of query q are chain_off[q] .. chain_off[q + 1], chain c holds recs[aln[aln_off[c]:
+        aln_off[c + 1]]], front first, with Chain::score score[c]."""
+        r = np.ascontiguousarray(recs, REC_DTYPE)
+        off = np.ascontiguousarray(query_off, np.uint64)
+        nl = np.ascontiguousarray(node_left, np.uint32)
+        nr = np.ascontiguousarray(node_right, np.uint32)
+        if len(off) < 1 or len(nl) != len(nr) or (len(off) > 1 and int(off.max()) > len(r)):
+            raise ValueError("chain_alignments: offsets inside the records, one node pair per indexed sequence id")
+        nq = len(off) - 1
+        b = ChainBatch()
+        t0 = time.perf_counter()
+        self._check(self.L.fg_chain_alignments(self.h, C.byref(params), r.ctypes.data if len(r) else None, off.ctypes.data, nq,
+                                               int(first_ext_id), len(nl), nl.ctypes.data if len(nl) else None,
+                                               nr.ctypes.data if len(nr) else None, C.byref(b)))
+        self.last_chain_seconds = time.perf_counter() - t0
+        nc, na = int(b.n_chains), int(b.n_alns)
+        out = (np.ctypeslib.as_array(b.chain_off, (nq + 1,)).copy(), np.ctypeslib.as_array(b.aln_off, (nc + 1,)).copy(),
+               np.ctypeslib.as_array(b.aln, (na,)).copy() if na else np.zeros(0, np.uint64),
+               np.ctypeslib.as_array(b.score, (nc,)).copy() if nc else np.zeros(0, np.int32))
+        self.L.fg_release_chains(C.byref(b))
+        return out
+
+    def align_reads(self, detector_params, query_ids, chain_params, node_left, node_right, max_divergence, realign=False,
+                    use_hpc=False):
+        """The body of ReadAligner::alignReads' alignRead lambda (read_aligner.cpp:212-262) for a batch of reads of the
+        fg_set_queries container against the indexed edge sequences, as three device calls and one host fold:
+        fg_overlaps with the flags alignReads gives its detector (:186-192: no overhang test, every primary, no
+        kmerMatches, no divergence gate, no base-level alignment; max_jump, min_overlap and use_hpc are taken from
+        detector_params), fg_chain_alignments, with realign (reads_base_alignment) one fg_edit_ranges call over all
+        alignments of all chains, fg_chain_divergence, and the gate chainDivergence < max_divergence (:245).
+        node_left / node_right: the nodes of the edge behind indexed sequence id first_id + i, both strands.
+        Returns a ReadAlignments."""
+        p = DetectorParams(max_jump=detector_params.max_jump, min_overlap=detector_params.min_overlap, max_overhang=0,
+                           keep_alignment=0, only_max_ext=0, nucl_alignment=0, partition_bad_mappings=0,
+                           use_hpc=detector_params.use_hpc, max_divergence=1.0)
+        q = np.ascontiguousarray(query_ids, dtype=np.uint32)
+        b = OverlapBatch()
+        self._check(self.L.fg_overlaps(self.h, C.byref(p), q.ctypes.data, len(q), 0, 0, C.byref(b)))
+        res = OverlapResult(self.L, q, b)
+        recs = np.asarray(res.recs)
+        nl = np.ascontiguousarray(node_left, np.uint32)
+        nr = np.ascontiguousarray(node_right, np.uint32)
+        chain_off, aln_off, aln, _ = self.chain_alignments(recs, res.query_off, chain_params, self.first_id, nl, nr)
+        alns = recs[aln.astype(np.int64)]
+        div = self.edit_ranges(alns, use_hpc)[3] if realign else alns["seq_divergence"]
+        chain_div = chain_divergence(alns["cur_end"] - alns["cur_begin"], div, aln_off)
+        good = chain_div < np.float32(max_divergence)
+        out_chains, out_off = [], [0]
+        for i in range(len(q)):
+            mine = [alns[int(aln_off[c]):int(aln_off[c + 1])] for c in range(int(chain_off[i]), int(chain_off[i + 1])) if good[c]]
+            out_chains += mine + [complement(ch)[::-1] for ch in mine]
+            out_off.append(len(out_chains))
+        return ReadAlignments(q, out_off, out_chains, self.first_id, nl, nr, chain_off, chain_div)
+
     def kernel_times(self):
         arr = (KernelTime * 64)()
         n = self.L.fg_kernel_times(self.h, arr, 64)
         return {arr[i].name.decode(): (arr[i].seconds, arr[i].launches) for i in range(min(n, 64))}
+
+
+class ReadAlignments:
+    """What the alignRead lambda appends to _readAlignments for a batch of reads (read_aligner.cpp:251-278).  Per query i
+    the chains chain_off[i] .. chain_off[i + 1]: the good chains, then their complements (every record complemented, the
+    chain reversed).  Chain c = recs[aln_off[c]:aln_off[c + 1]] (REC_DTYPE) with the nodes of each alignment's edge in
+    node_left / node_right, read from the caller's tables at the record's ext_id -- the complement edge's entry for a
+    complemented record.  divergence: chainDivergence of EVERY chain chainReadAlignments returned, good or not, in the
+    order divergenceStats.add sees them (:244); query i's are divergence[all_chain_off[i]:all_chain_off[i + 1]]."""
+
+    def __init__(self, query_ids, chain_off, chains, first_ext_id, node_left, node_right, all_chain_off, divergence):
+        self.query_ids = query_ids
+        self.chain_off = np.asarray(chain_off, np.uint64)
+        self.aln_off = np.zeros(len(chains) + 1, np.uint64)
+        self.aln_off[1:] = np.cumsum([len(ch) for ch in chains])
+        self.recs = np.concatenate(chains) if chains else np.zeros(0, REC_DTYPE)
+        at = self.recs["ext_id"].astype(np.int64) - int(first_ext_id)
+        self.node_left, self.node_right = node_left[at], node_right[at]
+        self.all_chain_off = all_chain_off
+        self.divergence = divergence
+
+    def chains_of(self, i):
+        return [self.recs[int(self.aln_off[c]):int(self.aln_off[c + 1])]
+                for c in range(int(self.chain_off[i]), int(self.chain_off[i + 1]))]
 
 
 class VertexIndex:

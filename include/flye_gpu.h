@@ -559,6 +559,53 @@ int fg_edit_ranges(fg_ctx* ctx, const struct fg_range_pair* pairs, uint32_t n_pa
 int fg_chain_divergence(const int32_t* cur_range, const float* divergence, const uint64_t* chain_off,
                         uint32_t n_chains, float* out);
 
+/* The edge-chain step of ReadAligner::alignReads (read_aligner.cpp:212-262) for a batch of reads: the lambda's filter
+ * (:224-226), its std::sort by curBegin (:233-235) and chainReadAlignments (:24-154) -- the DP over the read's
+ * alignments with its two deques and their cleanup, the std::sort of "active then frozen" by score (:119-123) and the
+ * greedy selection of non-intersecting chains (:126-151).  What comes back is what chainReadAlignments returns, before
+ * the divergence gate of :238-249 (fg_edit_ranges / fg_chain_divergence give the caller that).
+ * recs[query_off[q] .. query_off[q + 1]) are the overlap records of query q in any order (fg_overlaps with only_max_ext
+ * = 0, a scheduler result, a loaded dump); node_left[i] / node_right[i] are the caller's numbers of edge->nodeLeft /
+ * nodeRight of the edge that owns indexed sequence first_ext_id + i, both strands listed (an odd id carries the
+ * complement edge's nodes, idToSegment of :165-175).  Per query: a record is kept when ext_len < long_edge ||
+ * min(cur_end - cur_begin, ext_end - ext_begin) > big_alignment; the kept ones are sorted by cur_begin and the chains
+ * by score in the permutations libstdc++'s std::sort produces, ties included; scores add in int32.  Chains of query q:
+ * chain_off[q] .. chain_off[q + 1], in the order chainReadAlignments returns them; alignments of chain c: aln[aln_off[c]
+ * .. aln_off[c + 1]), indices into recs, front of the chain first; score[c] = Chain::score.
+ * The step reads seven integers per record; only that table and the node tables go up and only the chains come back.
+ * The context lends its device and stream: no reads, no index are needed, and any member of a group serves.  Queries
+ * are worked on in sub-batches of FG_READCHAIN_BATCH_RECS records (environment, default 2^20; a longer query runs
+ * alone); fg_kernel_times afterwards reports the sums over them.  A query may have at most FG_CHAIN_MAX_RECS records:
+ * the DP is serial over a query's alignments.
+ * FG_ERR_ARG, found before any device work: NULL p or out; NULL recs, query_off or node tables with records to read; a
+ * decreasing query_off; max_jump <= 0 or another parameter < 0; a query beyond FG_CHAIN_MAX_RECS; a record whose ext_id
+ * is outside [first_ext_id, first_ext_id + n_ext_ids) or with cur_begin < 0, cur_end < cur_begin, ext_begin < 0,
+ * ext_end < ext_begin or ext_end > ext_len.  n_queries = 0 gives an empty batch (chain_off = {0}, aln_off = {0}). */
+#define FG_CHAIN_MAX_RECS 65536
+struct fg_chain_params {
+	int32_t max_jump;          /* Config "maximum_jump"            (read_aligner.cpp:27) */
+	int32_t max_read_overlap;  /* MAX_READ_OVLP = 50               (:28) */
+	int32_t min_alignment;     /* Parameters::minimumOverlap       (:29) */
+	int32_t max_separation;    /* Config "max_separation"          (:30) */
+	int32_t long_edge;         /* LONG_EDGE = 900                  (:160) */
+	int32_t big_alignment;     /* BIG_ALN = 500                    (:159) */
+};
+struct fg_chain_batch {
+	uint32_t  n_queries;
+	uint64_t  n_chains, n_alns;
+	uint64_t* chain_off;   /* n_queries + 1: chains of query q, in the order chainReadAlignments returns them */
+	uint64_t* aln_off;     /* n_chains + 1, into aln */
+	uint64_t* aln;         /* index into the caller's recs[], front of the chain first */
+	int32_t*  score;       /* n_chains: Chain::score */
+	void*     owner_;
+};
+int fg_chain_alignments(fg_ctx* ctx, const struct fg_chain_params* p,
+                        const struct fg_overlap_rec* recs, const uint64_t* query_off, uint32_t n_queries,
+                        uint32_t first_ext_id, uint32_t n_ext_ids,
+                        const uint32_t* node_left, const uint32_t* node_right,
+                        struct fg_chain_batch* out);
+void fg_release_chains(struct fg_chain_batch* b);
+
 #ifdef __cplusplus
 }
 #endif
