@@ -3,6 +3,7 @@
 // file; there is no CPU fallback -- without a HIP device fg_create fails.
 #include "fg_ctx.h"
 #include <chrono>
+#include <cmath>
 
 #include <algorithm>
 #include <new>
@@ -768,6 +769,24 @@ struct ChainOwner {
 	std::vector<uint64_t> chainOff, alnOff, aln;
 	std::vector<int32_t> score;
 };
+struct CoverageOwner {
+	std::vector<uint64_t> winOff;
+	std::vector<int32_t> full, junction, max, median, minGood, threshold;
+	std::vector<int64_t> sum;
+	std::vector<uint8_t> chimeric, degenerate;
+};
+// max, median, min of target t out of the device's three values per target
+void splitCoverageStats(const std::vector<i32>& stat, std::vector<int32_t>& mx, std::vector<int32_t>& med, std::vector<int32_t>* mn)
+{
+	const size_t n = stat.size() / 3;
+	mx.resize(n); med.resize(n);
+	if (mn) mn->resize(n);
+	for (size_t t = 0; t < n; ++t)
+	{
+		mx[t] = stat[3 * t]; med[t] = stat[3 * t + 1];
+		if (mn) (*mn)[t] = stat[3 * t + 2];
+	}
+}
 }
 
 int fg_align_ranges(fg_ctx* c, const struct fg_range_pair* pairs, uint32_t n_pairs, uint8_t use_hpc,
@@ -937,6 +956,208 @@ int fg_chain_alignments(fg_ctx* c, const struct fg_chain_params* p, const struct
 	out->score = own->score.data();
 	out->owner_ = own;
 	return FG_OK;
+}
+
+int fg_coverage_windows(int32_t seq_len, int32_t window, int32_t max_overhang, int32_t* n_windows, int32_t* max_flank,
+						uint8_t* degenerate)
+{
+	if (seq_len < 0 || window <= 0 || max_overhang < 0) return FG_ERR_ARG;
+	// chimera.cpp:114-115 as written there: float / int, + 1 in single precision, then the conversion to int
+	const int numWindows = std::ceil((float)seq_len / window) + 1;
+	const int n = numWindows - 2;
+	if (n_windows) *n_windows = n <= 0 ? 1 : n;
+	if (degenerate) *degenerate = n <= 0 ? 1 : 0;
+	// :168-169: int / float, truncated
+	if (max_flank) *max_flank = (int)((float)(int)max_overhang / (float)window);
+	return FG_OK;
+}
+
+int fg_coverage_verdict(const struct fg_coverage_params* p, uint32_t n, const int32_t* n_windows, const int64_t* sum,
+						const int32_t* median, const int32_t* min_good, int32_t* threshold, uint8_t* chimeric)
+{
+	if (!p || p->window <= 0 || p->max_overhang < 0 || !(p->max_drop_rate > 0)) return FG_ERR_ARG;
+	if (!n) return FG_OK;
+	if (!n_windows || !sum || !median || !min_good || !chimeric) return FG_ERR_ARG;
+	int32_t maxFlank = 0;
+	fg_coverage_windows(0, p->window, p->max_overhang, nullptr, &maxFlank, nullptr);
+	const float MAX_DROP_RATE = p->max_drop_rate;
+	for (u32 i = 0; i < n; ++i)
+	{
+		if (sum[i] == 0)		// chimera.cpp:153
+		{
+			if (threshold) threshold[i] = 0;
+			chimeric[i] = 1;
+			continue;
+		}
+		// :155-164
+		int thr;
+		if (!p->uneven_coverage) thr = std::max(1L, std::lround((float)p->overlap_coverage / MAX_DROP_RATE));
+		else thr = std::max(1L, std::lround(median[i] / MAX_DROP_RATE));
+		// :166-182 with the loop folded into min_good
+		const int32_t goodStart = maxFlank, goodEnd = n_windows[i] - maxFlank - 1;
+		if (threshold) threshold[i] = thr;
+		chimeric[i] = (goodEnd <= goodStart || min_good[i] < thr) ? 1 : 0;
+	}
+	return FG_OK;
+}
+
+int fg_read_coverage(fg_ctx* c, const struct fg_coverage_params* p, const struct fg_overlap_rec* recs,
+					 const uint64_t* query_off, uint32_t n_queries, const int32_t* query_len, struct fg_coverage_batch* out)
+{
+	if (!c) return FG_ERR_ARG;
+	if (out) memset(out, 0, sizeof(*out));
+	CoverageOwner* own = nullptr;
+	const int rc = guarded(c, [&]()
+	{
+		const std::string name = "fg_read_coverage";
+		if (!p || !out) throw FgError{FG_ERR_ARG, name + ": null parameters or result"};
+		if (p->window <= 0 || p->max_overhang < 0 || !(p->max_drop_rate > 0))
+			throw FgError{FG_ERR_ARG, name + ": window and max_drop_rate must be positive, max_overhang not negative"};
+		if (n_queries && (!query_off || !query_len)) throw FgError{FG_ERR_ARG, name + ": null query_off or query_len"};
+		for (u32 q = 0; q < n_queries; ++q)
+		{
+			if (query_off[q + 1] < query_off[q]) throw FgError{FG_ERR_ARG, name + ": query_off decreases at query " + std::to_string(q)};
+			if (query_len[q] < 0) throw FgError{FG_ERR_ARG, name + ": query " + std::to_string(q) + " has a negative length"};
+		}
+		const u64 r0 = n_queries ? query_off[0] : 0, nRec = n_queries ? query_off[n_queries] - r0 : 0;
+		if (nRec && !recs) throw FgError{FG_ERR_ARG, name + ": null records"};
+		for (u32 q = 0; q < n_queries; ++q)
+			for (u64 i = query_off[q]; i < query_off[q + 1]; ++i)
+			{
+				const fg_overlap_rec& r = recs[i];
+				if (r.cur_len != query_len[q] || r.cur_begin < 0 || r.cur_end < r.cur_begin || r.cur_end > r.cur_len || r.ext_begin < 0 ||
+					r.ext_end < r.ext_begin || r.ext_end > r.ext_len)
+					throw FgError{FG_ERR_ARG, name + ": record " + std::to_string(i) + " of query " + std::to_string(q) + ": ranges [" +
+											  std::to_string(r.cur_begin) + ", " + std::to_string(r.cur_end) + ") of " + std::to_string(r.cur_len) +
+											  " / [" + std::to_string(r.ext_begin) + ", " + std::to_string(r.ext_end) + ") of " +
+											  std::to_string(r.ext_len) + ", query length " + std::to_string(query_len[q])};
+			}
+		own = new CoverageOwner;
+		own->winOff.assign((size_t)n_queries + 1, 0);
+		own->degenerate.resize(n_queries);
+		std::vector<u64> qOff((size_t)n_queries + 1, 0);
+		std::vector<i32> nClip(n_queries), nWin(n_queries);
+		int32_t maxFlank = 0;
+		fg_coverage_windows(0, p->window, p->max_overhang, nullptr, &maxFlank, nullptr);
+		for (u32 q = 0; q < n_queries; ++q)
+		{
+			fg_coverage_windows(query_len[q], p->window, p->max_overhang, &nWin[q], nullptr, &own->degenerate[q]);
+			nClip[q] = own->degenerate[q] ? 0 : nWin[q];
+			own->winOff[q + 1] = own->winOff[q] + (u64)nWin[q];
+			qOff[q + 1] = query_off[q + 1] - r0;
+		}
+		const u64 nAll = own->winOff[n_queries];
+		if (p->want_vectors) { own->full.resize(nAll); own->junction.resize(nAll); }
+		own->sum.resize(n_queries);
+		own->threshold.resize(n_queries); own->chimeric.resize(n_queries);
+		std::vector<i32> stat(3 * (size_t)n_queries);
+		if (n_queries)
+		{
+			HIP_CHECK(hipSetDevice(c->device));
+			fgReadCoverage(c, p->window, p->max_overhang, maxFlank, recs ? recs + r0 : nullptr, qOff, own->winOff, nClip,
+						   p->want_vectors != 0, own->full.data(), own->junction.data(), (long long*)own->sum.data(), stat.data());
+		}
+		splitCoverageStats(stat, own->max, own->median, &own->minGood);
+		fg_coverage_verdict(p, n_queries, nWin.data(), own->sum.data(), own->median.data(), own->minGood.data(), own->threshold.data(),
+							own->chimeric.data());
+		for (auto* v : {&own->full, &own->junction, &own->max, &own->median, &own->minGood, &own->threshold})
+			if (v->empty()) v->reserve(1);
+		if (own->sum.empty()) own->sum.reserve(1);
+		if (own->chimeric.empty()) { own->chimeric.reserve(1); own->degenerate.reserve(1); }
+	});
+	if (rc != FG_OK) { delete own; return rc; }
+	out->n_queries = n_queries;
+	out->win_off = own->winOff.data();
+	out->full = p->want_vectors ? own->full.data() : nullptr;
+	out->junction = p->want_vectors ? own->junction.data() : nullptr;
+	out->sum = own->sum.data();
+	out->max = own->max.data();
+	out->median = own->median.data();
+	out->min_good = own->minGood.data();
+	out->threshold = own->threshold.data();
+	out->chimeric = own->chimeric.data();
+	out->degenerate = own->degenerate.data();
+	out->owner_ = own;
+	return FG_OK;
+}
+
+void fg_release_coverage(struct fg_coverage_batch* b)
+{
+	if (!b) return;
+	delete (CoverageOwner*)b->owner_;
+	memset(b, 0, sizeof(*b));
+}
+
+int fg_edge_coverage(fg_ctx* c, int32_t window, const struct fg_overlap_rec* recs, uint64_t n_recs, const uint64_t* aln,
+					 const uint64_t* aln_off, uint64_t n_paths, uint32_t first_ext_id, uint32_t n_ext_ids, const uint32_t* edge_of,
+					 uint32_t n_edges, const int32_t* edge_len, uint8_t want_vectors, struct fg_edge_coverage_batch* out)
+{
+	if (!c) return FG_ERR_ARG;
+	if (out) memset(out, 0, sizeof(*out));
+	CoverageOwner* own = nullptr;
+	const int rc = guarded(c, [&]()
+	{
+		const std::string name = "fg_edge_coverage";
+		if (!out) throw FgError{FG_ERR_ARG, name + ": null result"};
+		if (window <= 0) throw FgError{FG_ERR_ARG, name + ": window must be positive"};
+		if (n_edges && !edge_len) throw FgError{FG_ERR_ARG, name + ": null edge_len"};
+		if (n_paths && !aln_off) throw FgError{FG_ERR_ARG, name + ": null aln_off"};
+		if (n_ext_ids && !edge_of) throw FgError{FG_ERR_ARG, name + ": null edge_of"};
+		for (u32 e = 0; e < n_edges; ++e)
+			if (edge_len[e] < 0) throw FgError{FG_ERR_ARG, name + ": edge " + std::to_string(e) + " has a negative length"};
+		for (u32 i = 0; i < n_ext_ids; ++i)
+			if (edge_of[i] >= n_edges)
+				throw FgError{FG_ERR_ARG, name + ": edge_of[" + std::to_string(i) + "] = " + std::to_string(edge_of[i]) + " is no edge"};
+		for (u64 k = 0; k < n_paths; ++k)
+			if (aln_off[k + 1] < aln_off[k]) throw FgError{FG_ERR_ARG, name + ": aln_off decreases at path " + std::to_string(k)};
+		const u64 a0 = n_paths ? aln_off[0] : 0, nEl = n_paths ? aln_off[n_paths] - a0 : 0;
+		if (nEl && (!aln || !recs)) throw FgError{FG_ERR_ARG, name + ": null records or alignment indices"};
+		if (nEl >= (1ULL << 30)) throw FgError{FG_ERR_ARG, name + ": more than 2^30 - 1 path elements in one call"};
+		std::vector<FgCovEdgeEl> el(nEl);
+		for (u64 k = 0; k < n_paths; ++k)
+			for (u64 i = aln_off[k]; i < aln_off[k + 1]; ++i)
+			{
+				if (aln[i] >= n_recs)
+					throw FgError{FG_ERR_ARG, name + ": aln[" + std::to_string(i) + "] = " + std::to_string(aln[i]) + " is no record"};
+				const fg_overlap_rec& r = recs[aln[i]];
+				if (r.ext_id < first_ext_id || r.ext_id - first_ext_id >= n_ext_ids)
+					throw FgError{FG_ERR_ARG, name + ": record " + std::to_string(aln[i]) + ": ext_id " + std::to_string(r.ext_id) +
+											  " has no entry in edge_of"};
+				el[i - a0] = FgCovEdgeEl{r.ext_begin, r.ext_end, edge_of[r.ext_id - first_ext_id],
+										 (i > aln_off[k] ? 1u : 0u) | (i + 1 < aln_off[k + 1] ? 2u : 0u)};
+			}
+		own = new CoverageOwner;
+		own->winOff.assign((size_t)n_edges + 1, 0);
+		for (u32 e = 0; e < n_edges; ++e) own->winOff[e + 1] = own->winOff[e] + (u64)(edge_len[e] / window);
+		if (want_vectors) own->full.resize(own->winOff[n_edges]);
+		own->sum.resize(n_edges);
+		std::vector<i32> stat(3 * (size_t)n_edges);
+		if (n_edges)
+		{
+			HIP_CHECK(hipSetDevice(c->device));
+			fgEdgeCoverage(c, window, el, own->winOff, want_vectors != 0, own->full.data(), (long long*)own->sum.data(), stat.data());
+		}
+		splitCoverageStats(stat, own->max, own->median, nullptr);
+		for (auto* v : {&own->full, &own->max, &own->median})
+			if (v->empty()) v->reserve(1);
+		if (own->sum.empty()) own->sum.reserve(1);
+	});
+	if (rc != FG_OK) { delete own; return rc; }
+	out->n_edges = n_edges;
+	out->win_off = own->winOff.data();
+	out->cov = want_vectors ? own->full.data() : nullptr;
+	out->sum = own->sum.data();
+	out->max = own->max.data();
+	out->median = own->median.data();
+	out->owner_ = own;
+	return FG_OK;
+}
+
+void fg_release_edge_coverage(struct fg_edge_coverage_batch* b)
+{
+	if (!b) return;
+	delete (CoverageOwner*)b->owner_;
+	memset(b, 0, sizeof(*b));
 }
 
 void fg_release_chains(struct fg_chain_batch* b)

@@ -428,6 +428,12 @@ struct fg_ctx {
 	DevBuf<char> dRcTab, dRcAln;
 	DevBuf<u64> dRcOff, dRcKeys, dRcOut;
 	DevBuf<i32> dRcOutScore;
+	// fg_read_coverage / fg_edge_coverage (fg_coverage.hip): a sub-batch's records (or path elements), its packed
+	// intervals (twice for the edges' sort, with the keys), the per-target offsets and sums, the per-target 32-bit
+	// arrays (clip counts, class lists, max / median / min) and the window vectors
+	DevBuf<char> dCovRecs, dCovSort;
+	DevBuf<u64> dCovIv, dCovKeys, dCovOff;
+	DevBuf<i32> dCovI32, dCovVec;
 	PinnedBuf<char> hPrim;
 	PinnedBuf<u64> hOff;
 	PinnedBuf<u64> hScalar;		// staging of the counts the host reads between kernels (pinned: no bounce buffer)
@@ -750,6 +756,18 @@ struct FgChainAln { i32 curBegin, curEnd, extBegin, extEnd, extLen, score; u32 e
 void fgChainAlignments(fg_ctx* c, const fg_chain_params& p, const std::vector<FgChainAln>& tab, const std::vector<u64>& qOff,
 					   u64 recBase, const u32* nodeLeft, const u32* nodeRight, u32 nExt, std::vector<u64>& chainOff,
 					   std::vector<u64>& alnOff, std::vector<u64>& aln, std::vector<i32>& score);
+// fg_read_coverage / fg_edge_coverage behind their argument checks (fg_coverage.hip).  Reads: recs = the caller's records
+// from query_off[0] on, qOff / winOff: n_queries + 1 offsets (from 0) of the queries' records / windows, nClip[q]: the
+// windows an interval of query q may touch (0 for a degenerate query); queries are worked on in sub-batches of
+// FG_COVERAGE_BATCH_RECS records.  Edges: one FgCovEdgeEl per path element (flags 1 = not the first of its path, 2 = not
+// the last), winOff: n_edges + 1.  full / junction / cov may be null without wantVectors; sum: one per target; stat:
+// three per target (max, median, min over the good range).  Both reset and collect the timer.
+struct FgCovEdgeEl { i32 extBegin, extEnd; u32 edge, flags; };
+void fgReadCoverage(fg_ctx* c, i32 window, i32 maxOverhang, i32 maxFlank, const fg_overlap_rec* recs, const std::vector<u64>& qOff,
+					const std::vector<u64>& winOff, const std::vector<i32>& nClip, bool wantVectors, i32* full, i32* junction,
+					long long* sum, i32* stat);
+void fgEdgeCoverage(fg_ctx* c, i32 window, const std::vector<FgCovEdgeEl>& el, const std::vector<u64>& winOff, bool wantVectors,
+					i32* cov, long long* sum, i32* stat);
 void fgDebugSortPairs(fg_ctx* c, u64* keys, u32* vals, const u64* segOff, u32 nSeg);
 void fgDebugProbeSkipCheck(fg_ctx* c, u64* clearBits, u64* violations);
 void fgDebugEditDistances(fg_ctx* c, u32 nPairs, int useHpc, i32* outDist, i32* outLenA, i32* outLenB);

@@ -45,6 +45,8 @@ ABI_SYMBOLS = ["fg_abi_version", "fg_create", "fg_destroy", "fg_strerror", "fg_l
                "fg_kernel_times", "fg_debug_sort_pairs", "fg_debug_edit_distances", "fg_align_cigar_ksw", "fg_release_cigars",
                "fg_align_ranges", "fg_trim_ranges", "fg_release_trims", "fg_edit_ranges", "fg_chain_divergence",
                "fg_chain_alignments", "fg_release_chains",
+               "fg_read_coverage", "fg_release_coverage", "fg_coverage_windows", "fg_coverage_verdict",
+               "fg_edge_coverage", "fg_release_edge_coverage",
                "fg_index_keep_targets", "fg_index_shard", "fg_probe_hits", "fg_overlaps_from_hits",
                "fg_index_piece_split", "fg_index_scatter_begin", "fg_index_scatter_end", "fg_debug_probe_skip_check",
                "fg_group_create", "fg_group_destroy", "fg_group_size", "fg_group_member", "fg_group_last_error",
@@ -127,6 +129,36 @@ class ChainBatch(C.Structure):
     _fields_ = [("n_queries", C.c_uint32), ("n_chains", C.c_uint64), ("n_alns", C.c_uint64),
                 ("chain_off", C.POINTER(C.c_uint64)), ("aln_off", C.POINTER(C.c_uint64)), ("aln", C.POINTER(C.c_uint64)),
                 ("score", C.POINTER(C.c_int32)), ("owner_", C.c_void_p)]
+
+
+class CoverageParams(C.Structure):
+    """struct fg_coverage_params: the constants of ChimeraDetector's coverage test (chimera.cpp:110, :140, :156, :168)."""
+    _fields_ = [("window", C.c_int32), ("max_overhang", C.c_int32), ("max_drop_rate", C.c_float),
+                ("overlap_coverage", C.c_int32), ("uneven_coverage", C.c_uint8), ("want_vectors", C.c_uint8),
+                ("pad_", C.c_uint8 * 2)]
+
+    @classmethod
+    def from_config(cls, cfg: dict, overlap_coverage=0, uneven_coverage=False, want_vectors=True):
+        """cfg: a preset (config.preset) or config.assemble_stage; the two keys a preset does not carry take the
+        values of asm_defaults.cfg (config.ASSEMBLE_STAGE)."""
+        from .config import ASSEMBLE_STAGE
+        return cls(window=int(cfg.get("chimera_window", ASSEMBLE_STAGE["chimera_window"])), max_overhang=int(cfg["maximum_overhang"]),
+                   max_drop_rate=float(cfg.get("max_coverage_drop_rate", ASSEMBLE_STAGE["max_coverage_drop_rate"])),
+                   overlap_coverage=int(overlap_coverage),
+                   uneven_coverage=int(bool(uneven_coverage)), want_vectors=int(bool(want_vectors)))
+
+
+class CoverageBatch(C.Structure):
+    _fields_ = [("n_queries", C.c_uint32), ("win_off", C.POINTER(C.c_uint64)), ("full", C.POINTER(C.c_int32)),
+                ("junction", C.POINTER(C.c_int32)), ("sum", C.POINTER(C.c_int64)), ("max", C.POINTER(C.c_int32)),
+                ("median", C.POINTER(C.c_int32)), ("min_good", C.POINTER(C.c_int32)), ("threshold", C.POINTER(C.c_int32)),
+                ("chimeric", C.POINTER(C.c_uint8)), ("degenerate", C.POINTER(C.c_uint8)), ("owner_", C.c_void_p)]
+
+
+class EdgeCoverageBatch(C.Structure):
+    _fields_ = [("n_edges", C.c_uint32), ("win_off", C.POINTER(C.c_uint64)), ("cov", C.POINTER(C.c_int32)),
+                ("sum", C.POINTER(C.c_int64)), ("max", C.POINTER(C.c_int32)), ("median", C.POINTER(C.c_int32)),
+                ("owner_", C.c_void_p)]
 
 
 class BridgeStats(C.Structure):
@@ -231,6 +263,19 @@ def load_library():
                                           C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(ChainBatch)]
         L.fg_release_chains.argtypes = [C.POINTER(ChainBatch)]
         L.fg_release_chains.restype = None
+        L.fg_read_coverage.argtypes = [C.c_void_p, C.POINTER(CoverageParams), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                       C.POINTER(CoverageBatch)]
+        L.fg_release_coverage.argtypes = [C.POINTER(CoverageBatch)]
+        L.fg_release_coverage.restype = None
+        L.fg_coverage_windows.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                          C.POINTER(C.c_uint8)]
+        L.fg_coverage_verdict.argtypes = [C.POINTER(CoverageParams), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]
+        L.fg_edge_coverage.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                       C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint8,
+                                       C.POINTER(EdgeCoverageBatch)]
+        L.fg_release_edge_coverage.argtypes = [C.POINTER(EdgeCoverageBatch)]
+        L.fg_release_edge_coverage.restype = None
         L.fg_debug_group_bin_cuts.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         L.fg_debug_freq_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
         L.fg_debug_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int]
@@ -417,6 +462,50 @@ def chain_divergence(cur_range, divergence, chain_off):
     if rc != 0:
         raise FlyeGpuError(rc, L.fg_strerror(rc).decode())
     return out
+
+
+def coverage_windows(seq_len, window, max_overhang):
+    """fg_coverage_windows: (windows of the coverage vector of a sequence of seq_len bases -- chimera.cpp:114-117, at
+    least 1 --, MAX_FLANK of :168-169, whether the vector is the degenerate {0})."""
+    n, flank, deg = C.c_int32(), C.c_int32(), C.c_uint8()
+    L = load_library()
+    rc = L.fg_coverage_windows(int(seq_len), int(window), int(max_overhang), C.byref(n), C.byref(flank), C.byref(deg))
+    if rc != 0:
+        raise FlyeGpuError(rc, L.fg_strerror(rc).decode())
+    return n.value, flank.value, bool(deg.value)
+
+
+def coverage_verdict(params, n_windows, sums, median, min_good):
+    """fg_coverage_verdict: testReadByCoverage's threshold and return value (chimera.cpp:153-182) per vector, from its
+    size, sum, median and the minimum over its good range.  Returns (threshold int32, chimeric bool)."""
+    nw = np.ascontiguousarray(n_windows, np.int32)
+    sm = np.ascontiguousarray(sums, np.int64)
+    md = np.ascontiguousarray(median, np.int32)
+    mg = np.ascontiguousarray(min_good, np.int32)
+    n = len(nw)
+    if not (len(sm) == len(md) == len(mg) == n):
+        raise ValueError("coverage_verdict: one value of each kind per vector")
+    thr = np.zeros(n, np.int32)
+    chim = np.zeros(n, np.uint8)
+    L = load_library()
+    rc = L.fg_coverage_verdict(C.byref(params), n, *(a.ctypes.data if n else None for a in (nw, sm, md, mg, thr, chim)))
+    if rc != 0:
+        raise FlyeGpuError(rc, L.fg_strerror(rc).decode())
+    return thr, chim.astype(bool)
+
+
+class ReadCoverage:
+    """fg_coverage_batch copied out of its arena: win_off (n + 1), full / junction (None without want_vectors) and one
+    value per query of sum, max, median, min_good, threshold, chimeric, degenerate."""
+
+    def __init__(self, **arrays):
+        self.__dict__.update(arrays)
+
+    def full_of(self, q):
+        return self.full[int(self.win_off[q]):int(self.win_off[q + 1])]
+
+    def junction_of(self, q):
+        return self.junction[int(self.win_off[q]):int(self.win_off[q + 1])]
 
 
 class Context:
@@ -655,6 +744,69 @@ class Context:
                np.ctypeslib.as_array(b.aln, (na,)).copy() if na else np.zeros(0, np.uint64),
                np.ctypeslib.as_array(b.score, (nc,)).copy() if nc else np.zeros(0, np.int32))
         self.L.fg_release_chains(C.byref(b))
+        return out
+
+    def read_coverage(self, recs, query_off, query_len, params):
+        """fg_read_coverage: the window coverage of ChimeraDetector::getReadCoverage / getCachedCoverage
+        (chimera.cpp:106-134, :280-343) and testReadByCoverage's values (:137-202) for the per-read lists
+        recs[query_off[q]:query_off[q + 1]] (REC_DTYPE, any order) of reads of query_len[q] bases.  Returns a
+        ReadCoverage of numpy arrays."""
+        r = np.ascontiguousarray(recs, REC_DTYPE)
+        off = np.ascontiguousarray(query_off, np.uint64)
+        ln = np.ascontiguousarray(query_len, np.int32)
+        if len(off) != len(ln) + 1 or (len(off) > 1 and int(off.max()) > len(r)):
+            raise ValueError("read_coverage: one length per query, offsets inside the records")
+        nq = len(ln)
+        b = CoverageBatch()
+        t0 = time.perf_counter()
+        self._check(self.L.fg_read_coverage(self.h, C.byref(params), r.ctypes.data if len(r) else None, off.ctypes.data, nq,
+                                            ln.ctypes.data if nq else None, C.byref(b)))
+        self.last_coverage_seconds = time.perf_counter() - t0
+
+        def take(ptr, n, dtype):
+            return np.ctypeslib.as_array(ptr, (n,)).copy() if n else np.zeros(0, dtype)
+
+        win_off = np.ctypeslib.as_array(b.win_off, (nq + 1,)).copy()
+        nw = int(win_off[nq])
+        vec = bool(params.want_vectors)
+        out = ReadCoverage(win_off=win_off, full=take(b.full, nw, np.int32) if vec else None,
+                           junction=take(b.junction, nw, np.int32) if vec else None, sum=take(b.sum, nq, np.int64),
+                           max=take(b.max, nq, np.int32), median=take(b.median, nq, np.int32),
+                           min_good=take(b.min_good, nq, np.int32), threshold=take(b.threshold, nq, np.int32),
+                           chimeric=take(b.chimeric, nq, np.uint8).astype(bool),
+                           degenerate=take(b.degenerate, nq, np.uint8).astype(bool))
+        self.L.fg_release_coverage(C.byref(b))
+        return out
+
+    def edge_coverage(self, window, recs, aln, aln_off, first_ext_id, edge_of, edge_len, want_vectors=True):
+        """fg_edge_coverage: the window coverage of MultiplicityInferer::estimateCoverage (multiplicity_inferer.cpp:
+        14-41) for the paths recs[aln[aln_off[p]:aln_off[p + 1]]] (the layout chain_alignments returns).  edge_of[i]: the
+        edge of indexed sequence first_ext_id + i; edge_len[e]: GraphEdge::length().  Returns (win_off, cov or None, sum,
+        max, median) with one value per edge."""
+        r = np.ascontiguousarray(recs, REC_DTYPE)
+        a = np.ascontiguousarray(aln, np.uint64)
+        off = np.ascontiguousarray(aln_off, np.uint64)
+        eo = np.ascontiguousarray(edge_of, np.uint32)
+        el = np.ascontiguousarray(edge_len, np.int32)
+        if len(off) < 1 or (len(off) > 1 and int(off.max()) > len(a)):
+            raise ValueError("edge_coverage: offsets inside the alignment indices")
+        ne = len(el)
+        b = EdgeCoverageBatch()
+        t0 = time.perf_counter()
+        self._check(self.L.fg_edge_coverage(self.h, int(window), r.ctypes.data if len(r) else None, len(r),
+                                            a.ctypes.data if len(a) else None, off.ctypes.data, len(off) - 1, int(first_ext_id),
+                                            len(eo), eo.ctypes.data if len(eo) else None, ne, el.ctypes.data if ne else None,
+                                            int(bool(want_vectors)), C.byref(b)))
+        self.last_coverage_seconds = time.perf_counter() - t0
+        win_off = np.ctypeslib.as_array(b.win_off, (ne + 1,)).copy()
+        nw = int(win_off[ne])
+
+        def take(ptr, n, dtype):
+            return np.ctypeslib.as_array(ptr, (n,)).copy() if n else np.zeros(0, dtype)
+
+        out = (win_off, take(b.cov, nw, np.int32) if want_vectors else None, take(b.sum, ne, np.int64), take(b.max, ne, np.int32),
+               take(b.median, ne, np.int32))
+        self.L.fg_release_edge_coverage(C.byref(b))
         return out
 
     def align_reads(self, detector_params, query_ids, chain_params, node_left, node_right, max_divergence, realign=False,
@@ -1256,6 +1408,112 @@ class OverlapContainer:
         base = np.float32(self._mean_true_ovlp_div) if isRelative else np.float32(0.0)
         self.det.p.max_divergence = float(base + np.float32(threshold))
         return self.det.p.max_divergence
+
+
+class ChimeraDetector:
+    """Mirror of reference ChimeraDetector (src/assemble/chimera.cpp:31-343) on fg_read_coverage.
+
+    The reference tests one read at a time from its worker threads; ``classify`` is the batched form (one prefetch
+    plus one device call), ``isChimeric`` serves single reads from its cache as ``_chimeras`` does."""
+
+    def __init__(self, ctx: Context, ovlpContainer: OverlapContainer, cfg: dict, uneven_coverage: bool):
+        self.ctx, self.ovlp, self.cfg = ctx, ovlpContainer, cfg
+        self.uneven_coverage = bool(uneven_coverage)
+        self._overlapCoverage = 0
+        self._chimeras = {}
+        self._cached = {}
+
+    def _params(self, want_vectors):
+        return CoverageParams.from_config(self.cfg, self._overlapCoverage, self.uneven_coverage, want_vectors)
+
+    def _seq_len(self, readId):
+        return int(self.ctx.rs.length[(int(readId) - self.ctx.first_id) >> 1])
+
+    def _coverage(self, readIds, want_vectors):
+        """one prefetch and one device call over the lazySeqOverlaps records of readIds"""
+        ids = [int(r) for r in readIds]
+        self.ovlp.prefetch(ids)
+        lists = [self.ovlp.lazySeqOverlaps(r) for r in ids]
+        off = np.zeros(len(ids) + 1, np.uint64)
+        off[1:] = np.cumsum([len(x) for x in lists])
+        recs = np.concatenate(lists) if lists else np.zeros(0, REC_DTYPE)
+        return self.ctx.read_coverage(recs, off, [self._seq_len(r) for r in ids], self._params(want_vectors))
+
+    def getReadCoverage(self, readId):
+        """chimera.cpp:106-134"""
+        return self._coverage([readId], True).full_of(0)
+
+    def classify(self, readIds):
+        """testReadByCoverage (:137-202) of every read of readIds in one device call; both strands are cached
+        (:49-50).  Returns a bool array."""
+        ids = [int(r) for r in readIds]
+        todo = sorted({r for r in ids if r not in self._chimeras})
+        if todo:
+            res = self._coverage(todo, False)
+            for r, v in zip(todo, res.chimeric.tolist()):
+                if r not in self._chimeras:         # the first verdict of a pair stands, as in the reference
+                    self._chimeras[r] = v
+                    self._chimeras[r ^ 1] = v
+        return np.array([self._chimeras[r] for r in ids], bool)
+
+    def testReadByCoverage(self, readId):
+        return bool(self._coverage([readId], False).chimeric[0])
+
+    def isChimeric(self, readId):
+        """:31-53"""
+        return bool(self.classify([readId])[0])
+
+    def estimateGlobalCoverage(self, libc_rand=None):
+        """:55-104: rand() % sampleRate per sequence in container order over both strands, the coverage of the picked
+        ones in one device call, the pooled median of the vectors with a non-zero window."""
+        if libc_rand is None:
+            libc = C.CDLL(None)
+            libc.rand.restype = C.c_int
+            libc_rand = libc.rand
+        n_seqs = 2 * self.ctx.n_reads
+        num_samples = min(1000, n_seqs)
+        if not num_samples:
+            self._overlapCoverage = 0
+            return 0
+        sample_rate = n_seqs // num_samples
+        picks = [self.ctx.first_id + i for i in range(n_seqs) if libc_rand() % sample_rate == 0]
+        res = self._coverage(picks, True)
+        pooled = [res.full_of(q) for q in range(len(picks)) if res.max[q] != 0]
+        if not pooled:
+            self._overlapCoverage = 0
+        else:
+            v = np.sort(np.concatenate(pooled))
+            self._overlapCoverage = int(v[min(len(v) * 50 // 100, len(v) - 1)])      # utils.h median()
+        return self._overlapCoverage
+
+    def getCachedCoverage(self, readId):
+        """:280-343: (coverageFullAln, coverageIncomleteAln) from force-local overlaps"""
+        readId = int(readId)
+        if readId not in self._cached:
+            recs = self.ovlp.quickSeqOverlaps(readId, 0, True)
+            res = self.ctx.read_coverage(recs, [0, len(recs)], [self._seq_len(readId)], self._params(True))
+            if res.degenerate[0]:
+                raise RuntimeError("Zero-sized coverage vector")
+            self._cached[readId] = (res.full_of(0), res.junction_of(0))
+        return self._cached[readId]
+
+    def isRepetitiveRegion(self, readId, start, end):
+        """:204-278, in float32 as written there"""
+        HANG_END_RATE = np.float32(0.75)
+        REPEAT_WINDOW_RATE = np.float32(0.75)
+        window = self._params(True).window
+        coverage, junctions = self.getCachedCoverage(readId)
+        cdiv = lambda a: abs(int(a)) // window * (1 if a >= 0 else -1)      # C's division truncates
+        lo = max(0, cdiv(start))
+        hi = min(len(coverage), cdiv(end))
+        num_suspicious = range_len = 0
+        for pos in range(lo, hi):
+            if HANG_END_RATE * np.float32(coverage[pos]) <= np.float32(junctions[pos]):
+                num_suspicious += 1
+            range_len += 1
+        if range_len == 0:
+            return False
+        return bool(np.float32(num_suspicious) / np.float32(range_len) > REPEAT_WINDOW_RATE)
 
 
 class BatchingOverlapContainer:

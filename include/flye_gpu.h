@@ -606,6 +606,99 @@ int fg_chain_alignments(fg_ctx* ctx, const struct fg_chain_params* p,
                         struct fg_chain_batch* out);
 void fg_release_chains(struct fg_chain_batch* b);
 
+/* Window coverage of a read by its overlaps, and what ChimeraDetector reads off it (src/assemble/chimera.cpp:31-343).
+ * One pass serves getReadCoverage (:106-134) and getCachedCoverage (:280-343): recs[query_off[q] .. query_off[q + 1])
+ * are the overlap records of query q, in any order.  A record with ext_id == cur_id or ext_id == (cur_id ^ 1) is
+ * skipped (:120-121).  Every other one adds 1 to the windows cur_begin / window .. cur_end / window - 2 inclusive
+ * (:125-130 with FLANK = 1; nothing when the upper bound is below the lower) of `full` when lrOverhang() =
+ * max(min(cur_begin, ext_begin), min(cur_len - cur_end, ext_len - ext_end)) (overlap.h:195-199) <= max_overhang, of
+ * `junction` otherwise.  `full` over lazySeqOverlaps records is getReadCoverage's vector -- IterNoOverhang
+ * (overlap.h:456-523) drops exactly the records that land in `junction`; `full` and `junction` over
+ * quickSeqOverlaps(id, 0, force_local = true) records are getCachedCoverage's two vectors (:302-322).
+ * Windows of a query: fg_coverage_windows below (the reference's float expression; a query of n <= 0 windows has one
+ * window holding 0 and degenerate = 1).  sum / max / median / min_good are taken of `full` (:145-152, :166-182);
+ * threshold and chimeric are fg_coverage_verdict's, computed on the host from those integers: no float runs on the
+ * device.  Windows past the vector's end (the reference's .at() would throw; reachable only where (float)cur_len
+ * rounds down, above 2^24 bp) are not counted.
+ * The context lends its device and stream: no reads and no index are needed.  Queries are worked on in sub-batches of
+ * FG_COVERAGE_BATCH_RECS records (environment, default 2^20; a longer query runs alone); fg_kernel_times afterwards
+ * reports the sums over them.  FG_COVERAGE_TILE (windows per LDS tile, 64 .. 2048) and FG_COVERAGE_WAVE_MAX (the largest
+ * window count a single wave takes, 0 .. 512; 0: every query takes a workgroup) are switches for tests.
+ * FG_ERR_ARG, found before any device work: NULL p or out; NULL recs, query_off or query_len with something to read; a
+ * decreasing query_off; window <= 0, max_overhang < 0, !(max_drop_rate > 0) or query_len[q] < 0; a record with
+ * cur_len != query_len[q], cur_begin < 0, cur_end < cur_begin, cur_end > cur_len, ext_begin < 0, ext_end < ext_begin
+ * or ext_end > ext_len.  n_queries = 0 gives an empty batch (win_off = {0}). */
+struct fg_coverage_params {
+	int32_t window;            /* Config "chimera_window"            (chimera.cpp:110, :294) */
+	int32_t max_overhang;      /* Config "maximum_overhang"          (overlap.h:467, chimera.cpp:168, :295) */
+	float   max_drop_rate;     /* Config "max_coverage_drop_rate"    (chimera.cpp:140) */
+	int32_t overlap_coverage;  /* ChimeraDetector::_overlapCoverage; read when uneven_coverage == 0 */
+	uint8_t uneven_coverage;   /* Parameters::get().unevenCoverage   (chimera.cpp:156) */
+	uint8_t want_vectors;      /* 0: only the per-read values come back */
+	uint8_t pad_[2];
+};
+struct fg_coverage_batch {
+	uint32_t  n_queries;
+	uint64_t* win_off;     /* n_queries + 1: windows of query q = win_off[q+1] - win_off[q] (always >= 1) */
+	int32_t*  full;        /* want_vectors: records with lrOverhang() <= max_overhang */
+	int32_t*  junction;    /* want_vectors: records with lrOverhang() >  max_overhang */
+	int64_t*  sum;         /* of full   (sumCov, chimera.cpp:146-151) */
+	int32_t*  max;         /* of full   (maxCov) */
+	int32_t*  median;      /* of full   (utils.h:32-51: sorted[min(n * 50 / 100, n - 1)]) */
+	int32_t*  min_good;    /* min of full[max_flank .. n - max_flank - 1]; INT32_MAX when that range is empty */
+	int32_t*  threshold;   /* chimera.cpp:155-164 */
+	uint8_t*  chimeric;    /* testReadByCoverage's return value */
+	uint8_t*  degenerate;  /* 1: numWindows - 2 <= 0 -- getReadCoverage returns {0}, getCachedCoverage throws */
+	void*     owner_;
+};
+int  fg_read_coverage(fg_ctx* ctx, const struct fg_coverage_params* p, const struct fg_overlap_rec* recs,
+                      const uint64_t* query_off, uint32_t n_queries, const int32_t* query_len,
+                      struct fg_coverage_batch* out);
+void fg_release_coverage(struct fg_coverage_batch* b);
+
+/* The two float steps of the above; host only, no context.
+ * fg_coverage_windows: numWindows = std::ceil((float)seq_len / window) + 1 in single precision, converted to int
+ * (chimera.cpp:114, :298 -- (float)seq_len rounds above 2^24 bp; this is the only place the expression is written);
+ * n = numWindows - 2; *n_windows = n, or 1 with *degenerate = 1 when n <= 0 (:115); *max_flank =
+ * (int)((float)max_overhang / (float)window) (:168-169).  Any of the three pointers may be NULL.  FG_ERR_ARG for
+ * seq_len < 0, window <= 0 or max_overhang < 0.
+ * fg_coverage_verdict: testReadByCoverage's decision (:153-182) for n vectors from their integers: chimeric = 1 and
+ * threshold = 0 when sum == 0; otherwise threshold = (int)std::max(1L, std::lround(x / max_drop_rate)) with x =
+ * (float)overlap_coverage, or the median converted to float when uneven_coverage is set; good_start = max_flank,
+ * good_end = n_windows - max_flank - 1, chimeric = good_end <= good_start || min_good < threshold.  threshold may be
+ * NULL.  FG_ERR_ARG for NULL p, a NULL array with n > 0, window <= 0, max_overhang < 0 or !(max_drop_rate > 0). */
+int fg_coverage_windows(int32_t seq_len, int32_t window, int32_t max_overhang, int32_t* n_windows, int32_t* max_flank,
+                        uint8_t* degenerate);
+int fg_coverage_verdict(const struct fg_coverage_params* p, uint32_t n, const int32_t* n_windows, const int64_t* sum,
+                        const int32_t* median, const int32_t* min_good, int32_t* threshold, uint8_t* chimeric);
+
+/* Window coverage of the graph edges by the read paths: the first half of MultiplicityInferer::estimateCoverage
+ * (src/repeat_graph/multiplicity_inferer.cpp:14-41) and the median of :63.  Path p is aln[aln_off[p] .. aln_off[p + 1]),
+ * indices into recs (n_recs of them), front of the path first: the layout of fg_chain_batch.  edge_of[i] is the
+ * caller's edge number of indexed sequence first_ext_id + i, edge_len[e] its GraphEdge::length()
+ * (repeat_graph.h:118-128); edge e has size = edge_len[e] / window windows (integer division; may be 0).  Position j
+ * of a path of m alignments adds 1 to the windows [from, to) of its edge, from = (j > 0) ? 0 : max(0, ext_begin /
+ * window + 1), to = (j < m - 1) ? size : min(size, ext_end / window) (:32-39); nothing when from >= to.  Per edge: the
+ * vector (want_vectors), its sum, max and median (0 for an empty vector, utils.h:34).  _meanCoverage, the
+ * complement-edge average and the quantile of :43-88 are a few integer operations over these and stay with the
+ * caller.  One call is one device batch (at most 2^30 - 1 path elements); the context lends its device and stream.
+ * FG_ERR_ARG, found before any device work: NULL out; window <= 0; an aln index >= n_recs; an ext_id outside
+ * [first_ext_id, first_ext_id + n_ext_ids); edge_of[i] >= n_edges; edge_len[e] < 0; a decreasing aln_off; a NULL
+ * array where something must be read.  n_edges = 0 gives an empty batch (win_off = {0}). */
+struct fg_edge_coverage_batch {
+	uint32_t  n_edges;
+	uint64_t* win_off;     /* n_edges + 1: edge_len[e] / window windows (integer division; may be 0) */
+	int32_t*  cov;         /* want_vectors */
+	int64_t*  sum; int32_t* max; int32_t* median;   /* median of an empty vector is 0 (utils.h:34) */
+	void*     owner_;
+};
+int  fg_edge_coverage(fg_ctx* ctx, int32_t window, const struct fg_overlap_rec* recs, uint64_t n_recs,
+                      const uint64_t* aln, const uint64_t* aln_off, uint64_t n_paths,
+                      uint32_t first_ext_id, uint32_t n_ext_ids, const uint32_t* edge_of,
+                      uint32_t n_edges, const int32_t* edge_len, uint8_t want_vectors,
+                      struct fg_edge_coverage_batch* out);
+void fg_release_edge_coverage(struct fg_edge_coverage_batch* b);
+
 #ifdef __cplusplus
 }
 #endif
