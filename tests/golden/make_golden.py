@@ -1,7 +1,7 @@
 """Generates tests/golden/*.  Run in the build container (needs /root/reference
 and oracle/_ref/ref_dumper, see oracle/Makefile):
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py [case names ...]
 
 Each case = seeded simulator parameters (inputs are regenerated from the seed, not
 stored) + what the UNMODIFIED reference (Flye 2.8.1 compiled from /root/reference)
@@ -102,6 +102,33 @@ CASES = [
                   max_len=30000, n_repeat_families=8, n_homopolymers=40),
          min_read_len=0, min_overlap=1000, only_max=False, max_overhang=0, nucl_aln=True, minimizer_index=True,
          keep_aln=True, max_div=0.015),
+    # k-mer sizes other than 17: the wide lookup table (k >= 18), the subassembly preset (k = 31, its own cfg
+    # file) and the counter below 17.  ``kmer_size`` overrides the preset's value (--params kmer_size=N); the
+    # tandem repeats make some k-mers repetitive at these widths too (index.repetitive_kmers > 0).
+    dict(name="subasm", preset="subasm",
+         sim=dict(seed=201, genome_len=30_000, coverage=20, kind="hifi", n_tandems=40, n_repeat_families=6),
+         min_read_len=1000),
+    dict(name="subasm_rc_max", preset="subasm",
+         sim=dict(seed=202, genome_len=30_000, coverage=20, kind="hifi03", n_tandems=20, n_homopolymers=20),
+         min_read_len=1000, rc_queries=True, max_overlaps=20),
+    dict(name="corrected_k18", preset="corrected", kmer_size=18,
+         sim=dict(seed=203, genome_len=30_000, coverage=20, kind="hifi03", n_tandems=20, n_homopolymers=10),
+         min_read_len=1000),
+    dict(name="raw_k15", preset="raw", kmer_size=15,
+         sim=dict(seed=204, genome_len=30_000, coverage=20, kind="pb_raw"),
+         min_read_len=1000),
+    dict(name="edges_subasm_aln", preset="subasm",
+         sim=dict(seed=205, genome_len=40_000, coverage=4, kind="hifi03", median_len=20000, min_len=8000,
+                  max_len=30000, read_seed=7, n_repeat_families=6, n_tandems=8),
+         queries_sim=dict(seed=205, genome_len=40_000, coverage=8, kind="hifi", read_seed=9, n_repeat_families=6,
+                          n_tandems=8),
+         min_read_len=0, min_overlap=1000, only_max=False, max_overhang=0, nucl_aln=False, minimizer_index=True,
+         keep_aln=True),
+    dict(name="repeat_subasm", preset="subasm",
+         sim=dict(seed=206, genome_len=40_000, coverage=4, kind="hifi03", median_len=15000, min_len=6000,
+                  max_len=30000, n_repeat_families=8),
+         min_read_len=0, min_overlap=1000, only_max=False, max_overhang=0, nucl_aln=True, minimizer_index=True,
+         keep_aln=True, max_div=0.03),
 ]
 
 
@@ -125,11 +152,13 @@ def main():
             fa = os.path.join(tmp, "reads.fasta")
             rs = synth.simulate(fasta_path=fa, **case["sim"]).filter_min_len(case["min_read_len"])
             extra = {}
-            params = None
+            params = []
+            if "kmer_size" in case:
+                params.append(f"kmer_size={int(case['kmer_size'])}")
             if case.get("minimizer_index"):
                 cfgd = config.preset(case["preset"])
                 wnd = int(cfgd["minimizer_window"]) if cfgd["use_minimizers"] else 1
-                params = f"use_minimizers=1,minimizer_window={wnd}"     # read_aligner.cpp:180-182
+                params.append(f"use_minimizers=1,minimizer_window={wnd}")     # read_aligner.cpp:180-182
                 extra = dict(only_max=case["only_max"], max_overhang=case["max_overhang"],
                              nucl_aln=case["nucl_aln"], min_overlap=case["min_overlap"])
                 if "max_div" in case:
@@ -138,7 +167,7 @@ def main():
                     qfa = os.path.join(tmp, "queries.fasta")
                     synth.simulate(fasta_path=qfa, **case["queries_sim"])
                     extra["queries_fasta"] = qfa
-            info = O.run_ref(fa, config=CFG_DIR + config.CFG_FILES[case["preset"]], params_string=params, threads=8,
+            info = O.run_ref(fa, config=CFG_DIR + config.CFG_FILES[case["preset"]], params_string=",".join(params) or None, threads=8,
                              min_read_len=case["min_read_len"], max_overlaps=case.get("max_overlaps", 0),
                              force_local=case.get("force_local", False),
                              div_mode=case.get("div_mode", "none"),

@@ -16,6 +16,15 @@ def golden_reads(case):
     return rs
 
 
+def case_config(case):
+    """The preset of a golden case with the case's own ``kmer_size`` where it carries one (make_golden.py passes
+    it to the reference as --params kmer_size=N)."""
+    from flye_amd import config
+    cfg = config.preset(case["preset"])
+    cfg["kmer_size"] = float(int(case.get("kmer_size", cfg["kmer_size"])))
+    return cfg
+
+
 def golden_lines(name):
     with gzip.open(os.path.join(GOLDEN, name + ".ovlp.gz"), "rt") as f:
         return [l.strip() for l in f if l.strip() and not l.startswith("#")]

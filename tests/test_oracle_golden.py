@@ -2,19 +2,24 @@
 the compiled, unmodified reference (tests/golden/make_golden.py)."""
 import pytest
 
-from helpers import (bits_to_float, case_queries, check_index_stats, golden_lines, golden_reads,
+from helpers import (bits_to_float, case_config, case_queries, check_index_stats, golden_lines, golden_reads,
                      index_digest)
 
-CASES = ["raw_pb", "raw_ont_rc", "raw_div", "raw_local", "hifi", "corrected_local", "hifi_rc_max", "raw_pb_aln"]
+CASES = ["raw_pb", "raw_ont_rc", "raw_div", "raw_local", "hifi", "corrected_local", "hifi_rc_max", "raw_pb_aln",
+         "subasm", "subasm_rc_max", "corrected_k18", "raw_k15"]
+# k-mer sizes other than 17 (tests/test_kmer_sizes.py runs the same vectors through the device)
+KMER_CASES = {"subasm": 31, "subasm_rc_max": 31, "corrected_k18": 18, "raw_k15": 15, "edges_subasm_aln": 31,
+              "repeat_subasm": 31}
+# the wide lookup table's "repetitive" marker is only reached where the index has repetitive k-mers
+REPETITIVE_CASES = ["subasm", "subasm_rc_max", "corrected_k18"]
 
 
 @pytest.mark.parametrize("name", CASES)
 def test_oracle_matches_reference_golden(built, golden_cases, name):
-    from flye_amd import config
     from oracle import oracle as O
     case = golden_cases[name]
     rs = golden_reads(case)
-    cfg = config.preset(case["preset"])
+    cfg = case_config(case)
     o = O.Oracle(int(cfg["kmer_size"]))
     o.set_reads(rs)
     st = o.build_index(cfg)
@@ -26,20 +31,33 @@ def test_oracle_matches_reference_golden(built, golden_cases, name):
                      force_local=case.get("force_local", False))
     assert res.lines() == golden_lines(name)
     assert len(res.recs) == case["n_overlaps"]
+    if name in KMER_CASES:
+        assert len(res.recs) > 0
 
 
-@pytest.mark.parametrize("name", ["edges_raw", "edges_hifi", "edges_raw_max", "edges_raw_aln", "edges_hifi_aln"])
+@pytest.mark.parametrize("name", sorted(KMER_CASES))
+def test_kmer_size_cases_reach_what_they_are_for(golden_cases, name):
+    """What the reference itself reported for the cases at other k-mer sizes: the width, overlaps, and -- where the
+    case is there for it -- repetitive k-mers."""
+    case = golden_cases[name]
+    assert int(case_config(case)["kmer_size"]) == KMER_CASES[name]
+    assert case["n_overlaps"] > 0 and case["index"]["index_entries"] > 0
+    if name in REPETITIVE_CASES:
+        assert case["index"]["repetitive_kmers"] > 0
+
+
+@pytest.mark.parametrize("name", ["edges_raw", "edges_hifi", "edges_raw_max", "edges_raw_aln", "edges_hifi_aln",
+                                  "edges_subasm_aln"])
 def test_oracle_read_aligner_style_golden(built, golden_cases, name):
     """Queries from a second container against an index of other sequences, all primaries
     (ReadAligner::alignReads flags), vs the reference's output."""
     import numpy as np
-    from flye_amd import config
     from oracle import oracle as O
     from helpers import edges_setup, golden_queries
     case = golden_cases[name]
     edges = golden_reads(case)
     reads = golden_queries(case)
-    cfg = config.preset(case["preset"])
+    cfg = case_config(case)
     wnd, dk = edges_setup(case, cfg)
     o = O.Oracle(int(cfg["kmer_size"]))
     o.set_reads(edges, 0)
@@ -53,17 +71,16 @@ def test_oracle_read_aligner_style_golden(built, golden_cases, name):
     assert len(res.recs) == case["n_overlaps"] > 0
 
 
-@pytest.mark.parametrize("name", ["repeat_raw", "repeat_hifi"])
+@pytest.mark.parametrize("name", ["repeat_raw", "repeat_hifi", "repeat_subasm"])
 def test_oracle_repeat_stage_golden(built, golden_cases, name):
     """RepeatGraph::build flags: sequences against themselves, every primary, kmerMatches kept,
     base-level divergence; gated-out primaries returned marked (partition_bad_mappings)."""
     import numpy as np
-    from flye_amd import config
     from oracle import oracle as O
     from helpers import check_repeat_stage_result, repeat_stage_setup
     case = golden_cases[name]
     seqs = golden_reads(case)
-    cfg = config.preset(case["preset"])
+    cfg = case_config(case)
     wnd, dk = repeat_stage_setup(case, cfg)
     o = O.Oracle(int(cfg["kmer_size"]))
     o.set_reads(seqs, 0)
