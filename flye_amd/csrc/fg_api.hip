@@ -1160,6 +1160,161 @@ void fg_release_edge_coverage(struct fg_edge_coverage_batch* b)
 	memset(b, 0, sizeof(*b));
 }
 
+namespace {
+struct PolishOwner {
+	std::vector<uint8_t> cand, status, stepSeq;
+	std::vector<uint64_t> candOff, stepOff, stepSeqOff;
+	std::vector<uint32_t> nSteps;
+	std::vector<int64_t> stepScore;
+};
+int polishLetter(const std::string& item, bool last)
+{
+	if (item.empty()) return -1;
+	switch (last ? item[item.size() - 1] : item[0])
+	{
+	case 'A': return 0;
+	case 'C': return 1;
+	case 'G': return 2;
+	case 'T': return 3;
+	default: return -1;
+	}
+}
+}
+
+int fg_subs_matrix_load(const char* path, struct fg_subs_matrix* out)
+{
+	if (!path || !out) return FG_ERR_ARG;
+	memset(out, 0, sizeof(*out));
+	FILE* f = fopen(path, "rb");
+	if (!f) return FG_ERR_ARG;
+	std::string text;
+	char buf[4096];
+	size_t got;
+	while ((got = fread(buf, 1, sizeof(buf), f)) > 0) text.append(buf, got);
+	fclose(f);
+	size_t at = 0;
+	while (at < text.size())
+	{
+		size_t end = text.find('\n', at);
+		if (end == std::string::npos) end = text.size();
+		std::string line = text.substr(at, end - at);
+		at = end + 1;
+		if (!line.empty() && line[line.size() - 1] == '\r') line.pop_back();
+		std::vector<std::string> items;
+		size_t a = 0;
+		for (;;)
+		{
+			const size_t t = line.find('\t', a);
+			items.push_back(line.substr(a, t == std::string::npos ? t : t - a));
+			if (t == std::string::npos) break;
+			a = t + 1;
+		}
+		const std::string& kind = items[0];
+		if (kind != "mat" && kind != "mis" && kind != "del" && kind != "ins") continue;
+		if (items.size() < 3) return FG_ERR_ARG;
+		const int x = polishLetter(items[1], false), y = polishLetter(items[1], true);
+		if (x < 0 || (kind == "mis" && y < 0)) return FG_ERR_ARG;
+		char* stop = nullptr;
+		const double p = strtod(items[2].c_str(), &stop);
+		if (stop == items[2].c_str()) return FG_ERR_ARG;
+		const int64_t sc = (int64_t)std::round(std::log(p) * 131072.0);
+		if (kind == "mat") out->score[x][x] = sc;
+		else if (kind == "mis") out->score[x][y] = sc;
+		else if (kind == "del") out->score[x][5] = sc;
+		else out->score[5][x] = sc;
+	}
+	return FG_OK;
+}
+
+int fg_polish_bubbles(fg_ctx* c, const struct fg_subs_matrix* matrix, const uint8_t* cand, const uint64_t* cand_off,
+					  const uint8_t* branches, const uint64_t* branch_off, const uint64_t* bubble_branch_off, uint32_t n_bubbles,
+					  uint8_t fix_dinucleotides, uint8_t want_steps, struct fg_polish_batch* out)
+{
+	if (!c) return FG_ERR_ARG;
+	if (out) memset(out, 0, sizeof(*out));
+	PolishOwner* own = nullptr;
+	const int rc = guarded(c, [&]()
+	{
+		const std::string name = "fg_polish_bubbles";
+		if (!matrix || !out) throw FgError{FG_ERR_ARG, name + ": null matrix or result"};
+		if (n_bubbles && (!cand_off || !bubble_branch_off)) throw FgError{FG_ERR_ARG, name + ": null cand_off or bubble_branch_off"};
+		for (u32 i = 0; i < n_bubbles; ++i)
+		{
+			if (cand_off[i + 1] < cand_off[i]) throw FgError{FG_ERR_ARG, name + ": cand_off decreases at bubble " + std::to_string(i)};
+			if (bubble_branch_off[i + 1] < bubble_branch_off[i])
+				throw FgError{FG_ERR_ARG, name + ": bubble_branch_off decreases at bubble " + std::to_string(i)};
+		}
+		const u64 c0 = n_bubbles ? cand_off[0] : 0, c1 = n_bubbles ? cand_off[n_bubbles] : 0;
+		const u64 r0 = n_bubbles ? bubble_branch_off[0] : 0, r1 = n_bubbles ? bubble_branch_off[n_bubbles] : 0;
+		if (c1 > c0 && !cand) throw FgError{FG_ERR_ARG, name + ": null cand"};
+		if (r1 > r0 && !branch_off) throw FgError{FG_ERR_ARG, name + ": null branch_off"};
+		for (u64 r = r0; r < r1; ++r)
+			if (branch_off[r + 1] < branch_off[r]) throw FgError{FG_ERR_ARG, name + ": branch_off decreases at branch " + std::to_string(r)};
+		const u64 b0 = r1 > r0 ? branch_off[r0] : 0, b1 = r1 > r0 ? branch_off[r1] : 0;
+		if (b1 > b0 && !branches) throw FgError{FG_ERR_ARG, name + ": null branches"};
+		for (u64 k = c0; k < c1; ++k)
+			if (cand[k] >= 128) throw FgError{FG_ERR_ARG, name + ": byte " + std::to_string(cand[k]) + " in a candidate"};
+		for (u64 k = b0; k < b1; ++k)
+			if (branches[k] >= 128) throw FgError{FG_ERR_ARG, name + ": byte " + std::to_string(branches[k]) + " in a branch"};
+		own = new PolishOwner;
+		std::vector<std::string> outCand;
+		std::vector<std::vector<std::pair<std::string, int64_t>>> steps;
+		if (n_bubbles)
+		{
+			HIP_CHECK(hipSetDevice(c->device));
+			fgPolishBubbles(c, &matrix->score[0][0], cand, cand_off, branches, branch_off, bubble_branch_off, n_bubbles,
+							fix_dinucleotides != 0, want_steps != 0, outCand, own->nSteps, own->status, steps);
+		}
+		own->candOff.assign(1, 0);
+		for (const std::string& v : outCand)
+		{
+			own->cand.insert(own->cand.end(), v.begin(), v.end());
+			own->candOff.push_back(own->cand.size());
+		}
+		if (want_steps)
+		{
+			own->stepOff.assign(1, 0);
+			own->stepSeqOff.assign(1, 0);
+			for (const auto& list : steps)
+			{
+				for (const auto& st : list)
+				{
+					own->stepSeq.insert(own->stepSeq.end(), st.first.begin(), st.first.end());
+					own->stepSeqOff.push_back(own->stepSeq.size());
+					own->stepScore.push_back(st.second);
+				}
+				own->stepOff.push_back(own->stepScore.size());
+			}
+		}
+		for (auto* v : {&own->cand, &own->status, &own->stepSeq})
+			if (v->empty()) v->reserve(1);
+		if (own->nSteps.empty()) own->nSteps.reserve(1);
+		if (own->stepScore.empty()) own->stepScore.reserve(1);
+	});
+	if (rc != FG_OK) { delete own; return rc; }
+	out->n_bubbles = n_bubbles;
+	out->cand = own->cand.data();
+	out->cand_off = own->candOff.data();
+	out->n_steps = own->nSteps.data();
+	out->status = own->status.data();
+	if (want_steps)
+	{
+		out->step_off = own->stepOff.data();
+		out->step_score = own->stepScore.data();
+		out->step_seq = own->stepSeq.data();
+		out->step_seq_off = own->stepSeqOff.data();
+	}
+	out->owner_ = own;
+	return FG_OK;
+}
+
+void fg_release_polish(struct fg_polish_batch* b)
+{
+	if (!b) return;
+	delete (PolishOwner*)b->owner_;
+	memset(b, 0, sizeof(*b));
+}
+
 void fg_release_chains(struct fg_chain_batch* b)
 {
 	if (!b) return;

@@ -434,6 +434,11 @@ struct fg_ctx {
 	DevBuf<char> dCovRecs, dCovSort;
 	DevBuf<u64> dCovIv, dCovKeys, dCovOff;
 	DevBuf<i32> dCovI32, dCovVec;
+	// fg_polish_bubbles (fg_polish.hip): the call's branches (bytes, offsets) and score table; per chunk of a round the
+	// candidates, items, branch alignments, edit offsets, the F / R cells, the edit sums and the results
+	DevBuf<char> dPolBytes, dPolCand, dPolItems, dPolTasks, dPolRes;
+	DevBuf<u64> dPolOff, dPolEdOff;
+	DevBuf<long long> dPolScore, dPolCells, dPolEdits;
 	PinnedBuf<char> hPrim;
 	PinnedBuf<u64> hOff;
 	PinnedBuf<u64> hScalar;		// staging of the counts the host reads between kernels (pinned: no bounce buffer)
@@ -768,6 +773,13 @@ void fgReadCoverage(fg_ctx* c, i32 window, i32 maxOverhang, i32 maxFlank, const 
 					long long* sum, i32* stat);
 void fgEdgeCoverage(fg_ctx* c, i32 window, const std::vector<FgCovEdgeEl>& el, const std::vector<u64>& winOff, bool wantVectors,
 					i32* cov, long long* sum, i32* stat);
+// fg_polish_bubbles behind its argument checks (fg_polish.hip): score36 = the 6 x 6 table [consensus class][read class];
+// the flat inputs of the ABI call; per bubble the final candidate, the number of steps, the status bits and (wantSteps)
+// the steps as (sequence, score).  Resets and collects the timer.
+void fgPolishBubbles(fg_ctx* c, const int64_t* score36, const uint8_t* cand, const uint64_t* candOff, const uint8_t* branches,
+					 const uint64_t* branchOff, const uint64_t* bubbleBranchOff, u32 nBubbles, bool fixDinucleotides, bool wantSteps,
+					 std::vector<std::string>& outCand, std::vector<uint32_t>& nSteps, std::vector<uint8_t>& status,
+					 std::vector<std::vector<std::pair<std::string, int64_t>>>& steps);
 void fgDebugSortPairs(fg_ctx* c, u64* keys, u32* vals, const u64* segOff, u32 nSeg);
 void fgDebugProbeSkipCheck(fg_ctx* c, u64* clearBits, u64* violations);
 void fgDebugEditDistances(fg_ctx* c, u32 nPairs, int useHpc, i32* outDist, i32* outLenA, i32* outLenB);

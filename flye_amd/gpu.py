@@ -12,6 +12,8 @@ like calls into the reference:
 * ``OverlapContainer.quickSeqOverlaps / lazySeqOverlaps /
   estimateOverlaperParameters / setDivergenceThreshold``
   (src/sequence/overlap.cpp:518-574, :744-827)
+* ``BubbleProcessor(ctx, subs_matrix_path).polishAll(in_bubbles, out_consensus, log_path)``
+  (src/polishing/bubble_processor.cpp:32-148; without the homopolymer matrix, which the reference never uses)
 
 There is no CPU fallback: if the HIP library or a device is missing every entry
 point raises ``FlyeGpuError``.
@@ -47,6 +49,7 @@ ABI_SYMBOLS = ["fg_abi_version", "fg_create", "fg_destroy", "fg_strerror", "fg_l
                "fg_chain_alignments", "fg_release_chains",
                "fg_read_coverage", "fg_release_coverage", "fg_coverage_windows", "fg_coverage_verdict",
                "fg_edge_coverage", "fg_release_edge_coverage",
+               "fg_subs_matrix_load", "fg_polish_bubbles", "fg_release_polish",
                "fg_index_keep_targets", "fg_index_shard", "fg_probe_hits", "fg_overlaps_from_hits",
                "fg_index_piece_split", "fg_index_scatter_begin", "fg_index_scatter_end", "fg_debug_probe_skip_check",
                "fg_group_create", "fg_group_destroy", "fg_group_size", "fg_group_member", "fg_group_last_error",
@@ -159,6 +162,18 @@ class EdgeCoverageBatch(C.Structure):
     _fields_ = [("n_edges", C.c_uint32), ("win_off", C.POINTER(C.c_uint64)), ("cov", C.POINTER(C.c_int32)),
                 ("sum", C.POINTER(C.c_int64)), ("max", C.POINTER(C.c_int32)), ("median", C.POINTER(C.c_int32)),
                 ("owner_", C.c_void_p)]
+
+
+class SubsMatrixStruct(C.Structure):
+    """struct fg_subs_matrix: score[consensus class][read class], classes A C G T other gap"""
+    _fields_ = [("score", (C.c_int64 * 6) * 6)]
+
+
+class PolishBatch(C.Structure):
+    _fields_ = [("n_bubbles", C.c_uint32), ("cand", C.POINTER(C.c_uint8)), ("cand_off", C.POINTER(C.c_uint64)),
+                ("n_steps", C.POINTER(C.c_uint32)), ("status", C.POINTER(C.c_uint8)), ("step_off", C.POINTER(C.c_uint64)),
+                ("step_score", C.POINTER(C.c_int64)), ("step_seq", C.POINTER(C.c_uint8)),
+                ("step_seq_off", C.POINTER(C.c_uint64)), ("owner_", C.c_void_p)]
 
 
 class BridgeStats(C.Structure):
@@ -276,6 +291,11 @@ def load_library():
                                        C.POINTER(EdgeCoverageBatch)]
         L.fg_release_edge_coverage.argtypes = [C.POINTER(EdgeCoverageBatch)]
         L.fg_release_edge_coverage.restype = None
+        L.fg_subs_matrix_load.argtypes = [C.c_char_p, C.POINTER(SubsMatrixStruct)]
+        L.fg_polish_bubbles.argtypes = [C.c_void_p, C.POINTER(SubsMatrixStruct), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_uint32, C.c_uint8, C.c_uint8, C.POINTER(PolishBatch)]
+        L.fg_release_polish.argtypes = [C.POINTER(PolishBatch)]
+        L.fg_release_polish.restype = None
         L.fg_debug_group_bin_cuts.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         L.fg_debug_freq_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
         L.fg_debug_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int]
@@ -492,6 +512,31 @@ def coverage_verdict(params, n_windows, sums, median, min_good):
     if rc != 0:
         raise FlyeGpuError(rc, L.fg_strerror(rc).decode())
     return thr, chim.astype(bool)
+
+
+class SubstitutionMatrix:
+    """The reference's SubstitutionMatrix (src/polishing/subs_matrix.cpp:58-104) as the 6 x 6 table of
+    fg_subs_matrix_load; ``table`` is a numpy view of it."""
+
+    def __init__(self, path=None, table=None):
+        self.c = SubsMatrixStruct()
+        if path is not None:
+            rc = load_library().fg_subs_matrix_load(os.fsencode(path), C.byref(self.c))
+            if rc != 0:
+                raise FlyeGpuError(rc, f"fg_subs_matrix_load({path})")
+        self.table = np.ctypeslib.as_array(self.c.score)
+        if table is not None:
+            self.table[:] = np.asarray(table, np.int64).reshape(6, 6)
+
+
+class PolishResult:
+    """fg_polish_batch copied out of its arena: candidates (bytes per bubble), n_steps, status, and with want_steps
+    steps[i] = [(sequence bytes, score), ...]"""
+
+    SKIPPED, OVERFLOW, ITER_LIMIT, FIXED = 1, 2, 4, 8
+
+    def __init__(self, candidates, n_steps, status, steps):
+        self.candidates, self.n_steps, self.status, self.steps = candidates, n_steps, status, steps
 
 
 class ReadCoverage:
@@ -777,6 +822,46 @@ class Context:
                            degenerate=take(b.degenerate, nq, np.uint8).astype(bool))
         self.L.fg_release_coverage(C.byref(b))
         return out
+
+    def polish_bubbles(self, matrix, cand, cand_off, branches, branch_off, bubble_branch_off, fix_dinucleotides=True,
+                       want_steps=True):
+        """fg_polish_bubbles: GeneralPolisher::polishBubble and DinucleotideFixer::fixBubble for bubbles given as flat
+        bytes with offsets (bubble i: cand[cand_off[i]:cand_off[i + 1]], branches bubble_branch_off[i] ..
+        bubble_branch_off[i + 1], branch r = branches[branch_off[r]:branch_off[r + 1]]).  Returns a PolishResult."""
+        cb = np.frombuffer(bytes(cand), np.uint8)
+        bb = np.frombuffer(bytes(branches), np.uint8)
+        co = np.ascontiguousarray(cand_off, np.uint64)
+        bo = np.ascontiguousarray(branch_off, np.uint64)
+        bbo = np.ascontiguousarray(bubble_branch_off, np.uint64)
+        n = len(co) - 1
+        if n < 0 or len(bbo) != n + 1 or (n and (int(co.max()) > len(cb) or int(bbo.max()) + 1 > len(bo))) or \
+                (len(bo) and int(bo.max()) > len(bb)):
+            raise ValueError("polish_bubbles: offsets outside their arrays")
+        b = PolishBatch()
+        t0 = time.perf_counter()
+        self._check(self.L.fg_polish_bubbles(self.h, C.byref(matrix.c), cb.ctypes.data if len(cb) else None, co.ctypes.data,
+                                             bb.ctypes.data if len(bb) else None, bo.ctypes.data if len(bo) else None,
+                                             bbo.ctypes.data, n, int(bool(fix_dinucleotides)), int(bool(want_steps)), C.byref(b)))
+        self.last_polish_seconds = time.perf_counter() - t0
+
+        def take(ptr, k, dtype):
+            return np.ctypeslib.as_array(ptr, (k,)).copy() if k else np.zeros(0, dtype)
+
+        off = take(b.cand_off, n + 1, np.uint64)
+        raw = take(b.cand, int(off[n]), np.uint8).tobytes()
+        cands = [raw[int(off[i]):int(off[i + 1])] for i in range(n)]
+        n_steps, status = take(b.n_steps, n, np.uint32), take(b.status, n, np.uint8)
+        steps = None
+        if want_steps:
+            so = take(b.step_off, n + 1, np.uint64)
+            ns = int(so[n])
+            sso = take(b.step_seq_off, ns + 1, np.uint64)
+            sraw = take(b.step_seq, int(sso[ns]), np.uint8).tobytes()
+            score = take(b.step_score, ns, np.int64)
+            steps = [[(sraw[int(sso[t]):int(sso[t + 1])], int(score[t])) for t in range(int(so[i]), int(so[i + 1]))]
+                     for i in range(n)]
+        self.L.fg_release_polish(C.byref(b))
+        return PolishResult(cands, n_steps, status, steps)
 
     def edge_coverage(self, window, recs, aln, aln_off, first_ext_id, edge_of, edge_len, want_vectors=True):
         """fg_edge_coverage: the window coverage of MultiplicityInferer::estimateCoverage (multiplicity_inferer.cpp:
@@ -1576,3 +1661,67 @@ class BatchingOverlapContainer:
         st = BridgeStats()
         self.L.fgb_get_stats(self.h, C.byref(st))
         return {k: int(getattr(st, k)) for k, _ in st._fields_}
+
+
+class BubbleProcessor:
+    """Mirror of the reference's BubbleProcessor (src/polishing/bubble_processor.cpp) on fg_polish_bubbles: reads a
+    bubbles file as cacheBubbles does (:151-204), polishes every bubble in one device call and writes the consensus file
+    and the --debug log as one worker thread would (:75-148)."""
+
+    BUBBLES_CACHE = 100
+
+    def __init__(self, ctx: Context, subs_matrix_path, fix_dinucleotides=True):
+        self.ctx = ctx
+        self.matrix = SubstitutionMatrix(subs_matrix_path)
+        self.fix_dinucleotides = fix_dinucleotides
+
+    @staticmethod
+    def read_bubbles(path):
+        """-> [(header, position, candidate, [branches])], everything upper-cased, up to the first empty header line"""
+        with open(path, "rb") as f:
+            lines = f.read().decode("latin-1").split("\n")
+        if lines == [""]:
+            raise RuntimeError("Empty bubbles file!")
+        lines.append("")
+        out, at = [], 0
+        while at < len(lines) - 1:
+            buf = lines[at]
+            if not buf:
+                break
+            elems = buf.split(" ")
+            if len(elems) < 3 or elems[0][:1] != ">":
+                raise RuntimeError("Error parsing bubbles file")
+            cand = lines[min(at + 1, len(lines) - 1)].upper()
+            at += 2
+            branches = []
+            for _ in range(int(elems[2])):
+                if not buf:       # the line before was empty: the reference stops counting here and throws
+                    raise RuntimeError("Error parsing bubbles file")
+                buf = lines[min(at + 1, len(lines) - 1)].upper()
+                at += 2
+                branches.append(buf)
+            out.append((elems[0][1:], int(elems[1]), cand, branches))
+        return out
+
+    def polishAll(self, in_bubbles, out_consensus, log_path=None):
+        bubbles = self.read_bubbles(in_bubbles)
+        cand = "".join(b[2] for b in bubbles).encode("latin-1")
+        flat = [w for b in bubbles for w in b[3]]
+        res = self.ctx.polish_bubbles(self.matrix, cand, np.cumsum([0] + [len(b[2]) for b in bubbles]),
+                                      "".join(flat).encode("latin-1"), np.cumsum([0] + [len(w) for w in flat]),
+                                      np.cumsum([0] + [len(b[3]) for b in bubbles]), self.fix_dinucleotides,
+                                      want_steps=log_path is not None)
+        order = []
+        for a in range(0, len(bubbles), self.BUBBLES_CACHE):
+            order += range(min(a + self.BUBBLES_CACHE, len(bubbles)) - 1, a - 1, -1)
+        with open(out_consensus, "wb") as f:
+            for i in order:
+                b = bubbles[i]
+                f.write((">%s %d %d\n" % (b[0], b[1], len(b[3]))).encode("latin-1") + res.candidates[i] + b"\n")
+        if log_path is not None:
+            with open(log_path, "wb") as f:
+                for i in order:
+                    for seq, score in res.steps[i]:
+                        f.write(b"%-22s%s\n%-22s%d\n\n" % (b"Consensus: ", seq, b"Score: ", score))
+                    f.write(b"-----------------\n")
+        return res

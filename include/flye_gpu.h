@@ -699,6 +699,61 @@ int  fg_edge_coverage(fg_ctx* ctx, int32_t window, const struct fg_overlap_rec* 
                       struct fg_edge_coverage_batch* out);
 void fg_release_edge_coverage(struct fg_edge_coverage_batch* b);
 
+/* Bubble polishing: what flye-modules polisher does to every bubble (src/polishing: BubbleProcessor::parallelWorker,
+ * GeneralPolisher::polishBubble / makeStep, Alignment, DinucleotideFixer::fixBubble; HomoPolisher is switched off in the
+ * reference, bubble_processor.cpp:99, and is not here).
+ * Bytes fall into six classes: 'A' 0, 'C' 1, 'G' 2, 'T' 3, '-' 5 (gap), every other byte below 128 class 4 (lower case
+ * too: the reference's file reader upper-cases, this call does not).  score[c][r] is the score of consensus class c
+ * against read class r: score[x][x] = mat x, score[x][y] = mis x->y, score[x][5] = del x, score[5][y] = ins y; the
+ * reference leaves every other pair at 0, so row and column 4 and score[5][5] are 0 in a loaded matrix.
+ * For a candidate v (length L) and a branch w (length Lb): F[i][j] = the best score of v[0:i] against w[0:j] (F[0][0] =
+ * 0, borders by del / ins, inside max of left + ins, up + del, diagonal + score), R the same for the last i bases of v
+ * against the last j of w.  A(v) = sum over the branches of F[L][Lb], where a branch counts 0 when L = 0 or Lb = 0
+ * (alignment.cpp:150-190 returns its untouched local).  makeStep (general_polisher.cpp:60-123): the deletions of v[p]
+ * (max_j F[p][j] + R[L-1-p][Lb-j]), p ascending, the first maximum above A(v) wins; only if none improves the
+ * insertions of A, C, G, T before p = 0 .. L (sub[0] = F[p][0] + del b, sub[j+1] = max(F[p][j] + score[b][w[j]],
+ * F[p][j+1] + del b); max_j sub[j] + R[L-p][Lb-j]); only if none improves the substitutions of v[p] by every letter
+ * that differs from it (the same sub against R[L-1-p]).  optimize (:10-35) repeats makeStep and records every step;
+ * it stops when a step changes nothing, when a step's score is > 0 (status bit 1) or when more than 10 * len(v0)
+ * earlier iterations have run (bit 2); in the last two cases the step is recorded and the candidate from before it
+ * stays.  A bubble of more than 10 branches is first optimized against five of them: std::sort by length (libstdc++'s
+ * permutation), positions [n/2 - 2, n/2 + 3).  Then fixBubble (fix_dinucleotides != 0): the longest run (>= 3) of a pair
+ * of two different bases that a different pair ends (shift 0 before shift 1, the first longest) is lengthened by one
+ * pair if that raises A, else shortened by one pair if that raises A (bit 3, one more step of score 0).  A bubble with
+ * a candidate of 5000 bytes or more, or with fewer than two branches, comes back unchanged without steps (bit 0).
+ * Bubble i: candidate cand[cand_off[i] .. cand_off[i+1]), branches bubble_branch_off[i] .. bubble_branch_off[i+1],
+ * branch r = branches[branch_off[r] .. branch_off[r+1]).
+ * The context lends its device and stream: no reads and no index are needed.  The host drives the step loop; each
+ * round works on the bubbles still at work in chunks of at most FG_POLISH_SCRATCH_BYTES of scratch (environment,
+ * default 8 GiB; 16 bytes per cell of (L + 1) * (Lb + 1) per branch plus 72 (L + 1)); FG_POLISH_BATCH_BUBBLES (a switch
+ * for tests) also bounds the bubbles of a chunk.  The result does not depend on either.  fg_kernel_times afterwards
+ * reports the sums over all rounds.
+ * FG_ERR_ARG, found before any device work: NULL matrix or out; a NULL array with n_bubbles > 0; an offset array that
+ * decreases; a byte >= 128 in a candidate or a branch.  FG_ERR_NOMEM: one bubble alone needs more than the scratch
+ * budget.  n_bubbles = 0 gives an empty batch (cand_off = {0}). */
+struct fg_subs_matrix { int64_t score[6][6]; };
+struct fg_polish_batch {
+	uint32_t  n_bubbles;
+	uint8_t*  cand;          /* the polished candidates, bubble i at cand_off[i] .. cand_off[i+1] */
+	uint64_t* cand_off;      /* n_bubbles + 1 */
+	uint32_t* n_steps;       /* recorded steps of bubble i (both optimize phases and the fixer) */
+	uint8_t*  status;        /* bit 0 skipped, 1 stopped on score > 0, 2 stopped on the iteration limit, 3 fixer changed it */
+	uint64_t* step_off;      /* want_steps: n_bubbles + 1, the steps of bubble i are step_off[i] .. step_off[i+1] */
+	int64_t*  step_score;    /* want_steps */
+	uint8_t*  step_seq;      /* want_steps: step t at step_seq_off[t] .. step_seq_off[t+1] */
+	uint64_t* step_seq_off;  /* want_steps: number of steps + 1 */
+	void*     owner_;
+};
+/* Host only, no context: reads the reference's *_substitutions.mat text (tab-separated "mat X p", "mis X->Y p",
+ * "del X p", "ins X p"; other lines are ignored, a trailing \r is dropped); score = (int64)round(log(p) * 131072) in
+ * double.  FG_ERR_ARG: NULL arguments, a file that cannot be read, a line of those four kinds that is malformed or
+ * names a letter outside A, C, G, T. */
+int  fg_subs_matrix_load(const char* path, struct fg_subs_matrix* out);
+int  fg_polish_bubbles(fg_ctx* ctx, const struct fg_subs_matrix* matrix, const uint8_t* cand, const uint64_t* cand_off,
+                       const uint8_t* branches, const uint64_t* branch_off, const uint64_t* bubble_branch_off,
+                       uint32_t n_bubbles, uint8_t fix_dinucleotides, uint8_t want_steps, struct fg_polish_batch* out);
+void fg_release_polish(struct fg_polish_batch* b);
+
 #ifdef __cplusplus
 }
 #endif
