@@ -439,6 +439,8 @@ struct fg_ctx {
 	DevBuf<char> dPolBytes, dPolCand, dPolItems, dPolTasks, dPolRes;
 	DevBuf<u64> dPolOff, dPolEdOff;
 	DevBuf<long long> dPolScore, dPolCells, dPolEdits;
+	// fg_make_bubbles (fg_bubbles.hip): the buffers of one sub-batch, handed out in call order
+	DevBuf<char> dBub[36];
 	PinnedBuf<char> hPrim;
 	PinnedBuf<u64> hOff;
 	PinnedBuf<u64> hScalar;		// staging of the counts the host reads between kernels (pinned: no bounce buffer)

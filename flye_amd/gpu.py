@@ -14,6 +14,8 @@ like calls into the reference:
   (src/sequence/overlap.cpp:518-574, :744-827)
 * ``BubbleProcessor(ctx, subs_matrix_path).polishAll(in_bubbles, out_consensus, log_path)``
   (src/polishing/bubble_processor.cpp:32-148; without the homopolymer matrix, which the reference never uses)
+* ``BubbleMaker(ctx).make(contigs, alignments_by_contig, err_mode)`` / ``write_bubbles`` / ``uniform_alignments`` /
+  ``polish``  (flye/polishing/bubbles.py:87-172 and alignment.py:95-153; alignment records instead of a SAM file)
 
 There is no CPU fallback: if the HIP library or a device is missing every entry
 point raises ``FlyeGpuError``.
@@ -49,7 +51,7 @@ ABI_SYMBOLS = ["fg_abi_version", "fg_create", "fg_destroy", "fg_strerror", "fg_l
                "fg_chain_alignments", "fg_release_chains",
                "fg_read_coverage", "fg_release_coverage", "fg_coverage_windows", "fg_coverage_verdict",
                "fg_edge_coverage", "fg_release_edge_coverage",
-               "fg_subs_matrix_load", "fg_polish_bubbles", "fg_release_polish",
+               "fg_subs_matrix_load", "fg_polish_bubbles", "fg_release_polish", "fg_make_bubbles", "fg_release_bubbles",
                "fg_index_keep_targets", "fg_index_shard", "fg_probe_hits", "fg_overlaps_from_hits",
                "fg_index_piece_split", "fg_index_scatter_begin", "fg_index_scatter_end", "fg_debug_probe_skip_check",
                "fg_group_create", "fg_group_destroy", "fg_group_size", "fg_group_member", "fg_group_last_error",
@@ -176,6 +178,38 @@ class PolishBatch(C.Structure):
                 ("step_seq_off", C.POINTER(C.c_uint64)), ("owner_", C.c_void_p)]
 
 
+class BubbleParams(C.Structure):
+    """struct fg_bubble_params: cfg.vals of flye/config/py_cfg.py:41-46 and the err_modes entry of the platform"""
+    _fields_ = [("solid_kmer_length", C.c_int32), ("simple_kmer_length", C.c_int32), ("max_bubble_length", C.c_int32),
+                ("max_bubble_branches", C.c_int32), ("min_polish_aln_len", C.c_int32), ("pad_", C.c_int32),
+                ("solid_missmatch", C.c_double), ("solid_indel", C.c_double), ("max_aln_error", C.c_double)]
+
+    # the reference's values (py_cfg.py:41-46, :52-66)
+    DEFAULTS = dict(simple_kmer_length=4, solid_kmer_length=10, max_bubble_length=500, max_bubble_branches=50,
+                    min_polish_aln_len=500)
+    ERR_MODES = dict(pacbio=dict(solid_missmatch=0.2, solid_indel=0.2, max_aln_error=0.25),
+                     nano=dict(solid_missmatch=0.3, solid_indel=0.3, max_aln_error=0.25))
+
+    @classmethod
+    def for_mode(cls, err_mode, **overrides):
+        vals = dict(cls.DEFAULTS)
+        vals.update(cls.ERR_MODES[err_mode])
+        vals.update(overrides)
+        return cls(**vals)
+
+
+class BubbleBatch(C.Structure):
+    _fields_ = [("n_contigs", C.c_uint32), ("n_bubbles", C.c_uint32), ("n_alignments", C.c_uint64),
+                ("bubble_off", C.POINTER(C.c_uint64)), ("position", C.POINTER(C.c_int32)), ("cand", C.POINTER(C.c_uint8)),
+                ("cand_off", C.POINTER(C.c_uint64)), ("branches", C.POINTER(C.c_uint8)), ("branch_off", C.POINTER(C.c_uint64)),
+                ("bubble_branch_off", C.POINTER(C.c_uint64)), ("n_long_bubbles", C.POINTER(C.c_int32)),
+                ("n_empty", C.POINTER(C.c_int32)), ("n_long_branch", C.POINTER(C.c_int32)), ("mean_cov", C.POINTER(C.c_int64)),
+                ("n_partition", C.POINTER(C.c_int32)), ("in_profile", C.POINTER(C.c_uint8)), ("part_off", C.POINTER(C.c_uint64)),
+                ("partition", C.POINTER(C.c_int32)), ("prof_off", C.POINTER(C.c_uint64)), ("coverage", C.POINTER(C.c_int32)),
+                ("num_inserts", C.POINTER(C.c_int32)), ("num_deletions", C.POINTER(C.c_int32)),
+                ("num_missmatch", C.POINTER(C.c_int32)), ("nucl", C.POINTER(C.c_uint8)), ("owner_", C.c_void_p)]
+
+
 class BridgeStats(C.Structure):
     _fields_ = [("device_calls", C.c_uint64), ("reads_computed", C.c_uint64), ("requests", C.c_uint64),
                 ("cache_hits", C.c_uint64), ("cached_overlaps", C.c_uint64), ("reads_ahead", C.c_uint64),
@@ -296,6 +330,10 @@ def load_library():
                                         C.c_void_p, C.c_uint32, C.c_uint8, C.c_uint8, C.POINTER(PolishBatch)]
         L.fg_release_polish.argtypes = [C.POINTER(PolishBatch)]
         L.fg_release_polish.restype = None
+        L.fg_make_bubbles.argtypes = [C.c_void_p, C.POINTER(BubbleParams), C.c_uint32] + [C.c_void_p] * 9 + \
+            [C.c_uint8, C.POINTER(BubbleBatch)]
+        L.fg_release_bubbles.argtypes = [C.POINTER(BubbleBatch)]
+        L.fg_release_bubbles.restype = None
         L.fg_debug_group_bin_cuts.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         L.fg_debug_freq_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
         L.fg_debug_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int]
@@ -527,6 +565,27 @@ class SubstitutionMatrix:
         self.table = np.ctypeslib.as_array(self.c.score)
         if table is not None:
             self.table[:] = np.asarray(table, np.int64).reshape(6, 6)
+
+
+class BubbleResult:
+    """fg_bubble_batch copied out of its arena, arrays under the names of the header.  bubbles(i) gives the bubbles of
+    contig i as (position, consensus bytes, [branch bytes])."""
+
+    def __init__(self, **arrays):
+        self.__dict__.update(arrays)
+
+    def bubbles(self, i):
+        cand, br = self.cand.tobytes(), self.branches.tobytes()
+        out = []
+        for b in range(int(self.bubble_off[i]), int(self.bubble_off[i + 1])):
+            rs = range(int(self.bubble_branch_off[b]), int(self.bubble_branch_off[b + 1]))
+            out.append((int(self.position[b]), cand[int(self.cand_off[b]):int(self.cand_off[b + 1])],
+                        [br[int(self.branch_off[r]):int(self.branch_off[r + 1])] for r in rs]))
+        return out
+
+    def same_as(self, other):
+        return self.__dict__.keys() == other.__dict__.keys() and all(
+            (v is None and other.__dict__[k] is None) or np.array_equal(v, other.__dict__[k]) for k, v in self.__dict__.items())
 
 
 class PolishResult:
@@ -862,6 +921,54 @@ class Context:
                      for i in range(n)]
         self.L.fg_release_polish(C.byref(b))
         return PolishResult(cands, n_steps, status, steps)
+
+    def make_bubbles(self, params, contig_len, contig_circular, contig_aln_off, trg_start, trg_end, err_rate, col_off,
+                     trg_cols, qry_cols, want_profile=False):
+        """fg_make_bubbles: the reference's bubbles.py from _compute_profile onward for a batch of contigs.  Contig i has
+        the alignments contig_aln_off[i] .. contig_aln_off[i + 1]; alignment a has the columns col_off[a] .. col_off[a + 1]
+        of the gapped strings trg_cols / qry_cols (bytes, '-' the gap).  Returns a BubbleResult."""
+        cl = np.ascontiguousarray(contig_len, np.int32)
+        n = len(cl)
+        cc = np.ascontiguousarray(contig_circular, np.uint8) if contig_circular is not None else np.zeros(n, np.uint8)
+        cao = np.ascontiguousarray(contig_aln_off, np.uint64)
+        ts, te = np.ascontiguousarray(trg_start, np.int32), np.ascontiguousarray(trg_end, np.int32)
+        er = np.ascontiguousarray(err_rate, np.float64)
+        co = np.ascontiguousarray(col_off, np.uint64)
+        tc, qc = np.frombuffer(bytes(trg_cols), np.uint8), np.frombuffer(bytes(qry_cols), np.uint8)
+        if len(cao) != n + 1 or len(cc) != n or len(tc) != len(qc) or len(ts) != len(te) or len(ts) != len(er) or \
+                (n and int(cao.max()) > len(ts)) or (len(ts) and len(co) != len(ts) + 1) or (len(co) and int(co.max()) > len(tc)):
+            raise ValueError("make_bubbles: offsets outside their arrays")
+        ptr = lambda a: a.ctypes.data if len(a) else None
+        b = BubbleBatch()
+        t0 = time.perf_counter()
+        self._check(self.L.fg_make_bubbles(self.h, C.byref(params), n, ptr(cl), ptr(cc), cao.ctypes.data, ptr(ts), ptr(te), ptr(er),
+                                           ptr(co), ptr(tc), ptr(qc), int(bool(want_profile)), C.byref(b)))
+        self.last_bubbles_seconds = time.perf_counter() - t0
+
+        def take(p, k, dtype):
+            return np.ctypeslib.as_array(p, (k,)).copy() if k else np.zeros(0, dtype)
+
+        nb = int(b.n_bubbles)
+        bbo = take(b.bubble_branch_off, nb + 1, np.uint64)
+        bro = take(b.branch_off, int(bbo[nb]) + 1, np.uint64)
+        cdo = take(b.cand_off, nb + 1, np.uint64)
+        out = dict(bubble_off=take(b.bubble_off, n + 1, np.uint64), position=take(b.position, nb, np.int32),
+                   cand=take(b.cand, int(cdo[nb]), np.uint8), cand_off=cdo, branches=take(b.branches, int(bro[-1]), np.uint8),
+                   branch_off=bro, bubble_branch_off=bbo, n_long_bubbles=take(b.n_long_bubbles, n, np.int32),
+                   n_empty=take(b.n_empty, n, np.int32), n_long_branch=take(b.n_long_branch, n, np.int32),
+                   mean_cov=take(b.mean_cov, n, np.int64), n_partition=take(b.n_partition, n, np.int32),
+                   in_profile=take(b.in_profile, int(b.n_alignments), np.uint8))
+        for k in ("part_off", "partition", "prof_off", "coverage", "num_inserts", "num_deletions", "num_missmatch", "nucl"):
+            out[k] = None
+        if want_profile:
+            out["part_off"], out["prof_off"] = take(b.part_off, n + 1, np.uint64), take(b.prof_off, n + 1, np.uint64)
+            out["partition"] = take(b.partition, int(out["part_off"][n]), np.int32)
+            npos = int(out["prof_off"][n])
+            for k in ("coverage", "num_inserts", "num_deletions", "num_missmatch"):
+                out[k] = take(getattr(b, k), npos, np.int32)
+            out["nucl"] = take(b.nucl, npos, np.uint8)
+        self.L.fg_release_bubbles(C.byref(b))
+        return BubbleResult(**out)
 
     def edge_coverage(self, window, recs, aln, aln_off, first_ext_id, edge_of, edge_len, want_vectors=True):
         """fg_edge_coverage: the window coverage of MultiplicityInferer::estimateCoverage (multiplicity_inferer.cpp:
@@ -1725,3 +1832,82 @@ class BubbleProcessor:
                         f.write(b"%-22s%s\n%-22s%d\n\n" % (b"Consensus: ", seq, b"Score: ", score))
                     f.write(b"-----------------\n")
         return res
+
+
+class BubbleMaker:
+    """Mirror of the reference's flye/polishing/bubbles.py on fg_make_bubbles.  Alignments are records with the fields of
+    the reference's Alignment tuple (trg_start, trg_end, trg_seq, qry_seq, err_rate, is_secondary are read); contigs are
+    records with id, length and type.  SAM parsing stays with the caller."""
+
+    WINDOW, MIN_COV, COV_RATE = 100, 10, 1.25
+
+    def __init__(self, ctx: Context, **overrides):
+        self.ctx = ctx
+        self.overrides = overrides
+        self.contigs, self.result = [], None
+
+    @classmethod
+    def uniform_alignments(cls, alignments, seq_len):
+        """get_uniform_alignments (flye/polishing/alignment.py:95-153): per 100 bp window the best alignments up to 1.25
+        times the median primary coverage; an alignment stays when it passes in more than half of its windows.  Raises
+        ValueError where the reference raises IndexError (an alignment that ends beyond the last window)."""
+        n_w = seq_len // cls.WINDOW + 1
+        primary = [0] * n_w
+        quality = [[] for _ in range(n_w)]
+        for aln in alignments:
+            for i in range(aln.trg_start // cls.WINDOW, aln.trg_end // cls.WINDOW):
+                if i >= n_w:
+                    raise ValueError("uniform_alignments: an alignment ends beyond the contig")
+                if not aln.is_secondary:
+                    primary[i] += 1
+                quality[i].append(aln.err_rate)
+        ordered = sorted(primary)
+        median = ordered[n_w // 2] if n_w % 2 else (ordered[n_w // 2 - 1] + ordered[n_w // 2]) / 2
+        cov_threshold = max(int(cls.COV_RATE * median), cls.MIN_COV)
+        threshold = [sorted(q)[cov_threshold] if len(q) > cov_threshold else 1.0 for q in quality]
+        kept = []
+        for aln in alignments:
+            first, last = aln.trg_start // cls.WINDOW, aln.trg_end // cls.WINDOW
+            good = sum(1 for i in range(first, last) if aln.err_rate <= threshold[i])
+            if good > (last - first) // 2:
+                kept.append(aln)
+        return kept
+
+    def make(self, contigs, alignments_by_contig, err_mode, want_profile=False):
+        """make_bubbles for the contigs in the given order -> (bubbles, coverage_stats, mean_aln_error); bubbles is a list
+        of (contig id, position, consensus bytes, [branch bytes]).  mean_aln_error is sum / (n + 1) over the profiled
+        alignments summed in contig order (the reference sums in the order its workers finish, so its last bits depend on
+        the run)."""
+        params = BubbleParams.for_mode(err_mode, **self.overrides)
+        alns = [a for c in contigs for a in alignments_by_contig.get(c.id, [])]
+        trg = "".join(a.trg_seq for a in alns).encode("latin-1")
+        qry = "".join(a.qry_seq for a in alns).encode("latin-1")
+        res = self.ctx.make_bubbles(params, [c.length for c in contigs], [c.type == "circular" for c in contigs],
+                                    np.cumsum([0] + [len(alignments_by_contig.get(c.id, [])) for c in contigs]),
+                                    [a.trg_start for a in alns], [a.trg_end for a in alns], [a.err_rate for a in alns],
+                                    np.cumsum([0] + [len(a.trg_seq) for a in alns]), trg, qry, want_profile)
+        self.contigs, self.result = list(contigs), res
+        self.bubbles = [(c.id,) + b for i, c in enumerate(contigs) for b in res.bubbles(i)]
+        self.aln_errors = [a.err_rate for a, f in zip(alns, res.in_profile) if f]
+        coverage_stats = {c.id: int(res.mean_cov[i]) for i, c in enumerate(contigs)}
+        total = 0.0
+        for e in self.aln_errors:
+            total += e
+        return self.bubbles, coverage_stats, total / (len(self.aln_errors) + 1)
+
+    def write_bubbles(self, path):
+        """the bubbles of the last make() in the form of _output_bubbles (bubbles.py:159-172)"""
+        with open(path, "wb") as f:
+            for cid, position, cons, branches in self.bubbles:
+                f.write((">%s %d %d\n" % (cid, position, len(branches))).encode("latin-1") + cons + b"\n")
+                for k, w in enumerate(branches):
+                    f.write(b">%d\n%s\n" % (k, w))
+
+    def polish(self, contigs, alignments_by_contig, err_mode, matrix, fix_dinucleotides=True, want_steps=False):
+        """the two device stages as one call: make() -> upper case (the polisher's reader does that, bubble_processor.cpp:
+        151-204) -> Context.polish_bubbles.  Returns (bubbles, PolishResult); the branch bytes go back as they came."""
+        bubbles, _, _ = self.make(contigs, alignments_by_contig, err_mode)
+        r = self.result
+        upper = lambda a: np.frombuffer(a.tobytes().upper(), np.uint8)
+        return bubbles, self.ctx.polish_bubbles(matrix, upper(r.cand), r.cand_off, upper(r.branches), r.branch_off,
+                                                r.bubble_branch_off, fix_dinucleotides, want_steps)

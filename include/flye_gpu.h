@@ -754,6 +754,81 @@ int  fg_polish_bubbles(fg_ctx* ctx, const struct fg_subs_matrix* matrix, const u
                        uint32_t n_bubbles, uint8_t fix_dinucleotides, uint8_t want_steps, struct fg_polish_batch* out);
 void fg_release_polish(struct fg_polish_batch* b);
 
+/* The bubble partition of the reference's polisher: what _thread_worker (flye/polishing/bubbles.py:64-73) does to one
+ * contig from _compute_profile onward, for a batch of contigs: _compute_profile with both shift_gaps passes
+ * (alignment.py:68-92), _get_partition, _get_bubble_seqs and _postprocess_bubbles.  The output is, field for field, what
+ * fg_polish_bubbles takes (the reference's polisher reads its bubbles file upper-cased; this call keeps case).
+ * params are cfg.vals of flye/config/py_cfg.py:41-46 and the err_modes entry of the platform (:52-66).
+ * Contig i has contig_len[i] positions, contig_circular[i] != 0 where contig_info.type == "circular" (NULL: none is), and
+ * the alignments contig_aln_off[i] .. contig_aln_off[i+1], in the order of the reference's list (it decides nucl and the
+ * order and cap of the branches).  Alignment a: trg_start, trg_end, err_rate (the parser's value, not recomputed) and
+ * the gapped strings aln.trg_seq / aln.qry_seq as the columns col_off[a] .. col_off[a+1] of trg_cols / qry_cols, one byte
+ * per column, '-' the gap.  Offsets need not start at zero.
+ * shift_gaps: a gap run [a, b) of the second string moves left by m columns and the m bases before it move, in order, to
+ * [b - m, b); m = the number of k < min(b - a, a) in a row with second[a-1-k] == first[b-1-k].  Runs are handled left to
+ * right on the bytes earlier runs left; a run that reaches the end closes there (the "$" sentinels do that and stop the
+ * walk at the first column).  Profile (:273-314): only alignments with !(err_rate > max_aln_error) && columns >=
+ * min_polish_aln_len, shifted strings; a column with a target gap counts into num_inserts of the position before it
+ * (before position 0: contig_len - 1); any other column sets nucl (the last alignment in list order wins), adds to
+ * coverage, to num_deletions on a query gap, else to num_missmatch when the bytes differ; positions wrap at contig_len.
+ * A position is good when coverage > 0, (num_missmatch + num_deletions) / coverage <= solid_missmatch and num_inserts /
+ * coverage <= solid_indel in double (the host tabulates, per coverage, the largest numerator that passes).  Partition
+ * (:317-359): in a maximal run of good positions [s, e] the first min(floor((e-s+1) / SOLID), floor((len-SOLID-1-s) /
+ * SOLID) + 1) * SOLID positions are solid (none when s >= len - SOLID); prof_pos walks from SOLID while < len - SOLID,
+ * appends prof_pos + SIMPLE / 2 and jumps by SOLID at a landmark (SIMPLE solid positions and _is_simple_kmer) or when
+ * prof_pos - prev_partition > max_bubble_length (n_long_bubbles counts the latter).  Bubbles (:362-412): none without a
+ * partition; ALL alignments, ORIGINAL strings; a cut is a non-gap target column at position 0 or at a partition point
+ * (not the first non-gap column unless it is position 0); a cut gives the query bytes since the previous cut (since the
+ * string's start for the first), without gaps and through to_acgt (fasta_parser.py:217-219), to the bubble that was
+ * current, if a cut came before or the alignment starts in bubble 0 of a linear contig; trg_end > partition[-1] on a
+ * linear contig appends the rest to the last bubble.  Post-processing (:175-217) in integers: median = element n / 2 of
+ * the order (length, index); 2 * med > 3 * max_bubble_length keeps the median alone; else 2 * |len - med| < med stays;
+ * |med - len(consensus)| > med / 2 replaces the consensus; at most max_bubble_branches stay.
+ * The context lends its device and stream: no reads and no index are needed.  The call works in sub-batches of whole
+ * contigs of at most FG_BUBBLE_BATCH_COLS (environment, default 2^27) columns plus positions and, as a switch for tests,
+ * of at most FG_BUBBLE_BATCH_CONTIGS contigs; the result does not depend on either.  FG_ERR_NOMEM: a contig that alone exceeds it.  FG_ERR_UNSUPPORTED: simple_kmer_length odd, < 2, > 2 *
+ * solid_kmer_length or 3 * simple_kmer_length / 2 > solid_kmer_length + 1 (the reference's slices would leave the
+ * profile).  FG_ERR_ARG, found before any device work: NULL params or out; a NULL array where something must be read; an
+ * offset array that decreases; a byte >= 128; contig_len < 0; trg_start outside [0, contig_len); an alignment with more
+ * non-gap target columns than contig_len; a length or cap <= 0; a rate (err_rate too) that is NaN or negative.
+ * n_contigs = 0 gives an empty batch. */
+struct fg_bubble_params {
+	int32_t solid_kmer_length, simple_kmer_length, max_bubble_length, max_bubble_branches, min_polish_aln_len, pad_;
+	double  solid_missmatch, solid_indel, max_aln_error;
+};
+struct fg_bubble_batch {
+	uint32_t  n_contigs;
+	uint32_t  n_bubbles;
+	uint64_t  n_alignments;
+	uint64_t* bubble_off;         /* n_contigs + 1: the bubbles of contig i */
+	int32_t*  position;           /* n_bubbles */
+	uint8_t*  cand;               /* the consensus of bubble b at cand_off[b] .. cand_off[b+1] */
+	uint64_t* cand_off;           /* n_bubbles + 1 */
+	uint8_t*  branches;
+	uint64_t* branch_off;         /* number of branches + 1 */
+	uint64_t* bubble_branch_off;  /* n_bubbles + 1 */
+	int32_t*  n_long_bubbles;     /* per contig */
+	int32_t*  n_empty;
+	int32_t*  n_long_branch;
+	int64_t*  mean_cov;           /* sum(len(b.branches)) // (bubbles + 1) BEFORE post-processing (:71) */
+	int32_t*  n_partition;
+	uint8_t*  in_profile;         /* n_alignments: 1 where the alignment passed the filter of :283 */
+	uint64_t* part_off;           /* want_profile: n_contigs + 1 */
+	int32_t*  partition;          /* want_profile */
+	uint64_t* prof_off;           /* want_profile: n_contigs + 1, into the five arrays below */
+	int32_t*  coverage;
+	int32_t*  num_inserts;
+	int32_t*  num_deletions;
+	int32_t*  num_missmatch;
+	uint8_t*  nucl;               /* 0: no base */
+	void*     owner_;
+};
+int  fg_make_bubbles(fg_ctx* ctx, const struct fg_bubble_params* params, uint32_t n_contigs, const int32_t* contig_len,
+                     const uint8_t* contig_circular, const uint64_t* contig_aln_off, const int32_t* trg_start,
+                     const int32_t* trg_end, const double* err_rate, const uint64_t* col_off, const uint8_t* trg_cols,
+                     const uint8_t* qry_cols, uint8_t want_profile, struct fg_bubble_batch* out);
+void fg_release_bubbles(struct fg_bubble_batch* b);
+
 #ifdef __cplusplus
 }
 #endif
