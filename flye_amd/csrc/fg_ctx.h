@@ -393,6 +393,8 @@ struct fg_ctx {
 	DevBuf<char> dSortTasks, dSortBig;
 	DevBuf<unsigned long long> dSmallElems;	// DP elements in groups of <= 256 hits (work counter)
 	DevBuf<u32> dSortCnt;		// task counts of the sort's level loop, a row per level (fg_overlap.hip)
+	DevBuf<u32> dTieFree;		// per query, written by k_fill: 1 = no two of its hits share (extId, curPos)
+	u32 tieFreeQ0 = 0, tieFreeN = 0;	// the queries of the call dTieFree speaks of (0: the last sub-range had no flags)
 	DevBuf<int> dEditScratch;
 	DevBuf<u32> dEditList;		// pairs queued for the bit-vector kernel (two lists)
 	DevBuf<char> dEditCnt;
@@ -783,6 +785,9 @@ void fgPolishBubbles(fg_ctx* c, const int64_t* score36, const uint8_t* cand, con
 					 std::vector<std::string>& outCand, std::vector<uint32_t>& nSteps, std::vector<uint8_t>& status,
 					 std::vector<std::vector<std::pair<std::string, int64_t>>>& steps);
 void fgDebugSortPairs(fg_ctx* c, u64* keys, u32* vals, const u64* segOff, u32 nSeg);
+void fgDebugSortPairs32(fg_ctx* c, u32* keys, u32* vals, const u64* segOff, u32 nSeg, int curBits, int recBits,
+						const u32* tieFree, u64* radixSegments, u64* radixHits);
+void fgDebugTieFree(fg_ctx* c, u32* out, u32 maxN, u32* firstQuery, u32* n);
 void fgDebugProbeSkipCheck(fg_ctx* c, u64* clearBits, u64* violations);
 void fgDebugEditDistances(fg_ctx* c, u32 nPairs, int useHpc, i32* outDist, i32* outLenA, i32* outLenB);
 // option B: seed hits gathered from index shards, as the overlap stage takes them in place of its own seed

@@ -291,7 +291,8 @@ __global__ void k_fill(const u32* __restrict__ query, const i32* __restrict__ le
 					   const u64* __restrict__ qKmerOff, int k, u32 firstId, int curBits,
 					   const u64* __restrict__ probe, const u64* __restrict__ entries,
 					   const u64* __restrict__ hitOff, const u64* __restrict__ filtOff,
-					   KT* __restrict__ hitKey, u32* __restrict__ hitVal, i32* __restrict__ filtPos)
+					   KT* __restrict__ hitKey, u32* __restrict__ hitVal, i32* __restrict__ filtPos,
+					   u32* __restrict__ tieFree /* per query, or null: 1 = no two emitted hits share (record, curPos) */)
 {
 	// FILL_ITEMS consecutive positions per thread and step: a step is a chain of barriers, LDS searches and
 	// dependent loads (~4 us whatever it carries), and a read of 10^4 positions took 40 of them at one position per
@@ -307,6 +308,9 @@ __global__ void k_fill(const u32* __restrict__ query, const i32* __restrict__ le
 	const u64* pr = probe + qKmerOff[q];
 	u64 hbase = hitOff[q];
 	u64 fbase = filtOff[q];
+	// A list is ascending by record << 32 | pos, so two hits of one (record, curPos) are neighbours in it: output j > 0
+	// of a list against output j - 1, which the lane below holds (lane 0 loads it).  Both after the self-entry skip.
+	bool tied = false;
 	for (i32 p0 = 0; p0 < nk; p0 += WG * FI)
 	{
 		u64 vv[FI];
@@ -346,12 +350,27 @@ __global__ void k_fill(const u32* __restrict__ query, const i32* __restrict__ le
 		for (u32 o = threadIdx.x; o < tot; o += WG)
 		{
 			// owner = last t with sStart[t] <= o (it has a non-empty list)
-			u32 lo = 0, hi = WG * FI;
-			while (hi - lo > 1) { const u32 m = (lo + hi) >> 1; if (sStart[m] <= o) lo = m; else hi = m; }
+			constexpr u32 SPAN = WG * FI;
+			u32 lo = 0;
+			if constexpr ((SPAN & (SPAN - 1)) == 0)
+			{
+				// a power of two: the interval halves exactly, so every lane takes the same log2(SPAN) steps -- no
+				// per-step exit test and exec bookkeeping (five of a step's thirteen instructions)
+#pragma unroll
+				for (u32 half = SPAN >> 1; half; half >>= 1) if (sStart[lo + half] <= o) lo += half;
+			}
+			else
+			{
+				u32 hi = SPAN;
+				while (hi - lo > 1) { const u32 m = (lo + hi) >> 1; if (sStart[m] <= o) lo = m; else hi = m; }
+			}
 			const u32 t = lo;
 			const u32 j = o - sStart[t];
 			const u64 so = sOff[t];
 			u64 e = entries[(so & OFF_MASK) + j];
+			// the tie flag compares output j > 0 of a list with output j - 1, which the lane below holds; lane 0 of a wave
+			// loads the entry in front of its own instead (in flight together with its own)
+			u64 pe = (tieFree && j > 0 && (threadIdx.x & 63) == 0) ? entries[(so & OFF_MASK) + j - 1] : 0ULL;
 			if (so & FLAG_SELF)
 			{
 				// no trivial matches (overlap.cpp:188-190): the list is ascending and holds this
@@ -359,7 +378,14 @@ __global__ void k_fill(const u32* __restrict__ query, const i32* __restrict__ le
 				const i32 pq = p0 + (i32)t;
 				const bool fl = so & FLAG_FLIP;
 				const u64 own = ((u64)(rec ^ (fl ? 1u : 0u)) << 32) | (u32)(fl ? L - pq - k : pq);
+				if (pe >= own) pe = e;		// and output j - 1 is entry j - 1 before it, entry j after
 				if (e >= own) e = entries[(so & OFF_MASK) + j + 1];
+			}
+			if (tieFree)
+			{
+				// the record of the lane below, by a DPP move (wave_shr:1); lane 0 keeps the first operand: what it loaded
+				const u32 below = (u32)__builtin_amdgcn_update_dpp((int)(u32)(pe >> 32), (int)(u32)(e >> 32), 0x138, 0xf, 0xf, false);
+				tied |= j > 0 && below == (u32)(e >> 32);
 			}
 			u32 srec = (u32)(e >> 32);
 			i32 spos = (i32)(u32)e;
@@ -379,6 +405,11 @@ __global__ void k_fill(const u32* __restrict__ query, const i32* __restrict__ le
 		__syncthreads();
 		hbase += tot;
 		fbase += ftot;
+	}
+	if (tieFree)
+	{
+		const int anyTied = __syncthreads_or(tied);
+		if (threadIdx.x == 0) tieFree[q] = anyTied ? 0u : 1u;
 	}
 }
 
@@ -580,17 +611,184 @@ __device__ __forceinline__ void sort_route(const SortTask& t, bool valid, const 
 // and read the real counts back only now and then (a round trip per level was 80 us of an otherwise idle chip for
 // each of the ~12 tail levels that hold a handful of pieces).
 __global__ void k_sort_init(const u64* __restrict__ hitOff, u32 nq, SortLists L, SortTask* __restrict__ big,
-							SortTask* __restrict__ wide, u32* __restrict__ levelCnt, u32* __restrict__ smallCnt)
+							SortTask* __restrict__ wide, u32* __restrict__ levelCnt, u32* __restrict__ smallCnt,
+							const u32* __restrict__ tieFree, u32 radixMax, SortTask* __restrict__ radix)
 {
+	__shared__ u32 rcnt[WG / 64];
+	__shared__ u32 rbase;
 	const u32 q = blockIdx.x * WG + threadIdx.x;
+	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 	SortTask t{0, 0, 0};
 	if (q < nq)
 	{
 		const u64 n = hitOff[q + 1] - hitOff[q];
 		t.start = hitOff[q]; t.n = (u32)n; t.depth = n >= 2 ? 2 * fgsort::floor_log2_((int)n) : 0;
 	}
+	// A segment without tied keys has one sorted order, so it needs no introsort trajectory: k_sort_radix takes it
+	// (count in word [3] of row 0).  Pieces that fit k_sort_lds stay there, and a segment beyond radixMax stays in
+	// the level loop, where it spreads over many waves.
+	const bool isRadix = tieFree && q < nq && t.n > SORT_CAP && t.n <= radixMax && tieFree[q] != 0;
+	if (tieFree)		// uniform
+	{
+		const u64 mR = __ballot(isRadix);
+		if (lane == 0) rcnt[wv] = (u32)__popcll(mR);
+		__syncthreads();
+		if (threadIdx.x == 0)
+		{
+			u32 tot = 0;
+			for (int i = 0; i < WG / 64; ++i) tot += rcnt[i];
+			rbase = tot ? atomicAdd(&levelCnt[3], tot) : 0u;
+		}
+		__syncthreads();
+		u32 o = rbase;
+		for (int i = 0; i < wv; ++i) o += rcnt[i];
+		if (isRadix) radix[o + __popcll(mR & (lane == 0 ? 0ULL : (~0ULL >> (64 - lane))))] = t;
+	}
 	const u32 wideMin = sort_level_mode(L, nq, levelCnt, blockIdx.x == 0 && threadIdx.x == 0);
-	sort_route(t, q < nq, L, wideMin, big, wide, levelCnt, smallCnt);
+	sort_route(t, q < nq && !isRadix, L, wideMin, big, wide, levelCnt, smallCnt);
+}
+
+// Stable least-significant-digit radix sort of one tie-free segment per workgroup, on the record bits of the key only:
+// k_fill emits a query's hits by ascending curPos, so equal records are already in curPos order and a stable sort by
+// record is the (record, curPos) order.  8-bit digits over key bits [curBits, curBits + recBits); the digit counts of
+// every pass come from one read of the keys; a pass walks the segment tile by tile (ranking and reordering as
+// fg_devprim.h's onesweep kernel, the running digit starts in LDS instead of a look-back -- the block is the only
+// writer) from the home arrays to the segment's own ranges of the position scratch or back.  An odd number of passes
+// ends with a copy home.
+#define SORT_RADIX_ITEMS 8
+#define SORT_RADIX_TILE (WG * SORT_RADIX_ITEMS)
+#define SORT_RADIX_MAX_PASSES 4
+__global__ void __launch_bounds__(WG)
+k_sort_radix(const SortTask* __restrict__ tasks, u32 nTasks, u32* hitKey, u32* hitVal, u32* scratch /* read and written in turn */,
+			 u64 nHits, int curBits, int recBits)
+{
+	constexpr int IT = SORT_RADIX_ITEMS, TILE = SORT_RADIX_TILE, NW = WG / 64;
+	__shared__ u32 sKey[TILE];
+	__shared__ u32 sVal[TILE];
+	__shared__ u32 hist[SORT_RADIX_MAX_PASSES][256];	// per pass: digit counts, then the next free slot of each digit
+	__shared__ u32 waveHist[NW][256];
+	__shared__ u32 sTileStart[256];
+	__shared__ u32 sOffs[256];		// destination of slot j of digit d = sOffs[d] + j (mod 2^32)
+	__shared__ u32 shScan[WG / 64 + 1];
+	const u32 ti = blockIdx.x;
+	if (ti >= nTasks) return;
+	const SortTask t = tasks[ti];
+	const u64 start = fg_uni(t.start);
+	const u32 n = fg_uni(t.n);
+	const int nPasses = (recBits + 7) / 8;		// <= SORT_RADIX_MAX_PASSES (host)
+	const u32 lastMask = recBits % 8 ? (1u << (recBits % 8)) - 1u : 255u;
+	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+	const u64 below = lane == 0 ? 0ULL : (~0ULL >> (64 - lane));
+	u32* const kHome = hitKey + start; u32* const vHome = hitVal + start;
+	u32* const kTmp = scratch + start; u32* const vTmp = scratch + nHits + start;
+
+	for (int p = 0; p < nPasses; ++p) hist[p][threadIdx.x] = 0;
+	__syncthreads();
+	for (u32 i = threadIdx.x; i < n; i += WG)
+	{
+		const u32 r = kHome[i] >> curBits;
+		for (int p = 0; p < nPasses; ++p) atomicAdd(&hist[p][(r >> (8 * p)) & (p == nPasses - 1 ? lastMask : 255u)], 1u);
+	}
+	__syncthreads();
+	for (int p = 0; p < nPasses; ++p)
+	{
+		u32 tot;
+		const u32 c = hist[p][threadIdx.x];
+		const u32 ex = block_exscan(c, shScan, &tot);
+		hist[p][threadIdx.x] = ex;
+	}
+	__syncthreads();
+
+	for (int p = 0; p < nPasses; ++p)
+	{
+		const u32* kin = (p & 1) ? kTmp : kHome; const u32* vin = (p & 1) ? vTmp : vHome;
+		u32* kout = (p & 1) ? kHome : kTmp; u32* vout = (p & 1) ? vHome : vTmp;
+		const int shift = curBits + 8 * p;
+		const u32 mask = p == nPasses - 1 ? lastMask : 255u;
+		for (u32 tb = 0; tb < n; tb += TILE)
+		{
+#pragma unroll
+			for (int w = 0; w < NW; ++w) waveHist[w][threadIdx.x] = 0;
+			__syncthreads();
+			// the wave's stretch of the tile: item i of lane l = element i * 64 + l of it (input order = (wave, item, lane))
+			const u32 base = tb + (u32)wv * (64 * IT);
+			u32 k[IT], v[IT], rk[IT];
+#pragma unroll
+			for (int i = 0; i < IT; ++i)
+			{
+				const u32 j = base + (u32)i * 64 + lane;
+				k[i] = j < n ? kin[j] : 0u;
+				v[i] = j < n ? vin[j] : 0u;
+			}
+#pragma unroll
+			for (int i = 0; i < IT; ++i)
+			{
+				const bool valid = base + (u32)i * 64 + lane < n;
+				const u32 d = (k[i] >> shift) & mask;
+				u64 peers = __ballot(valid);		// lanes of this item holding the same digit
+#pragma unroll
+				for (int b = 0; b < 8; ++b)
+				{
+					const bool bit = (d >> b) & 1u;
+					const u64 m = __ballot(bit);
+					peers &= bit ? m : ~m;
+				}
+				const int leader = valid ? (int)__ffsll((unsigned long long)peers) - 1 : lane;
+				u32 pre = 0;
+				if (valid && lane == leader)
+				{
+					pre = waveHist[wv][d];
+					waveHist[wv][d] = pre + (u32)__popcll(peers);
+				}
+				pre = __shfl(pre, leader);
+				rk[i] = pre + (u32)__popcll(peers & below);
+			}
+			__syncthreads();
+			// thread d: digit d of this tile
+			const int d = threadIdx.x;
+			u32 cnt = 0;
+#pragma unroll
+			for (int w = 0; w < NW; ++w) { const u32 c = waveHist[w][d]; waveHist[w][d] = cnt; cnt += c; }
+			u32 tot;
+			const u32 tileStart = block_exscan(cnt, shScan, &tot);
+			sTileStart[d] = tileStart;
+			sOffs[d] = hist[p][d] - tileStart;
+			hist[p][d] += cnt;
+			__syncthreads();
+			// reorder through LDS, so that runs of equal digits leave as neighbouring stores
+#pragma unroll
+			for (int i = 0; i < IT; ++i)
+			{
+				const bool valid = base + (u32)i * 64 + lane < n;
+				const u32 dg = (k[i] >> shift) & mask;
+				if (valid)
+				{
+					const u32 slot = sTileStart[dg] + waveHist[wv][dg] + rk[i];
+					sKey[slot] = k[i];
+					sVal[slot] = v[i];
+				}
+			}
+			__syncthreads();
+#pragma unroll
+			for (int i = 0; i < IT; ++i)
+			{
+				const u32 j = (u32)i * WG + threadIdx.x;
+				if (j < tot)
+				{
+					const u32 kk = sKey[j];
+					const u32 dst = sOffs[(kk >> shift) & mask] + j;		// < n: the digit's slots lie inside the segment
+					kout[dst] = kk;
+					vout[dst] = sVal[j];
+				}
+			}
+			__syncthreads();		// every store of the tile is issued before the LDS tables change
+		}
+		// the next pass reads what other threads of this block stored
+		__threadfence_block();
+		__syncthreads();
+	}
+	if (nPasses & 1)
+		for (u32 i = threadIdx.x; i < n; i += WG) { kHome[i] = kTmp[i]; vHome[i] = vTmp[i]; }
 }
 
 // a workgroup of SORT_WIDE_WAVES waves per task: one partition of a huge piece
@@ -1012,10 +1210,17 @@ T fetchScalar(fg_ctx* c, const T* dptr)
 
 } // namespace
 
-// std::sort order of each segment [segOff[i], segOff[i+1]) of device arrays K, V
+// what took the radix path (fg_debug_sort_pairs32)
+struct SortRadixStats { u64 segments, hits; };
+
+// std::sort order of each segment [segOff[i], segOff[i+1]) of device arrays K, V.
+// dTieFree (32-bit keys record << curBits | curPos of recBits record bits, each segment emitted by ascending curPos;
+// null: none): segments flagged there hold no two equal keys; those of SORT_CAP < n <= FG_SORT_RADIX_MAX (65 536) hits
+// are sorted by k_sort_radix instead of the introsort emulation.  FG_SORT_TIEFREE=0 ignores the flags.
 #define SORT_MAX_LEVELS 128		// rows of level counts (the depth budget of 2 log2 n bounds the levels: n < 2^31)
 template <class KT>
-static void sortSegments(fg_ctx* c, const u64* dSegOff, u32 nSeg, KT* dK, u32* dV, u64 nHits, int curBits = 0)
+static void sortSegments(fg_ctx* c, const u64* dSegOff, u32 nSeg, KT* dK, u32* dV, u64 nHits, int curBits = 0,
+						 const u32* dTieFree = nullptr, int recBits = 0, SortRadixStats* stats = nullptr)
 {
 	hipStream_t s = c->stream;
 	// pieces are disjoint; even the median-of-3 killer stays far below one task per 8 hits
@@ -1023,7 +1228,7 @@ static void sortSegments(fg_ctx* c, const u64* dSegOff, u32 nSeg, KT* dK, u32* d
 	const u64 bigCap = nHits / SORT_CAP + nSeg + 16;
 	c->dTmp32.reserve(std::max<u64>(2 * nHits + 2, 4 * c->hitCapHint + 16));	// the chaining stage wants 4 per hit of it: sized once
 	c->dSortTasks.reserve((size_t)smallCap * sizeof(SortTask));
-	c->dSortBig.reserve((size_t)(6 * bigCap) * sizeof(SortTask));
+	c->dSortBig.reserve((size_t)(7 * bigCap) * sizeof(SortTask));
 	c->dListCnt.reserve(4);
 	c->dSortCnt.reserve(4 * (SORT_MAX_LEVELS + 2) + 4);
 	SortTask* smallT = (SortTask*)c->dSortTasks.p;
@@ -1032,6 +1237,13 @@ static void sortSegments(fg_ctx* c, const u64* dSegOff, u32 nSeg, KT* dK, u32* d
 	SortTask* kids = bigB + bigCap;	// 2 * bigCap
 	SortTask* wideA = kids + 2 * bigCap;
 	SortTask* wideB = wideA + bigCap;
+	SortTask* radixT = wideB + bigCap;		// bigCap > nSeg
+	if (stats) *stats = SortRadixStats{0, 0};
+	{
+		const char* e = getenv("FG_SORT_TIEFREE");
+		if (!std::is_same<KT, u32>::value || recBits <= 0 || recBits > 8 * SORT_RADIX_MAX_PASSES || (e && atoi(e) == 0)) dTieFree = nullptr;
+	}
+	const u32 radixMax = getenv("FG_SORT_RADIX_MAX") ? (u32)atoi(getenv("FG_SORT_RADIX_MAX")) : 65536u;
 	u32* levelCnt = c->dSortCnt.p;							// row l at levelCnt + 4 l
 	u32* smallCnt = c->dSortCnt.p + 4 * (SORT_MAX_LEVELS + 2);
 	const u32 streamMax = getenv("FG_SORT_STREAM_MAX") ? (u32)atoi(getenv("FG_SORT_STREAM_MAX")) : 8192u;
@@ -1046,9 +1258,11 @@ static void sortSegments(fg_ctx* c, const u64* dSegOff, u32 nSeg, KT* dK, u32* d
 	const SortLists lists{smallT, wideMin, smallCap, manyMin, std::max(streamMany, streamMax), streamMax};
 	HIP_CHECK(hipMemsetAsync(c->dSortCnt.p, 0, c->dSortCnt.bytes(), s));
 	{ ScopedK t(c->timer, "k_sort_level");
-	  hipLaunchKernelGGL(k_sort_init, (nSeg + WG - 1) / WG, WG, 0, s, dSegOff, nSeg, lists, bigA, wideA, levelCnt, smallCnt); }
+	  hipLaunchKernelGGL(k_sort_init, (nSeg + WG - 1) / WG, WG, 0, s, dSegOff, nSeg, lists, bigA, wideA, levelCnt, smallCnt,
+						 dTieFree, radixMax, radixT); }
 	// counts of level `lvl` (and the small pieces queued so far) to the host
 	u32 cnt[3] = {0, 0, 0};		// big, small (total), wide
+	u32 nRadix = 0;				// word [3] of row 0
 	auto fetchCounts = [&](int lvl)
 	{
 		c->hScalar.reserve(8);
@@ -1058,8 +1272,24 @@ static void sortSegments(fg_ctx* c, const u64* dSegOff, u32 nSeg, KT* dK, u32* d
 		u32 row[5];
 		memcpy(row, c->hScalar.p, 20);
 		cnt[0] = row[0]; cnt[2] = row[2]; cnt[1] = row[4];
+		if (lvl == 0) nRadix = row[3];
 	};
 	fetchCounts(0);
+	if constexpr (std::is_same<KT, u32>::value)
+		if (nRadix)
+		{
+			// ahead of level 0: its blocks run for as long as a few levels and fill the chip beside their thin tails
+			{ ScopedK t(c->timer, "k_sort_radix");
+			  hipLaunchKernelGGL(k_sort_radix, nRadix, WG, 0, s, radixT, nRadix, dK, dV, c->dTmp32.p, nHits, curBits, recBits); }
+			if (stats)
+			{
+				std::vector<SortTask> h(nRadix);
+				HIP_CHECK(hipMemcpyAsync(h.data(), radixT, (size_t)nRadix * sizeof(SortTask), hipMemcpyDeviceToHost, s));
+				HIP_CHECK(hipStreamSynchronize(s));
+				stats->segments = nRadix;
+				for (const SortTask& r : h) stats->hits += r.n;
+			}
+		}
 	static const bool trace = getenv("FG_SORT_TRACE") != nullptr;
 	static const char* levelNames[32] = {
 		"k_sort_level#00", "k_sort_level#01", "k_sort_level#02", "k_sort_level#03", "k_sort_level#04", "k_sort_level#05",
@@ -1178,6 +1408,37 @@ void fgDebugSortPairs(fg_ctx* c, u64* keys, u32* vals, const u64* segOff, u32 nS
 	HIP_CHECK(hipMemcpyAsync(keys, dK.p, n * 8, hipMemcpyDeviceToHost, s));
 	HIP_CHECK(hipMemcpyAsync(vals, dV.p, n * 4, hipMemcpyDeviceToHost, s));
 	HIP_CHECK(hipStreamSynchronize(s));
+}
+
+// fg_debug_sort_pairs32: the hit sort's 32-bit key form with per-segment tie-free flags, as deviceSub calls it
+void fgDebugSortPairs32(fg_ctx* c, u32* keys, u32* vals, const u64* segOff, u32 nSeg, int curBits, int recBits,
+						const u32* tieFree, u64* radixSegments, u64* radixHits)
+{
+	hipStream_t s = c->stream;
+	const u64 n = segOff[nSeg];
+	*radixSegments = *radixHits = 0;
+	DevBuf<u32> dK, dV, dFlag; DevBuf<u64> dOff;
+	dK.alloc(n + 1); dV.alloc(n + 1); dOff.alloc(nSeg + 1); dFlag.alloc(nSeg + 1);
+	HIP_CHECK(hipMemcpyAsync(dK.p, keys, n * 4, hipMemcpyHostToDevice, s));
+	HIP_CHECK(hipMemcpyAsync(dV.p, vals, n * 4, hipMemcpyHostToDevice, s));
+	HIP_CHECK(hipMemcpyAsync(dOff.p, segOff, (nSeg + 1) * 8ULL, hipMemcpyHostToDevice, s));
+	if (tieFree) HIP_CHECK(hipMemcpyAsync(dFlag.p, tieFree, nSeg * 4ULL, hipMemcpyHostToDevice, s));
+	SortRadixStats st{0, 0};
+	if (nSeg && n) sortSegments<u32>(c, dOff.p, nSeg, dK.p, dV.p, n, curBits, tieFree ? dFlag.p : nullptr, recBits, &st);
+	HIP_CHECK(hipMemcpyAsync(keys, dK.p, n * 4, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(hipMemcpyAsync(vals, dV.p, n * 4, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(hipStreamSynchronize(s));
+	*radixSegments = st.segments; *radixHits = st.hits;
+}
+
+// fg_debug_tie_free: k_fill's flags of the last sub-range this context expanded (the whole call where it was not cut)
+void fgDebugTieFree(fg_ctx* c, u32* out, u32 maxN, u32* firstQuery, u32* n)
+{
+	*firstQuery = c->tieFreeQ0; *n = c->tieFreeN;
+	const u32 m = std::min(maxN, c->tieFreeN);
+	if (!m) return;
+	HIP_CHECK(hipMemcpyAsync(out, c->dTieFree.p, m * 4ULL, hipMemcpyDeviceToHost, c->stream));
+	HIP_CHECK(hipStreamSynchronize(c->stream));
 }
 
 // the build's "frequent enough for a slot" bits where they hold for the queries (fg_ctx.h), or null: every k-mer is
@@ -1388,6 +1649,7 @@ static void deviceSub(fg_ctx* c, const fg_detector_params* p, uint8_t forceLocal
 	while ((1LL << curBits) < (long long)(c->hasQ ? c->qMaxLen : c->maxLen)) ++curBits;
 	while ((1ULL << recBits) < 2ULL * c->nReads) ++recBits;
 	const bool key32 = curBits + recBits <= 32 && !getenv("FG_FORCE_KEY64");
+	c->tieFreeN = 0;
 	// key mode: 0 = 32-bit keys + values; when (record, curPos) need more than 32 bits: 1 = packed 64-bit
 	// records (PK: record, curPos, extPos in one word, 8 bytes per hit in the sort levels instead of 12;
 	// FG_PACKED_KEYS=0 turns it off), else 2 = 64-bit keys + values
@@ -1396,12 +1658,14 @@ static void deviceSub(fg_ctx* c, const fg_detector_params* p, uint8_t forceLocal
 	const int keyMode = key32 ? 0 : ((canPack && wantPack) ? 1 : 2);
 	if (keyMode == 0)
 	{
-		c->dHitKey32.reserve(hitCap + 1); c->dHitVal.reserve(hitCap + 1);
+		c->dHitKey32.reserve(hitCap + 1); c->dHitVal.reserve(hitCap + 1); c->dTieFree.reserve(nq + 1);
 		if (recv) recvFill<u32>(c, recv, callQ0, sub0, nq, nHits, curBits, c->dHitKey32.p, c->dHitVal.p);
 		else { ScopedK t(c->timer, "k_fill");
 		  hipLaunchKernelGGL(k_fill<u32>, nq, WG, 0, s, dQuery, c->dLen.p, qLen, dQKmerOff, k, c->firstId, curBits,
-							 c->dProbe.p, c->dEntries.p, c->dHitOff.p, c->dFiltOff.p, c->dHitKey32.p, c->dHitVal.p, c->dFiltPos.p); }
-		sortSegments<u32>(c, c->dHitOff.p, nq, c->dHitKey32.p, c->dHitVal.p, nHits);
+							 c->dProbe.p, c->dEntries.p, c->dHitOff.p, c->dFiltOff.p, c->dHitKey32.p, c->dHitVal.p, c->dFiltPos.p, c->dTieFree.p); }
+		if (!recv) { c->tieFreeQ0 = callQ0 + sub0; c->tieFreeN = nq; }
+		// the receiver path knows no ties: every query goes through the emulation there
+		sortSegments<u32>(c, c->dHitOff.p, nq, c->dHitKey32.p, c->dHitVal.p, nHits, curBits, recv ? nullptr : c->dTieFree.p, recBits);
 	}
 	else if (keyMode == 1)
 	{
@@ -1409,7 +1673,7 @@ static void deviceSub(fg_ctx* c, const fg_detector_params* p, uint8_t forceLocal
 		if (recv) recvFill<PK>(c, recv, callQ0, sub0, nq, nHits, curBits, (PK*)c->dHitKey.p, (u32*)nullptr);
 		else { ScopedK t(c->timer, "k_fill");
 		  hipLaunchKernelGGL(k_fill<PK>, nq, WG, 0, s, dQuery, c->dLen.p, qLen, dQKmerOff, k, c->firstId, curBits,
-							 c->dProbe.p, c->dEntries.p, c->dHitOff.p, c->dFiltOff.p, (PK*)c->dHitKey.p, (u32*)nullptr, c->dFiltPos.p); }
+							 c->dProbe.p, c->dEntries.p, c->dHitOff.p, c->dFiltOff.p, (PK*)c->dHitKey.p, (u32*)nullptr, c->dFiltPos.p, (u32*)nullptr); }
 		sortSegments<PK>(c, c->dHitOff.p, nq, (PK*)c->dHitKey.p, (u32*)nullptr, nHits, curBits);
 	}
 	else
@@ -1418,7 +1682,7 @@ static void deviceSub(fg_ctx* c, const fg_detector_params* p, uint8_t forceLocal
 		if (recv) recvFill<u64>(c, recv, callQ0, sub0, nq, nHits, curBits, c->dHitKey.p, c->dHitVal.p);
 		else { ScopedK t(c->timer, "k_fill");
 		  hipLaunchKernelGGL(k_fill<u64>, nq, WG, 0, s, dQuery, c->dLen.p, qLen, dQKmerOff, k, c->firstId, 0,
-							 c->dProbe.p, c->dEntries.p, c->dHitOff.p, c->dFiltOff.p, c->dHitKey.p, c->dHitVal.p, c->dFiltPos.p); }
+							 c->dProbe.p, c->dEntries.p, c->dHitOff.p, c->dFiltOff.p, c->dHitKey.p, c->dHitVal.p, c->dFiltPos.p, (u32*)nullptr); }
 		sortSegments<u64>(c, c->dHitOff.p, nq, c->dHitKey.p, c->dHitVal.p, nHits, curBits);
 	}
 	const HitKeyView<u32> hk32{c->dHitKey32.p, c->dHitVal.p, curBits, c->firstId};
@@ -2064,7 +2328,7 @@ void fgProbeHits(fg_ctx* c, const u32* queryIds, u32 nq, u64* hitCounts, const f
 		{ ScopedK t(c->timer, "k_fill");
 		  hipLaunchKernelGGL(k_fill<fg_seed_hit>, cn, WG, 0, s, c->dQuery.p, c->dLen.p, qLen, c->dQKmerOff.p, k, c->firstId, 0,
 							 c->dProbe.p, c->dEntries.p, c->dHitOff.p, c->dFiltOff.p, c->dSeedHits.p + total, (u32*)nullptr,
-							 c->dFiltPos.p); }
+							 c->dFiltPos.p, (u32*)nullptr); }
 		total += chunkHits;
 		qa = qb;
 	}

@@ -58,7 +58,7 @@ ABI_SYMBOLS = ["fg_abi_version", "fg_create", "fg_destroy", "fg_strerror", "fg_l
                "fg_group_set_reads", "fg_group_set_queries", "fg_group_build_index_solid",
                "fg_group_build_index_minimizers", "fg_group_clear_index", "fg_group_overlaps", "fg_group_stats",
                "fg_group_build_info", "fg_debug_freq_accumulate", "fg_debug_group_bin_cuts", "fg_debug_scan",
-               "fg_debug_radix_sort_pairs"]
+               "fg_debug_radix_sort_pairs", "fg_debug_tie_free"]
 
 # struct fg_range_pair: one pair of fg_align_ranges
 RANGE_PAIR_DTYPE = np.dtype([("cur_id", "<u4"), ("ext_id", "<u4"), ("cur_begin", "<i4"), ("cur_end", "<i4"),
@@ -295,7 +295,10 @@ def load_library():
                                             C.c_uint8, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(OverlapBatch)]
         L.fg_kernel_times.argtypes = [C.c_void_p, C.POINTER(KernelTime), C.c_int]
         L.fg_debug_sort_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
-        L.fg_debug_probe_skip_check.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.fg_debug_sort_pairs32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int,
+                                            C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.fg_debug_tie_free.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.fg_debug_probe_skip_check.argtypes =[C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.fg_debug_edit_distances.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.fg_align_cigar_ksw.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.POINTER(CigarBatch)]
@@ -667,6 +670,35 @@ class Context:
         self._check(self.L.fg_debug_sort_pairs(self.h, k.ctypes.data, v.ctypes.data, off.ctypes.data,
                                                len(off) - 1))
         return k, v
+
+    def debug_sort_pairs32(self, keys, seg_off, cur_bits, rec_bits, tie_free=None):
+        """The hit sort in its 32-bit key form (``record << cur_bits | cur_pos``) with per-segment tie-free flags
+        (None: no flags).  Returns (sorted keys, permutation, segments on the radix path, hits on the radix path)."""
+        k = np.ascontiguousarray(keys, np.uint32).copy()
+        off = np.ascontiguousarray(seg_off, np.uint64)
+        v = np.empty(len(k), np.uint32)
+        for i in range(len(off) - 1):
+            a, b = int(off[i]), int(off[i + 1])
+            v[a:b] = np.arange(b - a, dtype=np.uint32)
+        flags = None if tie_free is None else np.ascontiguousarray(tie_free, np.uint32)
+        if flags is not None and len(flags) != len(off) - 1:
+            raise ValueError("one tie-free flag per segment")
+        segs, hits = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.L.fg_debug_sort_pairs32(self.h, k.ctypes.data, v.ctypes.data, off.ctypes.data, len(off) - 1,
+                                                 int(cur_bits), int(rec_bits),
+                                                 None if flags is None else flags.ctypes.data,
+                                                 C.byref(segs), C.byref(hits)))
+        return k, v, int(segs.value), int(hits.value)
+
+    def debug_tie_free(self, max_n):
+        """The seed expansion's tie-free flags of the last sub-range of queries this context expanded: (index of its
+        first query in the call's list, flags).  No flags (empty) on the receiver path and for 64-bit key forms."""
+        out = np.zeros(max(int(max_n), 1), np.uint32)
+        q0, n = C.c_uint32(0), C.c_uint32(0)
+        self._check(self.L.fg_debug_tie_free(self.h, out.ctypes.data, int(max_n), C.byref(q0), C.byref(n)))
+        if n.value > max_n:
+            raise ValueError(f"{n.value} flags, room for {max_n}")
+        return int(q0.value), out[:n.value].copy()
 
     def debug_freq_accumulate(self, dst, src):
         """k_freq_accumulate on the device: ``dst += src`` in place over uint32 (wrapping).  The device copies sit at

@@ -429,6 +429,21 @@ int fg_kernel_times(fg_ctx* ctx, struct fg_kernel_time* out, int max_entries);
 int fg_debug_sort_pairs(fg_ctx* ctx, uint64_t* keys, uint32_t* vals,
                         const uint64_t* seg_off, uint32_t n_seg);
 
+/* Test hook: the same sort in the overlap stage's 32-bit key form, key = record << cur_bits | cur_pos with rec_bits
+ * record bits (cur_bits + rec_bits <= 32), every segment given by ascending cur_pos as the seed expansion emits it.
+ * tie_free (n_seg words, or NULL = none): non-zero promises that the segment holds no two equal keys; such segments
+ * of a middle size are sorted by stable radix passes over the record bits instead of the introsort emulation
+ * (FG_SORT_TIEFREE=0 ignores the flags).  radix_segments / radix_hits: what took that path. */
+int fg_debug_sort_pairs32(fg_ctx* ctx, uint32_t* keys, uint32_t* vals, const uint64_t* seg_off, uint32_t n_seg,
+                          int cur_bits, int rec_bits, const uint32_t* tie_free,
+                          uint64_t* radix_segments, uint64_t* radix_hits);
+
+/* Test hook: the per-query tie-free flags the seed expansion wrote for the last sub-range of queries this context
+ * expanded in an fg_overlaps call (the whole call where it was not cut; none on the option-B receiver path and for
+ * 64-bit key forms): *first_query = index of its first query in the call's query list, *n = its queries, out[i]
+ * (i < min(max_n, *n)) = 1 when no two seed hits of query *first_query + i share (ext_id, cur_pos). */
+int fg_debug_tie_free(fg_ctx* ctx, uint32_t* out, uint32_t max_n, uint32_t* first_query, uint32_t* n);
+
 /* Test hook (host only): the key ranges a group build of `world` members cuts from hist[FG_INDEX_BINS]; member r
  * gets the bins [cuts[r], cuts[r + 1]); cuts has world + 1 entries.  They equal dist.balanced_bin_ranges. */
 int fg_debug_group_bin_cuts(const uint64_t* hist, uint32_t world, uint32_t* cuts);
