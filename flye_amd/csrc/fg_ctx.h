@@ -443,6 +443,8 @@ struct fg_ctx {
 	DevBuf<long long> dPolScore, dPolCells, dPolEdits;
 	// fg_make_bubbles (fg_bubbles.hip): the buffers of one sub-batch, handed out in call order
 	DevBuf<char> dBub[36];
+	// fg_uniform_alignments / fg_contig_consensus (fg_contigcons.hip): likewise
+	DevBuf<char> dCc[40];
 	PinnedBuf<char> hPrim;
 	PinnedBuf<u64> hOff;
 	PinnedBuf<u64> hScalar;		// staging of the counts the host reads between kernels (pinned: no bounce buffer)

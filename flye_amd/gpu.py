@@ -16,6 +16,8 @@ like calls into the reference:
   (src/polishing/bubble_processor.cpp:32-148; without the homopolymer matrix, which the reference never uses)
 * ``BubbleMaker(ctx).make(contigs, alignments_by_contig, err_mode)`` / ``write_bubbles`` / ``uniform_alignments`` /
   ``polish``  (flye/polishing/bubbles.py:87-172 and alignment.py:95-153; alignment records instead of a SAM file)
+* ``ContigConsensus(ctx).consensus(contigs, alignments_by_contig)``  (flye/polishing/consensus.py:52-181, get_consensus
+  without the SAM reader and the FASTA writer)
 
 There is no CPU fallback: if the HIP library or a device is missing every entry
 point raises ``FlyeGpuError``.
@@ -52,6 +54,7 @@ ABI_SYMBOLS = ["fg_abi_version", "fg_create", "fg_destroy", "fg_strerror", "fg_l
                "fg_read_coverage", "fg_release_coverage", "fg_coverage_windows", "fg_coverage_verdict",
                "fg_edge_coverage", "fg_release_edge_coverage",
                "fg_subs_matrix_load", "fg_polish_bubbles", "fg_release_polish", "fg_make_bubbles", "fg_release_bubbles",
+               "fg_uniform_alignments", "fg_release_uniform", "fg_contig_consensus", "fg_release_consensus",
                "fg_index_keep_targets", "fg_index_shard", "fg_probe_hits", "fg_overlaps_from_hits",
                "fg_index_piece_split", "fg_index_scatter_begin", "fg_index_scatter_end", "fg_debug_probe_skip_check",
                "fg_group_create", "fg_group_destroy", "fg_group_size", "fg_group_member", "fg_group_last_error",
@@ -210,6 +213,21 @@ class BubbleBatch(C.Structure):
                 ("num_missmatch", C.POINTER(C.c_int32)), ("nucl", C.POINTER(C.c_uint8)), ("owner_", C.c_void_p)]
 
 
+class UniformResultStruct(C.Structure):
+    """struct fg_uniform_result"""
+    _fields_ = [("n_contigs", C.c_uint32), ("pad_", C.c_uint32), ("n_alignments", C.c_uint64), ("keep", C.POINTER(C.c_uint8)),
+                ("cov_threshold", C.POINTER(C.c_int32)), ("wnd_off", C.POINTER(C.c_uint64)),
+                ("wnd_threshold", C.POINTER(C.c_double)), ("owner_", C.c_void_p)]
+
+
+class ConsensusBatch(C.Structure):
+    """struct fg_consensus_batch"""
+    _fields_ = [("n_contigs", C.c_uint32), ("pad_", C.c_uint32), ("seq_off", C.POINTER(C.c_uint64)), ("seq", C.POINTER(C.c_uint8)),
+                ("prof_off", C.POINTER(C.c_uint64)), ("nucl", C.POINTER(C.c_uint8)), ("match_total", C.POINTER(C.c_int32)),
+                ("num_ins", C.POINTER(C.c_int32)), ("max_match", C.POINTER(C.c_uint8)), ("accepted", C.POINTER(C.c_uint8)),
+                ("ins_off", C.POINTER(C.c_uint64)), ("ins", C.POINTER(C.c_uint8)), ("owner_", C.c_void_p)]
+
+
 class BridgeStats(C.Structure):
     _fields_ = [("device_calls", C.c_uint64), ("reads_computed", C.c_uint64), ("requests", C.c_uint64),
                 ("cache_hits", C.c_uint64), ("cached_overlaps", C.c_uint64), ("reads_ahead", C.c_uint64),
@@ -337,6 +355,12 @@ def load_library():
             [C.c_uint8, C.POINTER(BubbleBatch)]
         L.fg_release_bubbles.argtypes = [C.POINTER(BubbleBatch)]
         L.fg_release_bubbles.restype = None
+        L.fg_uniform_alignments.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 6 + [C.c_uint8, C.POINTER(UniformResultStruct)]
+        L.fg_release_uniform.argtypes = [C.POINTER(UniformResultStruct)]
+        L.fg_release_uniform.restype = None
+        L.fg_contig_consensus.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 8 + [C.c_uint8, C.POINTER(ConsensusBatch)]
+        L.fg_release_consensus.argtypes = [C.POINTER(ConsensusBatch)]
+        L.fg_release_consensus.restype = None
         L.fg_debug_group_bin_cuts.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         L.fg_debug_freq_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
         L.fg_debug_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int]
@@ -589,6 +613,22 @@ class BubbleResult:
     def same_as(self, other):
         return self.__dict__.keys() == other.__dict__.keys() and all(
             (v is None and other.__dict__[k] is None) or np.array_equal(v, other.__dict__[k]) for k, v in self.__dict__.items())
+
+
+class UniformResult(BubbleResult):
+    """fg_uniform_result copied out of its arena: keep (uint8 per alignment), cov_threshold (per contig) and, with
+    want_thresholds, wnd_off / wnd_threshold"""
+
+
+class ConsensusResult(BubbleResult):
+    """fg_consensus_batch copied out of its arena, arrays under the names of the header.  sequence(i) is the string
+    _flatten_profile returns for contig i (bytes, possibly empty); insertion(p) the chosen string of profile position p."""
+
+    def sequence(self, i):
+        return self.seq[int(self.seq_off[i]):int(self.seq_off[i + 1])].tobytes()
+
+    def insertion(self, p):
+        return self.ins[int(self.ins_off[p]):int(self.ins_off[p + 1])].tobytes()
 
 
 class PolishResult:
@@ -1001,6 +1041,77 @@ class Context:
             out["nucl"] = take(b.nucl, npos, np.uint8)
         self.L.fg_release_bubbles(C.byref(b))
         return BubbleResult(**out)
+
+    def uniform_alignments(self, contig_len, contig_aln_off, trg_start, trg_end, err_rate, is_secondary=None,
+                           want_thresholds=False):
+        """fg_uniform_alignments: get_uniform_alignments (flye/polishing/alignment.py:95-153) for a batch of contigs in the
+        layout of make_bubbles.  Returns a UniformResult; keep goes into contig_consensus as ``use``."""
+        cl = np.ascontiguousarray(contig_len, np.int32)
+        n = len(cl)
+        cao = np.ascontiguousarray(contig_aln_off, np.uint64)
+        ts, te = np.ascontiguousarray(trg_start, np.int32), np.ascontiguousarray(trg_end, np.int32)
+        er = np.ascontiguousarray(err_rate, np.float64)
+        sec = np.ascontiguousarray(is_secondary, np.uint8) if is_secondary is not None else None
+        if len(cao) != n + 1 or len(ts) != len(te) or len(ts) != len(er) or (sec is not None and len(sec) != len(ts)) or \
+                (n and int(cao.max()) > len(ts)):
+            raise ValueError("uniform_alignments: offsets outside their arrays")
+        ptr = lambda a: a.ctypes.data if a is not None and len(a) else None
+        r = UniformResultStruct()
+        t0 = time.perf_counter()
+        self._check(self.L.fg_uniform_alignments(self.h, n, ptr(cl), cao.ctypes.data, ptr(ts), ptr(te), ptr(er), ptr(sec),
+                                                 int(bool(want_thresholds)), C.byref(r)))
+        self.last_uniform_seconds = time.perf_counter() - t0
+
+        def take(p, k, dtype):
+            return np.ctypeslib.as_array(p, (k,)).copy() if k else np.zeros(0, dtype)
+
+        out = dict(keep=take(r.keep, int(r.n_alignments), np.uint8), cov_threshold=take(r.cov_threshold, n, np.int32),
+                   wnd_off=None, wnd_threshold=None)
+        if want_thresholds:
+            out["wnd_off"] = take(r.wnd_off, n + 1, np.uint64)
+            out["wnd_threshold"] = take(r.wnd_threshold, int(out["wnd_off"][n]), np.float64)
+        self.L.fg_release_uniform(C.byref(r))
+        return UniformResult(**out)
+
+    def contig_consensus(self, contig_len, contig_aln_off, trg_start, qry_id, col_off, trg_cols, qry_cols, use=None,
+                         want_profile=False):
+        """fg_contig_consensus: _contig_profile (after get_uniform_alignments) and _flatten_profile of the reference's
+        flye/polishing/consensus.py for a batch of contigs in the layout of make_bubbles; qry_id numbers the reads, use
+        (uint8 per alignment, None: all) selects the alignments that take part.  Returns a ConsensusResult."""
+        cl = np.ascontiguousarray(contig_len, np.int32)
+        n = len(cl)
+        cao = np.ascontiguousarray(contig_aln_off, np.uint64)
+        ts, qi = np.ascontiguousarray(trg_start, np.int32), np.ascontiguousarray(qry_id, np.int32)
+        us = np.ascontiguousarray(use, np.uint8) if use is not None else None
+        co = np.ascontiguousarray(col_off, np.uint64)
+        tc, qc = np.frombuffer(bytes(trg_cols), np.uint8), np.frombuffer(bytes(qry_cols), np.uint8)
+        if len(cao) != n + 1 or len(tc) != len(qc) or len(ts) != len(qi) or (us is not None and len(us) != len(ts)) or \
+                (n and int(cao.max()) > len(ts)) or (len(ts) and len(co) != len(ts) + 1) or (len(co) and int(co.max()) > len(tc)):
+            raise ValueError("contig_consensus: offsets outside their arrays")
+        ptr = lambda a: a.ctypes.data if a is not None and len(a) else None
+        b = ConsensusBatch()
+        t0 = time.perf_counter()
+        self._check(self.L.fg_contig_consensus(self.h, n, ptr(cl), cao.ctypes.data, ptr(ts), ptr(qi), ptr(us), ptr(co), ptr(tc),
+                                               ptr(qc), int(bool(want_profile)), C.byref(b)))
+        self.last_consensus_seconds = time.perf_counter() - t0
+
+        def take(p, k, dtype):
+            return np.ctypeslib.as_array(p, (k,)).copy() if k else np.zeros(0, dtype)
+
+        so = take(b.seq_off, n + 1, np.uint64)
+        out = dict(seq_off=so, seq=take(b.seq, int(so[n]), np.uint8))
+        for k in ("prof_off", "nucl", "match_total", "num_ins", "max_match", "accepted", "ins_off", "ins"):
+            out[k] = None
+        if want_profile:
+            out["prof_off"] = take(b.prof_off, n + 1, np.uint64)
+            npos = int(out["prof_off"][n])
+            for k, t in (("nucl", np.uint8), ("match_total", np.int32), ("num_ins", np.int32), ("max_match", np.uint8),
+                         ("accepted", np.uint8)):
+                out[k] = take(getattr(b, k), npos, t)
+            out["ins_off"] = np.ctypeslib.as_array(b.ins_off, (npos + 1,)).copy()
+            out["ins"] = take(b.ins, int(out["ins_off"][npos]), np.uint8)
+        self.L.fg_release_consensus(C.byref(b))
+        return ConsensusResult(**out)
 
     def edge_coverage(self, window, recs, aln, aln_off, first_ext_id, edge_of, edge_len, want_vectors=True):
         """fg_edge_coverage: the window coverage of MultiplicityInferer::estimateCoverage (multiplicity_inferer.cpp:
@@ -1905,6 +2016,14 @@ class BubbleMaker:
                 kept.append(aln)
         return kept
 
+    @staticmethod
+    def uniform_alignments_device(ctx, alignments, seq_len):
+        """the same list through fg_uniform_alignments (Context.uniform_alignments)"""
+        res = ctx.uniform_alignments([seq_len], [0, len(alignments)], [a.trg_start for a in alignments],
+                                     [a.trg_end for a in alignments], [a.err_rate for a in alignments],
+                                     [bool(a.is_secondary) for a in alignments])
+        return [a for a, k in zip(alignments, res.keep) if k]
+
     def make(self, contigs, alignments_by_contig, err_mode, want_profile=False):
         """make_bubbles for the contigs in the given order -> (bubbles, coverage_stats, mean_aln_error); bubbles is a list
         of (contig id, position, consensus bytes, [branch bytes]).  mean_aln_error is sum / (n + 1) over the profiled
@@ -1943,3 +2062,47 @@ class BubbleMaker:
         upper = lambda a: np.frombuffer(a.tobytes().upper(), np.uint8)
         return bubbles, self.ctx.polish_bubbles(matrix, upper(r.cand), r.cand_off, upper(r.branches), r.branch_off,
                                                 r.bubble_branch_off, fix_dinucleotides, want_steps)
+
+
+class ContigConsensus:
+    """Mirror of the reference's get_consensus (flye/polishing/consensus.py:52-105) on fg_uniform_alignments and
+    fg_contig_consensus.  Alignments are records with the fields of the reference's Alignment tuple (qry_id, trg_start,
+    trg_end, trg_seq, qry_seq, err_rate, is_secondary are read); contigs are records with id and length.  SAM parsing and
+    FASTA writing stay with the caller."""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+        self.result, self.uniform, self.aln_errors = None, None, []
+
+    def consensus(self, contigs, alignments_by_contig, uniform=True, want_profile=False):
+        """-> ({contig id: sequence} without the empty ones, mean_aln_error).  mean_aln_error is sum / (n + 1) over the
+        alignments that took part, summed in contig order (the reference sums in the order its workers finish, so its
+        last bits depend on the run).  The strings of qry_id are numbered per contig in the order they first appear."""
+        lists = [alignments_by_contig.get(c.id, []) for c in contigs]
+        alns = [a for lst in lists for a in lst]
+        aln_off = np.cumsum([0] + [len(lst) for lst in lists])
+        lengths = [c.length for c in contigs]
+        starts = [a.trg_start for a in alns]
+        qry_id = []
+        for lst in lists:
+            number = {}
+            qry_id += [number.setdefault(a.qry_id, len(number)) for a in lst]
+        use = None
+        if uniform:
+            self.uniform = self.ctx.uniform_alignments(lengths, aln_off, starts, [a.trg_end for a in alns],
+                                                       [a.err_rate for a in alns], [bool(a.is_secondary) for a in alns])
+            use = self.uniform.keep
+        res = self.ctx.contig_consensus(lengths, aln_off, starts, qry_id, np.cumsum([0] + [len(a.trg_seq) for a in alns]),
+                                        "".join(a.trg_seq for a in alns).encode("latin-1"),
+                                        "".join(a.qry_seq for a in alns).encode("latin-1"), use, want_profile)
+        self.result = res
+        self.aln_errors = [a.err_rate for k, a in enumerate(alns) if use is None or use[k]]
+        total = 0.0
+        for e in self.aln_errors:
+            total += e
+        out = {}
+        for i, c in enumerate(contigs):
+            seq = res.sequence(i)
+            if len(seq) > 0:
+                out[c.id] = seq.decode("latin-1")
+        return out, total / (len(self.aln_errors) + 1)

@@ -844,6 +844,79 @@ int  fg_make_bubbles(fg_ctx* ctx, const struct fg_bubble_params* params, uint32_
                      const uint8_t* qry_cols, uint8_t want_profile, struct fg_bubble_batch* out);
 void fg_release_bubbles(struct fg_bubble_batch* b);
 
+/* get_uniform_alignments (flye/polishing/alignment.py:95-153): the per-window coverage cap that both _contig_profile
+ * (consensus.py:114) and make_bubbles call first, for a batch of contigs in the layout of fg_make_bubbles.  Contig i has
+ * n_w = contig_len[i] / 100 + 1 windows and the alignments contig_aln_off[i] .. contig_aln_off[i+1]; alignment a covers the
+ * windows [trg_start / 100, trg_end / 100) (none when trg_end < trg_start, as on a circular contig), adds its err_rate to
+ * the list of each and, unless is_secondary[a] (NULL: none is), one to wnd_primary_cov.  With s the sorted primary
+ * coverages and m2 twice their median (2 s[n_w / 2] for odd n_w, else s[n_w / 2 - 1] + s[n_w / 2]), cov_threshold =
+ * max(5 * m2 / 8, 10) in integers: the reference's int(1.25 * median) is exact in double for these values.  A window of
+ * more than cov_threshold entries has the threshold element cov_threshold of its ascending list, else 1.0; keep[a] = 1
+ * when good > floor(total / 2), good = the alignment's windows with err_rate <= threshold, total = trg_end / 100 -
+ * trg_start / 100 (an alignment inside one window is dropped, one with negative total is kept).  All compares are exact.
+ * want_thresholds also returns the windows' thresholds, contig i at wnd_off[i] .. wnd_off[i+1].
+ * The context lends its device and stream.  Sub-batches of whole contigs of at most FG_UNIFORM_BATCH_PAIRS (environment,
+ * default 2^26) (alignment, window) pairs; the result does not depend on the cut; FG_ERR_NOMEM: a contig that alone needs
+ * more.  FG_ERR_ARG, found before any device work: NULL where something is read; decreasing offsets; contig_len < 0;
+ * trg_start < 0 or trg_end < 0; max(trg_start, trg_end) / 100 > contig_len / 100 (the reference raises IndexError); an
+ * err_rate that is NaN or negative.  n_contigs = 0 gives an empty result. */
+struct fg_uniform_result {
+	uint32_t  n_contigs;
+	uint32_t  pad_;
+	uint64_t  n_alignments;
+	uint8_t*  keep;               /* n_alignments, from contig_aln_off[0] on */
+	int32_t*  cov_threshold;      /* per contig */
+	uint64_t* wnd_off;            /* want_thresholds: n_contigs + 1 */
+	double*   wnd_threshold;      /* want_thresholds */
+	void*     owner_;
+};
+int  fg_uniform_alignments(fg_ctx* ctx, uint32_t n_contigs, const int32_t* contig_len, const uint64_t* contig_aln_off,
+                           const int32_t* trg_start, const int32_t* trg_end, const double* err_rate,
+                           const uint8_t* is_secondary, uint8_t want_thresholds, struct fg_uniform_result* out);
+void fg_release_uniform(struct fg_uniform_result* r);
+
+/* The reference's consensus stage (flye/polishing/consensus.py:108-181: _contig_profile after get_uniform_alignments, and
+ * _flatten_profile) for a batch of contigs.  The contig and alignment arrays are those of fg_make_bubbles (offsets need
+ * not start at zero; trg_end and circularity are not read).  qry_id[a] is the caller's number for aln.qry_id: alignments
+ * of one contig with the same number are the same read.  Only alignments with use[a] != 0 take part (NULL: all), in list
+ * order: the keep[] of fg_uniform_alignments goes here as it is.
+ * Both shift_gaps passes run first (see fg_make_bubbles).  A non-gap target column c lands at trg_start + c, wrapped once
+ * at contig_len; a target-gap column at the position before it (before position 0: contig_len - 1).  A column with a
+ * target gap and a query base appends the base to insertions[qry_id] of its position, in list order of the alignments,
+ * then column order; every other column sets nucl to the target byte (the last writer wins; a gap against a gap sets '-')
+ * and counts matches[query byte].  Per position: max_match = the smallest byte among those of the largest count (nucl
+ * when nothing matched), max_insert = the most frequent insertion string, ties to the smallest in byte order (a proper
+ * prefix is smaller); the sequence takes max_match unless it is '-', then max_insert when num_ins > match_total / 2
+ * (num_ins = the reads with an insertion there, match_total = the sum of matches).  Bytes below 128, case kept.
+ * want_profile also returns, per position, nucl ('-' where nothing set it), match_total, num_ins, max_match, accepted
+ * (max_insert went into the sequence) and max_insert itself (empty without insertions) behind ins_off.
+ * Sub-batches of whole contigs of at most FG_CONSENSUS_BATCH_COLS (environment, default 2^27) columns plus positions and,
+ * as a switch for tests, FG_CONSENSUS_BATCH_CONTIGS contigs; the result depends on neither.  FG_ERR_NOMEM: a contig that
+ * alone exceeds the budget.  FG_ERR_ARG, found before any device work: NULL out or a NULL array where something must be
+ * read; an offset array that decreases; a byte >= 128; contig_len < 0; and, for an alignment in use (the positions of
+ * the others are not looked at): trg_start outside [0, contig_len), more non-gap target columns than contig_len, a contig
+ * of length 0.  n_contigs = 0 gives an empty batch (seq_off = {0}). */
+struct fg_consensus_batch {
+	uint32_t  n_contigs;
+	uint32_t  pad_;
+	uint64_t* seq_off;            /* n_contigs + 1 */
+	uint8_t*  seq;                /* contig i at seq_off[i] .. seq_off[i+1], possibly empty */
+	uint64_t* prof_off;           /* want_profile: n_contigs + 1, into the arrays below */
+	uint8_t*  nucl;
+	int32_t*  match_total;
+	int32_t*  num_ins;
+	uint8_t*  max_match;
+	uint8_t*  accepted;
+	uint64_t* ins_off;            /* positions + 1 */
+	uint8_t*  ins;                /* max_insert of position p at ins_off[p] .. ins_off[p+1] */
+	void*     owner_;
+};
+int  fg_contig_consensus(fg_ctx* ctx, uint32_t n_contigs, const int32_t* contig_len, const uint64_t* contig_aln_off,
+                         const int32_t* trg_start, const int32_t* qry_id, const uint8_t* use, const uint64_t* col_off,
+                         const uint8_t* trg_cols, const uint8_t* qry_cols, uint8_t want_profile,
+                         struct fg_consensus_batch* out);
+void fg_release_consensus(struct fg_consensus_batch* b);
+
 #ifdef __cplusplus
 }
 #endif
