@@ -636,6 +636,18 @@ int fg_debug_probe_skip_check(fg_ctx* c, uint64_t* clear_bits, uint64_t* violati
 	});
 }
 
+int fg_debug_chain_lazy(fg_ctx* c, uint64_t out[6])
+{
+	if (!c || !out) return FG_ERR_ARG;
+	return guarded(c, [&]()
+	{
+		HIP_CHECK(hipSetDevice(c->device));
+		u64 h[6];
+		fgDebugChainLazy(c, h);
+		for (int i = 0; i < 6; ++i) out[i] = h[i];
+	});
+}
+
 int fg_debug_edit_distances(fg_ctx* c, uint32_t n_pairs, int use_hpc, int32_t* out_dist, int32_t* out_len_a,
 							int32_t* out_len_b)
 {

@@ -29,6 +29,8 @@ struct ChainParams {
 	int onlyMaxExt;
 	int keepAln;		// the DP's back pointers must survive the backtracking (k_chain_matches re-walks them)
 	int ablate;			// timing experiments only (FG_ABLATE env; results become wrong)
+	int lazy;			// onlyMaxExt and FG_CHAIN_LAZY not 0: try lazy_primary before the full backtracking stage
+	unsigned long long* lazyCnt;	// FG_LAZY_STRIPES rows of 8 counters (fg_debug_chain_lazy)
 };
 
 namespace {
@@ -612,6 +614,124 @@ __device__ __forceinline__ i32 fast_score_order(const i32 n, const i32* score, c
 // k_chain_finish<global> went from 5.9 to 6.6 ms -- its scattered 4-byte stores are what it waits for.  The bitonic
 // network on words in LDS for groups of 257..1024 hits: HiFi 87 -> 82 ms, bench workload 5.7 -> 6.3 ms: dropped too.)
 
+// ---- the only_max_ext primary without the score order and the chain walks -------------------------------------------
+// With only_max_ext the stage keeps ONE candidate per group.  The DP leaves element 0 with score 0 and no back pointer,
+// every other element without one (a root) with score exactly k, every element with one (live) with score > k, and
+// back[i] < i.  Let e* be the live element of the strictly largest score.  It is visited first under any tie handling
+// of std::sort and nothing is consumed yet, so its candidate is (root(e*), e*, nodes on the path, score[e*] -
+// score[root] + k - 1).  A later candidate from a start s' ends at a root or at a consumed node, whose score is >=
+// that of root(s'), so it scores at most score[s'] - score[root(s')] + k - 1; when no live element can be rooted at a
+// lower-scoring root than e* (e*'s root is element 0, or nothing points at element 0) that is strictly below e*'s
+// candidate.  If e*'s candidate also passes overlapTest it is the unique maximum of extOverlaps, hence front() after
+// the candidates' std::sort whatever that does with ties: the primary.  Anything else -- a tied top
+// score, the root condition, a failed overlapTest -- leaves every array untouched and the group takes the full path.
+// Counters of fg_debug_chain_lazy: one row of LZ_ROW per block modulo FG_LAZY_STRIPES, so that no single address
+// serialises the atomics of a whole grid (lane 0 bumps "entered" and one outcome per group).
+enum { LZ_ENTERED = 0, LZ_FAST, LZ_NOLIVE, LZ_TIE, LZ_ROOT, LZ_TEST, LZ_ROW = 8 };
+__device__ __forceinline__ void lazy_count(const ChainParams& P, int what)
+{
+	if ((threadIdx.x & 63) == 0)
+		atomicAdd(&P.lazyCnt[(size_t)(blockIdx.x & (FG_LAZY_STRIPES - 1)) * LZ_ROW + what], 1ULL);
+}
+
+// true: the group is finished (its primary written, or it has no candidate at all).  stage: LDS for n back pointers
+// (groups of the global-scratch class up to BT_CAP hits: the reduction's loads fill it, the walk reads it); ja / jb:
+// n u32 each of LDS (USE_LDS only).
+template <bool USE_LDS, int BT_CAP>
+__device__ __forceinline__ bool lazy_primary(const ChainParams& P, const i32 n, const u32 curId, const u32 extId, const i32 curLen,
+											 const i32 extLen, const u32* cur, const u32* ext, const i32* score, const i32* back,
+											 i32* stage, u32* ja, u32* jb, int4* cd, u32* primCountG)
+{
+	const int lane = threadIdx.x & 63;
+	const bool staged = !USE_LDS && BT_CAP > 0 && n <= BT_CAP;
+	i32 bs = I32_MIN, bi = 0;
+	bool tie = false, toZero = false;
+#pragma unroll 4
+	for (i32 i = lane; i < n; i += 64)
+	{
+		i32 b, s;
+		if (USE_LDS)
+		{
+			b = back[i]; s = score[i];
+			ja[i] = b == -1 ? (u32)i << 16 : ((u32)b << 16) | 1u;	// for the chain of e* below
+		}
+		else
+		{
+			b = __hip_atomic_load(&back[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+			s = __hip_atomic_load(&score[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+			if (staged) stage[i] = b;
+		}
+		toZero |= b == 0;
+		if (b != -1)
+		{
+			tie = s == bs ? true : (s > bs ? false : tie);
+			bi = s > bs ? i : bi;
+			bs = max(bs, s);
+		}
+	}
+	const i32 top = __builtin_amdgcn_readlane(wave_incl_max(bs), 63);
+	if (top == I32_MIN) { lazy_count(P, LZ_NOLIVE); return true; }	// no chain start: *primCountG stays 0 as k_group_list left it
+	const u64 topM = __builtin_amdgcn_ballot_w64(bs == top);
+	if ((topM & (topM - 1)) || __builtin_amdgcn_ballot_w64(tie && bs == top)) { lazy_count(P, LZ_TIE); return false; }
+	const i32 last = __builtin_amdgcn_readlane(bi, __builtin_amdgcn_readfirstlane(__ffsll((long long)topM) - 1));
+	const bool anyToZero = __builtin_amdgcn_ballot_w64(toZero) != 0;
+	// root and length of e*'s chain, read only
+	i32 first = last, chainLength = 0;
+	if (USE_LDS)
+	{
+		// Pointer jumping over the (ancestor << 16 | hops) words the reduction left in ja (the score order's arrays are
+		// still free; <= 1024 hits: both halves fit), a root pointing at itself, doubling every chain's step per round
+		// until e*'s ancestor is a root: <= 8 rounds for 256 hits.  Only elements up to e* matter (back[i] < i).
+		// (Bench workload, k_chain_small by itself / beside the side streams: full path 10.2 / 18.8 ms, this 8.0 /
+		// 13.2 ms; a plain walk down sBack -- one dependent LDS read per node -- 8.9 / 14.1 ms.)
+		u32 *src = ja, *dst = jb;
+		wsort::wave_mem_fence();
+		while (true)
+		{
+			const u32 w = fg_uni(src[last]), a = w >> 16;
+			if ((fg_uni(src[a]) >> 16) == a) { first = (i32)a; chainLength = (i32)(w & 0xffffu) + 1; break; }
+			for (i32 i = lane; i <= last; i += 64)
+			{
+				const u32 w1 = src[i], w2 = src[w1 >> 16];
+				dst[i] = (w2 & 0xffff0000u) | ((w1 + w2) & 0xffffu);
+			}
+			wsort::wave_mem_fence();
+			u32* t = src; src = dst; dst = t;
+		}
+	}
+	else
+	{
+		// the 64-entry register window of the full walk (finish_group), without its stores
+		if (staged) wsort::wave_mem_fence();
+		i32 wbase = -0x40000000, win = -1, pos = last;
+		while (true)
+		{
+			if (pos < wbase || pos >= wbase + 64)
+			{
+				wbase = max(0, pos - 63);
+				if (staged) win = wbase + lane < n ? stage[wbase + lane] : -1;
+				else win = wbase + lane < n ? __hip_atomic_load(&back[wbase + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : -1;
+			}
+			const i32 np = __builtin_amdgcn_readlane(win, __builtin_amdgcn_readfirstlane(pos - wbase));
+			first = pos;
+			++chainLength;
+			if (np == -1) break;
+			pos = np;
+		}
+	}
+	if (first != 0 && anyToZero) { lazy_count(P, LZ_ROOT); return false; }
+	const i32 cb = (i32)cur[first], eb = (i32)ext[first];
+	const i32 ce = (i32)cur[last] + P.k - 1, ee = (i32)ext[last] + P.k - 1;
+	if (!overlap_test(P, curId, extId, curLen, extLen, cb, ce, eb, ee)) { lazy_count(P, LZ_TEST); return false; }
+	if (lane == 0)
+	{
+		cd[0] = make_int4(first, last, chainLength, top - score[first] + P.k - 1);
+		*primCountG = 1;
+	}
+	lazy_count(P, LZ_FAST);
+	return true;
+}
+
 // ---- finish ------------------------------------------------------------------------------
 // One group's backtracking stage on one wave (the body of k_chain_finish and of the fused small-group kernel):
 // score / back: the DP's arrays (LDS when USE_LDS, else the group's global ones; back is consumed), okey / oval:
@@ -624,6 +744,9 @@ __device__ __forceinline__ void finish_group(const ChainParams& P, const i32 n, 
 {
 	const int lane = threadIdx.x & 63;
 	const int k = P.k;
+	lazy_count(P, LZ_ENTERED);
+	if (P.lazy && lazy_primary<USE_LDS, BT_CAP>(P, n, curId, extId, curLen, extLen, cur, ext, score, back, btLds, okey, oval, cd, primCountG))
+		return;
 	// chain starts in descending score order, ties as std::sort leaves them (overlap.cpp:331-334)
 	i32 nOrder = -1;		// entries of oval to visit
 	if (USE_LDS && !(P.ablate & 64))
@@ -995,6 +1118,8 @@ void fgChainStage(fg_ctx* c, const fg_detector_params* p, uint8_t forceLocal, u6
 	cp.onlyMaxExt = p->only_max_ext ? 1 : 0;
 	cp.keepAln = p->keep_alignment ? 1 : 0;
 	cp.ablate = getenv("FG_ABLATE") ? atoi(getenv("FG_ABLATE")) : 0;
+	cp.lazy = cp.onlyMaxExt && !(getenv("FG_CHAIN_LAZY") && atoi(getenv("FG_CHAIN_LAZY")) == 0);
+	cp.lazyCnt = c->dLazyCnt.p;
 	if (!nGroups) return;
 	const i32* qLen = c->hasQ ? c->dQLen.p : c->dLen.p;
 	// smallest group size that can still have >= minUnique distinct query positions

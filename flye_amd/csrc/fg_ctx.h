@@ -392,6 +392,9 @@ struct fg_ctx {
 	PinnedBuf<u32> hMatchCnt;
 	DevBuf<char> dSortTasks, dSortBig;
 	DevBuf<unsigned long long> dSmallElems;	// DP elements in groups of <= 256 hits (work counter)
+	// fg_debug_chain_lazy: FG_LAZY_STRIPES rows of 8 counters the chaining kernels bump once per group (fg_chain.hip),
+	// zeroed per fg_overlaps call; the second lane's is a view of this one
+	DevBuf<unsigned long long> dLazyCnt;
 	DevBuf<u32> dSortCnt;		// task counts of the sort's level loop, a row per level (fg_overlap.hip)
 	DevBuf<u32> dTieFree;		// per query, written by k_fill: 1 = no two of its hits share (extId, curPos)
 	u32 tieFreeQ0 = 0, tieFreeN = 0;	// the queries of the call dTieFree speaks of (0: the last sub-range had no flags)
@@ -791,6 +794,8 @@ void fgDebugSortPairs32(fg_ctx* c, u32* keys, u32* vals, const u64* segOff, u32 
 						const u32* tieFree, u64* radixSegments, u64* radixHits);
 void fgDebugTieFree(fg_ctx* c, u32* out, u32 maxN, u32* firstQuery, u32* n);
 void fgDebugProbeSkipCheck(fg_ctx* c, u64* clearBits, u64* violations);
+#define FG_LAZY_STRIPES 64
+void fgDebugChainLazy(fg_ctx* c, u64 out[6]);
 void fgDebugEditDistances(fg_ctx* c, u32 nPairs, int useHpc, i32* outDist, i32* outLenA, i32* outLenB);
 // option B: seed hits gathered from index shards, as the overlap stage takes them in place of its own seed
 // expansion.  Per query qi of the call and source s: the run of hits[runStart[qi * nSrc + s] ..] of runLen[..]

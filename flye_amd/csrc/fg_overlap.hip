@@ -1390,6 +1390,18 @@ void fgDebugProbeSkipCheck(fg_ctx* c, u64* clearBits, u64* violations)
 	*clearBits = h[0]; *violations = h[1];
 }
 
+// fg_debug_chain_lazy: the striped per-group counters of the last fg_overlaps call (fg_chain.hip), summed
+void fgDebugChainLazy(fg_ctx* c, u64 out[6])
+{
+	for (int i = 0; i < 6; ++i) out[i] = 0;
+	if (!c->dLazyCnt.p) return;
+	std::vector<unsigned long long> h((size_t)FG_LAZY_STRIPES * 8);
+	HIP_CHECK(hipMemcpyAsync(h.data(), c->dLazyCnt.p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+	HIP_CHECK(hipStreamSynchronize(c->stream));
+	for (int r = 0; r < FG_LAZY_STRIPES; ++r)
+		for (int i = 0; i < 6; ++i) out[i] += h[(size_t)r * 8 + i];
+}
+
 void fgSortSegments(fg_ctx* c, const u64* dSegOff, u32 nSeg, u64* dKeys, u32* dVals, u64 n)
 {
 	if (nSeg && n) sortSegments<u64>(c, dSegOff, nSeg, dKeys, dVals, n);
@@ -1841,6 +1853,7 @@ static fg_ctx* laneTwo(fg_ctx* c)
 	l->dKeyOff.alias(c->dKeyOff); l->dEntries.alias(c->dEntries); l->dTable.alias(c->dTable); l->dIndexedBits.alias(c->dIndexedBits); l->dMaybeBits.alias(c->dMaybeBits);
 	l->dQuery.alias(c->dQuery); l->dQKmerOff.alias(c->dQKmerOff); l->dProbe.alias(c->dProbe);
 	l->dCntA.alias(c->dCntA); l->dCntB.alias(c->dCntB);
+	l->dLazyCnt.alias(c->dLazyCnt);
 	return l;
 }
 
@@ -1870,6 +1883,9 @@ void fgOverlaps(fg_ctx* c, const fg_detector_params* p, const u32* queryIds, u32
 	} evp(c->timer);
 	const hipEvent_t evA = evp.a, evB = evp.b;
 	HIP_CHECK(hipEventRecord(evA, s));
+	// (ahead of the probes, whose host synchronisation orders it before anything either lane launches)
+	c->dLazyCnt.reserve(FG_LAZY_STRIPES * 8);
+	HIP_CHECK(hipMemsetAsync(c->dLazyCnt.p, 0, FG_LAZY_STRIPES * 8 * sizeof(unsigned long long), s));
 
 	BatchOwner* own = BatchOwner::acquire();
 	out->owner_ = own;

@@ -61,7 +61,7 @@ ABI_SYMBOLS = ["fg_abi_version", "fg_create", "fg_destroy", "fg_strerror", "fg_l
                "fg_group_set_reads", "fg_group_set_queries", "fg_group_build_index_solid",
                "fg_group_build_index_minimizers", "fg_group_clear_index", "fg_group_overlaps", "fg_group_stats",
                "fg_group_build_info", "fg_debug_freq_accumulate", "fg_debug_group_bin_cuts", "fg_debug_scan",
-               "fg_debug_radix_sort_pairs", "fg_debug_tie_free"]
+               "fg_debug_radix_sort_pairs", "fg_debug_tie_free", "fg_debug_chain_lazy"]
 
 # struct fg_range_pair: one pair of fg_align_ranges
 RANGE_PAIR_DTYPE = np.dtype([("cur_id", "<u4"), ("ext_id", "<u4"), ("cur_begin", "<i4"), ("cur_end", "<i4"),
@@ -317,6 +317,7 @@ def load_library():
                                             C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.fg_debug_tie_free.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.fg_debug_probe_skip_check.argtypes =[C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.fg_debug_chain_lazy.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         L.fg_debug_edit_distances.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.fg_align_cigar_ksw.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.POINTER(CigarBatch)]
@@ -776,6 +777,14 @@ class Context:
         clear, bad = C.c_uint64(0), C.c_uint64(0)
         self._check(self.L.fg_debug_probe_skip_check(self.h, C.byref(clear), C.byref(bad)))
         return int(clear.value), int(bad.value)
+
+    def debug_chain_lazy(self):
+        """How the groups of the last fg_overlaps call left the chaining stage's backtracking: dict of ``entered``,
+        ``fast`` (primary taken straight from the DP tables), ``no_live`` (no chain start) and the fallbacks to the
+        full path ``tied_top``, ``root`` and ``overlap_test``."""
+        out = (C.c_uint64 * 6)()
+        self._check(self.L.fg_debug_chain_lazy(self.h, out))
+        return dict(zip(("entered", "fast", "no_live", "tied_top", "root", "overlap_test"), (int(x) for x in out)))
 
     def debug_edit_distances(self, n_pairs, use_hpc=False):
         """Device edit-distance kernels on the pairs (read 2i, read 2i+1) of the container;

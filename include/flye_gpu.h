@@ -479,6 +479,15 @@ int fg_debug_radix_sort_pairs(fg_ctx* ctx, uint64_t* keys, uint64_t* vals, uint6
  * k-mer is then looked up.  The environment switch FG_PROBE_SKIP=0 makes the overlap stage ignore the bits. */
 int fg_debug_probe_skip_check(fg_ctx* ctx, uint64_t* clear_bits, uint64_t* violations);
 
+/* Test hook for the lazy primary of the chaining stage (only_max_ext): how the groups of the last fg_overlaps call on
+ * this context left the backtracking stage.  out[0]: groups that reached it (through the prefilter and the DP);
+ * out[1]: groups whose primary was taken straight from the DP tables -- the live element of the strictly largest
+ * score, its chain read once, no score order and no consuming walks; out[2]: groups without any chain start (no
+ * candidate); out[3..5]: groups that took the full path because the top score was tied, because an element points at
+ * element 0 while the best chain is rooted elsewhere, or because the best chain failed overlapTest.  With
+ * only_max_ext = 0, or with the environment switch FG_CHAIN_LAZY=0, out[1..5] are 0.  All 0 before the first call. */
+int fg_debug_chain_lazy(fg_ctx* ctx, uint64_t out[6]);
+
 /* Test hook: the exact global edit distance (what edlibAlign(NW, TASK_DISTANCE, k = -1) returns,
  * reference src/sequence/alignment.cpp:233-238, src/sequence/edlib.cpp:141-296) of n_pairs string
  * pairs through the device kernels of the base-level divergence step.  Pair i = the forward
