@@ -939,13 +939,13 @@ void kswAlignDevice(fg_ctx* c, u32 nPairs, const uint8_t* dTrgP, const u64* trgO
 			{
 				const u32 cnt = (u32)order[cls].size();
 				if (!cnt) continue;
-				ScopedK t(c->timer, cls == 0 ? "k_ksw_extz2" : "k_ksw_extz2_lds");
+				// state in registers (FG_KSW_REG=0: in LDS rings, the round-2 form)
+				const bool regForm = !(getenv("FG_KSW_REG") && atoi(getenv("FG_KSW_REG")) == 0);
+				ScopedK t(c->timer, cls == 0 ? "k_ksw_extz2" : regForm ? "k_ksw_extz2_reg" : "k_ksw_extz2_lds");
 				const unsigned g = std::min<unsigned>(cnt, 8192u);
 				const u32* ord = dOrder.p + at;
 #define KSW_ARGS dJobs.p, ord, cnt, dTrgP, dQryP, dScratch.p, dCig.p, dN.p, dDense.p, dTotal.p, dBase.p
 				const u32 dbg = getenv("FG_KSW_DEBUG") ? (u32)atoi(getenv("FG_KSW_DEBUG")) : 0u;
-				// state in registers (FG_KSW_REG=0: in LDS rings, the round-2 form)
-				const bool regForm = !(getenv("FG_KSW_REG") && atoi(getenv("FG_KSW_REG")) == 0);
 				if (cls == 0) hipLaunchKernelGGL(k_ksw_extz2, g, 64, 0, s, KSW_ARGS);
 				else if (regForm && cls == 1) hipLaunchKernelGGL((k_ksw_extz2_reg<256, 2, 8, 96>), g, 64, 0, s, KSW_ARGS, dbg);
 				else if (regForm && cls == 2) hipLaunchKernelGGL((k_ksw_extz2_reg<256, 3, 8, 160>), g, 64, 0, s, KSW_ARGS, dbg);

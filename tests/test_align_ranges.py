@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from helpers import golden_reads, hpc, repeat_stage_setup
+from ksw_craft import band as ksw_band
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -62,21 +63,6 @@ def cut_pairs(cur, ext, pairs, use_hpc):
         t, q = cur.seq(cid)[cb:ce], ext.seq(eid)[eb:ee]
         out.append((hpc(t), hpc(q)) if use_hpc else (t, q))
     return out
-
-
-def ksw_band(tlen, qlen):
-    """The band getAlignmentCigarKsw ends with (alignment.cpp:147-159: 64, doubled while ksw_extz2 finds it too
-    narrow -- the last anti-diagonal decides), or 0 for an empty string."""
-    if not tlen or not qlen:
-        return 0
-    w = 64
-    while True:
-        r = qlen + tlen - 2
-        st = max(0, r - qlen + 1, (r - w + 1) >> 1)
-        en = min(tlen - 1, r, (r + w) >> 1)
-        if st <= en or w > max(qlen, tlen):
-            return w
-        w *= 2
 
 
 def check_against_oracle(ctx, pairs, strings, use_hpc, oracle=None):
@@ -282,7 +268,7 @@ def test_golden_records(repeat_records, use_hpc):
     assert np.array_equal(ops, want[1]) and np.array_equal(lens, want[2])
     assert len({ksw_band(len(t), len(x)) for t, x in strings} - {0}) > 1        # more than one band class
     kt = ctx.kernel_times()
-    assert kt["k_ksw_extz2_lds"][1] > 1
+    assert kt["k_ksw_extz2_reg"][1] > 1 and "k_ksw_extz2_lds" not in kt
     print({k: round(v[0] * 1e3, 3) for k, v in kt.items()})
 
 

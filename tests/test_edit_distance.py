@@ -231,8 +231,9 @@ def test_device_ksw_cigar_random_against_oracle(built, monkeypatch):
 
 @pytest.mark.gpu
 def test_device_ksw_lds_rings_equal_literal_state(built, monkeypatch):
-    """Read-sized pairs, bands 64 .. 1024 and beyond: the kernel with the byte state in LDS rings returns what the
-    literal one (whole arrays in memory, pinned above) returns, and both kernels ran."""
+    """Read-sized pairs, bands 64 .. 1024 and beyond: the kernel with the byte state in a register window (the default)
+    and the one with it in LDS rings (FG_KSW_REG=0) return what the literal one (whole arrays in memory, pinned above)
+    returns, and each form's kernel ran."""
     from flye_amd import gpu
     rng = np.random.default_rng(44)
     pairs = []
@@ -250,9 +251,15 @@ def test_device_ksw_lds_rings_equal_literal_state(built, monkeypatch):
     ctx = gpu.Context(17, 0)
     got = ctx.align_cigar_ksw(pairs)
     kt = ctx.kernel_times()
-    assert "k_ksw_extz2_lds" in kt and "k_ksw_extz2" in kt
+    assert "k_ksw_extz2_reg" in kt and "k_ksw_extz2" in kt and "k_ksw_extz2_lds" not in kt
+    monkeypatch.setenv("FG_KSW_REG", "0")
+    rings = ctx.align_cigar_ksw(pairs)
+    kt = ctx.kernel_times()
+    assert "k_ksw_extz2_lds" in kt and "k_ksw_extz2" in kt and "k_ksw_extz2_reg" not in kt
+    monkeypatch.delenv("FG_KSW_REG")
     monkeypatch.setenv("FG_KSW_LITERAL", "1")
     lit = ctx.align_cigar_ksw(pairs)
-    assert "k_ksw_extz2_lds" not in ctx.kernel_times()
-    assert got == lit
+    kt = ctx.kernel_times()
+    assert "k_ksw_extz2" in kt and "k_ksw_extz2_lds" not in kt and "k_ksw_extz2_reg" not in kt
+    assert got == lit and rings == lit
     assert len({len(c) for _, c in got}) > 50
