@@ -448,6 +448,8 @@ struct fg_ctx {
 	DevBuf<char> dBub[36];
 	// fg_uniform_alignments / fg_contig_consensus (fg_contigcons.hip): likewise
 	DevBuf<char> dCc[40];
+	// fg_expand_cigars (fg_cigar.hip): the call's contig bytes in the first, then the buffers of one sub-batch
+	DevBuf<char> dCig[20];
 	PinnedBuf<char> hPrim;
 	PinnedBuf<u64> hOff;
 	PinnedBuf<u64> hScalar;		// staging of the counts the host reads between kernels (pinned: no bounce buffer)

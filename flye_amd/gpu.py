@@ -18,14 +18,19 @@ like calls into the reference:
   ``polish``  (flye/polishing/bubbles.py:87-172 and alignment.py:95-153; alignment records instead of a SAM file)
 * ``ContigConsensus(ctx).consensus(contigs, alignments_by_contig)``  (flye/polishing/consensus.py:52-181, get_consensus
   without the SAM reader and the FASTA writer)
+* ``SamAlignments(ctx, sam_path, contigs, max_coverage, use_secondary).chunks() / by_contig()``
+  (flye/utils/sam_parser.py:123-404, SynchronizedSamReader: get_chunk on fg_expand_cigars)
 
 There is no CPU fallback: if the HIP library or a device is missing every entry
 point raises ``FlyeGpuError``.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
+import gzip
 import os
+import random
 
 import time
 
@@ -55,6 +60,7 @@ ABI_SYMBOLS = ["fg_abi_version", "fg_create", "fg_destroy", "fg_strerror", "fg_l
                "fg_edge_coverage", "fg_release_edge_coverage",
                "fg_subs_matrix_load", "fg_polish_bubbles", "fg_release_polish", "fg_make_bubbles", "fg_release_bubbles",
                "fg_uniform_alignments", "fg_release_uniform", "fg_contig_consensus", "fg_release_consensus",
+               "fg_expand_cigars", "fg_release_expand", "fg_cigar_parse",
                "fg_index_keep_targets", "fg_index_shard", "fg_probe_hits", "fg_overlaps_from_hits",
                "fg_index_piece_split", "fg_index_scatter_begin", "fg_index_scatter_end", "fg_debug_probe_skip_check",
                "fg_group_create", "fg_group_destroy", "fg_group_size", "fg_group_member", "fg_group_last_error",
@@ -228,6 +234,14 @@ class ConsensusBatch(C.Structure):
                 ("ins_off", C.POINTER(C.c_uint64)), ("ins", C.POINTER(C.c_uint8)), ("owner_", C.c_void_p)]
 
 
+class ExpandBatch(C.Structure):
+    """struct fg_expand_batch"""
+    _fields_ = [("n_alignments", C.c_uint64), ("col_off", C.POINTER(C.c_uint64)), ("trg_cols", C.POINTER(C.c_uint8)),
+                ("qry_cols", C.POINTER(C.c_uint8)), ("trg_start", C.POINTER(C.c_int32)), ("trg_end", C.POINTER(C.c_int32)),
+                ("qry_start", C.POINTER(C.c_int32)), ("qry_end", C.POINTER(C.c_int32)), ("qry_len", C.POINTER(C.c_int32)),
+                ("matches", C.POINTER(C.c_int64)), ("err_rate", C.POINTER(C.c_double)), ("owner_", C.c_void_p)]
+
+
 class BridgeStats(C.Structure):
     _fields_ = [("device_calls", C.c_uint64), ("reads_computed", C.c_uint64), ("requests", C.c_uint64),
                 ("cache_hits", C.c_uint64), ("cached_overlaps", C.c_uint64), ("reads_ahead", C.c_uint64),
@@ -362,6 +376,11 @@ def load_library():
         L.fg_contig_consensus.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 8 + [C.c_uint8, C.POINTER(ConsensusBatch)]
         L.fg_release_consensus.argtypes = [C.POINTER(ConsensusBatch)]
         L.fg_release_consensus.restype = None
+        L.fg_expand_cigars.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 7 + \
+            [C.c_uint8, C.POINTER(ExpandBatch)]
+        L.fg_release_expand.argtypes = [C.POINTER(ExpandBatch)]
+        L.fg_release_expand.restype = None
+        L.fg_cigar_parse.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         L.fg_debug_group_bin_cuts.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         L.fg_debug_freq_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
         L.fg_debug_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int]
@@ -630,6 +649,28 @@ class ConsensusResult(BubbleResult):
 
     def insertion(self, p):
         return self.ins[int(self.ins_off[p]):int(self.ins_off[p + 1])].tobytes()
+
+
+class ExpandResult(BubbleResult):
+    """fg_expand_batch copied out of its arena, arrays under the names of the header (trg_cols / qry_cols None without
+    want_cols).  columns(a) gives (aln.trg_seq, aln.qry_seq) of alignment a as bytes."""
+
+    def columns(self, a):
+        lo, hi = int(self.col_off[a]), int(self.col_off[a + 1])
+        return self.trg_cols[lo:hi].tobytes(), self.qry_cols[lo:hi].tobytes()
+
+
+def cigar_parse(cigar):
+    """fg_cigar_parse: the tokens of the reference's re "[0-9]+[MIDNSHP=X]" in a CIGAR (bytes) -> (ops uint8, lens uint32)"""
+    L = load_library()
+    cigar = bytes(cigar)
+    cap = len(cigar) // 2 + 1
+    ops, lens = np.zeros(cap, np.uint8), np.zeros(cap, np.uint32)
+    n = C.c_uint64()
+    rc = L.fg_cigar_parse(cigar, len(cigar), ops.ctypes.data, lens.ctypes.data, cap, C.byref(n))
+    if rc != 0:
+        raise FlyeGpuError(rc, "fg_cigar_parse: " + L.fg_strerror(rc).decode())
+    return ops[:n.value], lens[:n.value]
 
 
 class PolishResult:
@@ -1121,6 +1162,42 @@ class Context:
             out["ins"] = take(b.ins, int(out["ins_off"][npos]), np.uint8)
         self.L.fg_release_consensus(C.byref(b))
         return ConsensusResult(**out)
+
+    def expand_cigars(self, contig_off, contig_seq, aln_contig, ctg_pos, run_off, run_op, run_len, read_off, read_seq,
+                      want_cols=True):
+        """fg_expand_cigars: _parse_cigar (flye/utils/sam_parser.py:260-323) for a batch of SAM records.  Contig i is
+        contig_seq[contig_off[i]:contig_off[i + 1]]; alignment a lies on contig aln_contig[a] at SAM POS ctg_pos[a], has the
+        runs run_off[a] .. run_off[a + 1] of run_op (ASCII) / run_len and the SEQ bytes read_off[a] .. read_off[a + 1] of
+        read_seq.  Returns an ExpandResult."""
+        as_bytes = lambda x: np.ascontiguousarray(x, np.uint8) if isinstance(x, np.ndarray) else np.frombuffer(bytes(x), np.uint8)
+        cto = np.ascontiguousarray(contig_off, np.uint64)
+        cs, rop, rs = as_bytes(contig_seq), as_bytes(run_op), as_bytes(read_seq)
+        ac, cp = np.ascontiguousarray(aln_contig, np.uint32), np.ascontiguousarray(ctg_pos, np.int32)
+        ro, rdo = np.ascontiguousarray(run_off, np.uint64), np.ascontiguousarray(read_off, np.uint64)
+        rl = np.ascontiguousarray(run_len, np.uint32)
+        n = len(ac)
+        if len(cto) < 1 or len(cp) != n or len(ro) != n + 1 or len(rdo) != n + 1 or len(rop) != len(rl) or \
+                int(cto.max()) > len(cs) or int(ro.max()) > len(rl) or int(rdo.max()) > len(rs):
+            raise ValueError("expand_cigars: offsets outside their arrays")
+        ptr = lambda a: a.ctypes.data if len(a) else None
+        b = ExpandBatch()
+        t0 = time.perf_counter()
+        self._check(self.L.fg_expand_cigars(self.h, len(cto) - 1, cto.ctypes.data, ptr(cs), n, ptr(ac), ptr(cp), ro.ctypes.data,
+                                            ptr(rop), ptr(rl), rdo.ctypes.data, ptr(rs), int(bool(want_cols)), C.byref(b)))
+        self.last_expand_seconds = time.perf_counter() - t0
+
+        def take(p, k, dtype):
+            return np.ctypeslib.as_array(p, (k,)).copy() if k else np.zeros(0, dtype)
+
+        co = np.ctypeslib.as_array(b.col_off, (n + 1,)).copy()
+        out = dict(col_off=co, trg_cols=None, qry_cols=None)
+        if want_cols:
+            out["trg_cols"], out["qry_cols"] = take(b.trg_cols, int(co[n]), np.uint8), take(b.qry_cols, int(co[n]), np.uint8)
+        for k in ("trg_start", "trg_end", "qry_start", "qry_end", "qry_len"):
+            out[k] = take(getattr(b, k), n, np.int32)
+        out["matches"], out["err_rate"] = take(b.matches, n, np.int64), take(b.err_rate, n, np.float64)
+        self.L.fg_release_expand(C.byref(b))
+        return ExpandResult(**out)
 
     def edge_coverage(self, window, recs, aln, aln_off, first_ext_id, edge_of, edge_len, want_vectors=True):
         """fg_edge_coverage: the window coverage of MultiplicityInferer::estimateCoverage (multiplicity_inferer.cpp:
@@ -1989,7 +2066,7 @@ class BubbleProcessor:
 class BubbleMaker:
     """Mirror of the reference's flye/polishing/bubbles.py on fg_make_bubbles.  Alignments are records with the fields of
     the reference's Alignment tuple (trg_start, trg_end, trg_seq, qry_seq, err_rate, is_secondary are read); contigs are
-    records with id, length and type.  SAM parsing stays with the caller."""
+    records with id, length and type.  SamAlignments.by_contig() makes the alignments of a SAM file."""
 
     WINDOW, MIN_COV, COV_RATE = 100, 10, 1.25
 
@@ -2076,8 +2153,8 @@ class BubbleMaker:
 class ContigConsensus:
     """Mirror of the reference's get_consensus (flye/polishing/consensus.py:52-105) on fg_uniform_alignments and
     fg_contig_consensus.  Alignments are records with the fields of the reference's Alignment tuple (qry_id, trg_start,
-    trg_end, trg_seq, qry_seq, err_rate, is_secondary are read); contigs are records with id and length.  SAM parsing and
-    FASTA writing stay with the caller."""
+    trg_end, trg_seq, qry_seq, err_rate, is_secondary are read); contigs are records with id and length.  SamAlignments.by_contig()
+    makes the alignments of a SAM file; FASTA writing stays with the caller."""
 
     def __init__(self, ctx: Context):
         self.ctx = ctx
@@ -2115,3 +2192,123 @@ class ContigConsensus:
             if len(seq) > 0:
                 out[c.id] = seq.decode("latin-1")
         return out, total / (len(self.aln_errors) + 1)
+
+
+# the reference's Alignment tuple (flye/utils/sam_parser.py:44-48)
+Alignment = collections.namedtuple("Alignment", ["qry_id", "trg_id", "qry_start", "qry_end", "qry_sign", "qry_len", "trg_start",
+                                                 "trg_end", "trg_sign", "trg_len", "qry_seq", "trg_seq", "err_rate",
+                                                 "is_secondary"])
+
+
+class SamAlignments:
+    """Mirror of the reference's SynchronizedSamReader (flye/utils/sam_parser.py:123-404) on fg_expand_cigars: the whole
+    SAM file (plain or .gz) is read at once, tokenised on the host (CIGARs through fg_cigar_parse) and every record that
+    get_chunk would parse goes into ONE device call.  contigs maps contig id to sequence (str or bytes), as the
+    reference's reference_fasta.  max_coverage = None makes no cut (the reference compares with None there, which
+    Python 3 refuses).  Raises ValueError where the reference raises AlignmentException("Alignment file is not sorted")."""
+
+    HEADERS = (b"@PG", b"@HD", b"@SQ", b"@RG", b"@CO")
+
+    def __init__(self, ctx, sam_path, contigs, max_coverage=None, use_secondary=False):
+        self.ctx = ctx
+        self.max_coverage, self.use_secondary = max_coverage, use_secondary
+        as_bytes = lambda x: x if isinstance(x, bytes) else x.encode("latin-1")
+        self.contigs = {as_bytes(h): as_bytes(s) for h, s in contigs.items()}
+        opener = gzip.open if sam_path.endswith(".gz") else open
+        with opener(sam_path, "rb") as f:
+            self._chunks = self._parse(self._file_chunks(f))
+
+    @classmethod
+    def _file_chunks(cls, lines):
+        """_read_file_chunk (:168-213) until the end of the file: [(contig, [line])] in file order"""
+        out, processed, current = [], set(), None
+        for line in lines:
+            if line[:3] in cls.HEADERS:
+                continue
+            tab_1 = line.find(b"\t")
+            tab_2 = line.find(b"\t", tab_1 + 1)
+            tab_3 = line.find(b"\t", tab_2 + 1)
+            if tab_2 == -1 or tab_3 == -1:
+                continue
+            contig = line[tab_2 + 1:tab_3]
+            if contig in processed:
+                raise ValueError("Alignment file is not sorted")
+            if contig != current:
+                if current is not None:
+                    processed.add(current)
+                current = contig
+                out.append((contig, []))
+            out[-1][1].append(line)
+        return out
+
+    @staticmethod
+    def _span(ops, lens):
+        """(qry_start, qry_end) of _parse_cigar (:316-320) from the runs alone"""
+        lens = lens.astype(np.int64)
+        is_h, is_s = ops == ord("H"), ops == ord("S")
+        qry_pos = int(lens[(ops == ord("M")) | (ops == ord("I")) | is_s].sum())
+        hard_left = int(lens[0]) if len(ops) and is_h[0] else 0
+        other = np.flatnonzero(~is_h)
+        soft_left = int(lens[other[0]]) if len(other) and is_s[other[0]] else 0
+        return hard_left + soft_left, qry_pos + hard_left - (int(lens[is_s].sum()) - soft_left)
+
+    def _parse(self, file_chunks):
+        """get_chunk (:325-404) for every chunk; the records that survive its filters and its cut go to the device"""
+        kept = []                                   # per chunk: [(tokens, flags, ops, lens)]
+        for contig, lines in file_chunks:
+            lines = list(lines)
+            random.Random(42).shuffle(lines)
+            sequence_length, recs = 0, []
+            for line in lines:
+                tokens = line.strip().split()
+                if len(tokens) < 11:
+                    continue
+                flags = int(tokens[1])
+                if flags & 0x4:
+                    continue
+                if flags & 0x100 and not self.use_secondary:
+                    continue
+                if tokens[9] == b"*":
+                    raise Exception("Error parsing SAM: record without read sequence")
+                ops, lens = cigar_parse(tokens[5])
+                recs.append((tokens, flags, ops, lens))
+                qry_start, qry_end = self._span(ops, lens)
+                sequence_length += qry_end - qry_start
+                contig_length = len(self.contigs[contig])
+                if self.max_coverage is not None and sequence_length // contig_length > self.max_coverage:
+                    break
+            kept.append(recs)
+        flat = [r for recs in kept for r in recs]
+        used = []
+        for tokens, _, _, _ in flat:
+            if tokens[2] not in used:
+                used.append(tokens[2])
+        number = {h: i for i, h in enumerate(used)}
+        res = self.ctx.expand_cigars(
+            np.cumsum([0] + [len(self.contigs[h]) for h in used]), b"".join(self.contigs[h] for h in used),
+            [number[r[0][2]] for r in flat], [int(r[0][3]) for r in flat], np.cumsum([0] + [len(r[2]) for r in flat]),
+            np.concatenate([r[2] for r in flat]) if flat else np.zeros(0, np.uint8),
+            np.concatenate([r[3] for r in flat]) if flat else np.zeros(0, np.uint32),
+            np.cumsum([0] + [len(r[0][9]) for r in flat]), b"".join(r[0][9] for r in flat))
+        self.result = res
+        out, a = [], 0
+        for (contig, _), recs in zip(file_chunks, kept):
+            alns = []
+            for tokens, flags, _, _ in recs:
+                trg, qry = res.columns(a)
+                alns.append(Alignment(tokens[0].decode(), tokens[2].decode(), int(res.qry_start[a]), int(res.qry_end[a]),
+                                      "-" if flags & 0x16 else "+", int(res.qry_len[a]), int(res.trg_start[a]),
+                                      int(res.trg_end[a]), "+", len(self.contigs[tokens[2]]), qry.decode(), trg.decode(),
+                                      float(res.err_rate[a]), flags & 0x100))
+                a += 1
+            alns.sort(key=lambda x: (x.qry_id, -(x.qry_end - x.qry_start)))
+            out.append((contig.decode(), alns))
+        return out
+
+    def chunks(self):
+        """[(contig id, [Alignment])] in file order: what successive get_chunk calls return"""
+        return self._chunks
+
+    def by_contig(self):
+        """{contig id: [Alignment]}: what BubbleMaker.make and ContigConsensus.consensus take"""
+        return dict(self._chunks)

@@ -926,6 +926,53 @@ int  fg_contig_consensus(fg_ctx* ctx, uint32_t n_contigs, const int32_t* contig_
                          struct fg_consensus_batch* out);
 void fg_release_consensus(struct fg_consensus_batch* b);
 
+/* SynchronizedSamReader._parse_cigar (flye/utils/sam_parser.py:260-323) for a batch of SAM records: the step that makes
+ * the input of the three calls above.  Contig i is the bytes contig_off[i] .. contig_off[i+1] of contig_seq; alignment a
+ * lies on contig aln_contig[a] at SAM POS ctg_pos[a] (1-based), has the CIGAR runs run_off[a] .. run_off[a+1] (run_op the
+ * operation as its ASCII byte, run_len its length) and the SAM SEQ bytes read_off[a] .. read_off[a+1] of read_seq.
+ * Offsets need not start at zero.  Per run, in order (:275-306): M appends the next run_len read bytes to qry_seq and the
+ * next run_len contig bytes to trg_seq; I the read bytes against '-'; D '-' against the contig bytes; S advances the read
+ * position and counts as left soft clip only while no operation other than H has come before, else as right soft clip,
+ * wherever it stands; H counts as left hard clip only as the very first operation, else as right hard clip.  A run of
+ * length 0 is legal and gives nothing.  Bytes are upper-cased as bytes.upper() does it (a-z only) and compared after that.
+ * trg_start = ctg_pos - 1, trg_end = trg_start + the contig bytes consumed; with qry_pos the read bytes consumed (:316-320)
+ * qry_start = left hard + left soft, qry_end = qry_pos + left hard - right soft, qry_len = qry_pos + left hard + right
+ * hard.  matches = the columns with equal bytes (:310-313, counted on the device); err_rate = 1.0 - (double)matches /
+ * (double)columns on the host, bit-equal to Python's 1 - matches / len.  The columns of alignment a are col_off[a] ..
+ * col_off[a+1] of trg_cols / qry_cols, the layout fg_make_bubbles and fg_contig_consensus read; want_cols = 0 leaves both
+ * NULL and still counts (for a caller that runs fg_uniform_alignments first and expands only what it keeps).
+ * The context lends its device and stream: no reads and no index are needed.  The contig bytes go up once per call; the
+ * call works in sub-batches of whole alignments of at most FG_CIGAR_BATCH_COLS columns (environment, default 2^27) and,
+ * as a switch for tests, FG_CIGAR_BATCH_ALNS alignments; FG_CIGAR_TILE (columns per workgroup of k_cig_expand, a power of
+ * two in 64 .. 4096, default 2048) is a switch for tests too.  The result depends on none of them.  FG_ERR_NOMEM: an
+ * alignment that alone exceeds the column budget.  FG_ERR_UNSUPPORTED: an operation among N P = X (the reference raises
+ * AlignmentException, :303).  FG_ERR_ARG, found before any device work: NULL out or a NULL array where something must be
+ * read; an offset array that decreases; aln_contig >= n_contigs; ctg_pos < 1; any other operation byte; a byte >= 128 in
+ * a contig or a read; an alignment whose runs consume more read bytes than its SEQ holds or walk past the end of its
+ * contig (the reference silently returns strings of unequal length there; this call refuses); an alignment of zero
+ * columns (the reference divides by zero, :314); totals that do not fit int32.  After an error *out is all zero.
+ * n_alignments = 0 gives an empty batch (col_off = {0}). */
+struct fg_expand_batch {
+	uint64_t  n_alignments;
+	uint64_t* col_off;            /* n_alignments + 1, starts at 0 */
+	uint8_t*  trg_cols;           /* want_cols: aln.trg_seq, one byte per column, '-' the gap */
+	uint8_t*  qry_cols;           /* want_cols: aln.qry_seq */
+	int32_t  *trg_start, *trg_end, *qry_start, *qry_end, *qry_len;
+	int64_t*  matches;            /* columns with equal bytes */
+	double*   err_rate;           /* 1.0 - (double)matches / (double)columns, computed on the host */
+	void*     owner_;
+};
+int  fg_expand_cigars(fg_ctx* ctx, uint32_t n_contigs, const uint64_t* contig_off, const uint8_t* contig_seq,
+                      uint64_t n_alignments, const uint32_t* aln_contig, const int32_t* ctg_pos /* SAM POS, 1-based */,
+                      const uint64_t* run_off, const uint8_t* run_op /* ASCII */, const uint32_t* run_len,
+                      const uint64_t* read_off, const uint8_t* read_seq, uint8_t want_cols, struct fg_expand_batch* out);
+void fg_release_expand(struct fg_expand_batch* b);
+/* host only, no context: the tokens of the reference's re "[0-9]+[MIDNSHP=X]" (:140) in order, as findall gives them
+ * (bytes that match nothing are skipped).  *n_runs = the number of tokens; at most cap of them are written.  FG_ERR_ARG:
+ * more tokens than cap (*n_runs still says how many), a length beyond uint32, NULL n_runs, NULL where something is read
+ * or written. */
+int  fg_cigar_parse(const char* cigar, uint64_t n_bytes, uint8_t* ops, uint32_t* lens, uint64_t cap, uint64_t* n_runs);
+
 #ifdef __cplusplus
 }
 #endif
