@@ -74,8 +74,8 @@ __device__ __forceinline__ bool overlap_test(const ChainParams& P, u32 curId, u3
 // lists: one atomic per list and block of LIST_ITEMS * 256 groups (same-address atomics
 // serialise; the list kernels were bound by exactly these atomics at one per 256 groups)
 #define LIST_ITEMS 8
-__device__ __forceinline__ void append2_multi(const bool (&a)[LIST_ITEMS], const bool (&b)[LIST_ITEMS], u32 g0,
-											  u32* listA, u32* listB, u32* counts)
+__device__ __forceinline__ void append2_offsets(const bool (&a)[LIST_ITEMS], const bool (&b)[LIST_ITEMS], u32* counts,
+												u32& oA, u32& oB)
 {
 	__shared__ u32 wtot[2][WG / 64];
 	__shared__ u32 base[2];
@@ -98,8 +98,14 @@ __device__ __forceinline__ void append2_multi(const bool (&a)[LIST_ITEMS], const
 		base[threadIdx.x] = t ? atomicAdd(&counts[threadIdx.x], t) : 0u;
 	}
 	__syncthreads();
-	u32 oA = base[0] + iA - cA, oB = base[1] + iB - cB;
+	oA = base[0] + iA - cA; oB = base[1] + iB - cB;
 	for (int i = 0; i < wv; ++i) { oA += wtot[0][i]; oB += wtot[1][i]; }
+}
+__device__ __forceinline__ void append2_multi(const bool (&a)[LIST_ITEMS], const bool (&b)[LIST_ITEMS], u32 g0,
+											  u32* listA, u32* listB, u32* counts)
+{
+	u32 oA, oB;
+	append2_offsets(a, b, counts, oA, oB);
 #pragma unroll
 	for (int t = 0; t < LIST_ITEMS; ++t)
 	{
@@ -111,14 +117,22 @@ __device__ __forceinline__ void append2_multi(const bool (&a)[LIST_ITEMS], const
 // groups that can still have >= minUnique distinct query positions (unique <= size) and whose
 // query span reaches minOverlap (the first and last hit of the sorted group give it: overlap.cpp:
 // 244-249 would drop the group anyway, here it never costs k_group_prep a wave)
+// CLASSES: the groups above the fused kernel's cap are listed by the size classes of the DP and the backtracking
+// at once (a survivor of the prefilter has dpSize == its size, so k_dp_list would sort it into the same class):
+//   n <= bigMin           -> list,    written downwards from list[mid - 1]       counts[0]
+//   bigMin < n <= hugeMax -> list[mid ..] AND listBig[mid ..], upwards           counts[3]
+//   hugeMax < n           -> listBig, written downwards from listBig[mid - 1]    counts[1]
+// so that the middle class is contiguous with either neighbour: which of the two it joins depends on the number
+// of groups listed (the small-call rule of fgChainStage), which the host knows only after this kernel.
+template <bool CLASSES>
 __global__ void k_group_list(u64 nGroups, u64 nHits, const u64* __restrict__ groupStart, u32 minSize,
 							 const u32* __restrict__ groupFirstCur, const u32* __restrict__ groupLastCur, i32 minOverlap,
-							 u32* __restrict__ list, u32* __restrict__ listBig, u32 bigMin,
+							 u32* __restrict__ list, u32* __restrict__ listBig, u32 bigMin, u32 hugeMax, u32 mid,
 							 u32* __restrict__ listFused, u32 fusedMax /* 0: no fused class */, u32* __restrict__ counts,
 							 u32* __restrict__ primCount, u32* __restrict__ dpSize)
 {
 	const u64 g0 = ((u64)blockIdx.x * WG + threadIdx.x) * LIST_ITEMS;
-	bool a[LIST_ITEMS], b[LIST_ITEMS], f[LIST_ITEMS], none[LIST_ITEMS];
+	bool a[LIST_ITEMS], b[LIST_ITEMS], f[LIST_ITEMS], m[LIST_ITEMS];
 	u64 start = g0 < nGroups ? groupStart[g0] : nHits;
 #pragma unroll
 	for (int t = 0; t < LIST_ITEMS; ++t)
@@ -140,13 +154,31 @@ __global__ void k_group_list(u64 nGroups, u64 nHits, const u64* __restrict__ gro
 		a[t] = ok && n > fusedMax && n <= bigMin;
 		b[t] = ok && n > bigMin && n > fusedMax;	// groups that k_group_prep handles in global memory (never one that
 												// k_chain_small takes: FG_FUSED_CAP > PREP_CAP)
-		none[t] = false;
+		m[t] = false;
+		if (CLASSES) { m[t] = b[t] && n <= hugeMax; b[t] = b[t] && !m[t]; }	// (hugeMax >= bigMin)
 	}
-	append2_multi(a, b, (u32)g0, list, listBig, counts);
-	if (fusedMax)
+	if (!CLASSES)
 	{
-		__syncthreads();	// the helper's shared counters are reused
-		append2_multi(f, none, (u32)g0, listFused, listFused, counts + 2);
+		append2_multi(a, b, (u32)g0, list, listBig, counts);
+		if (fusedMax)
+		{
+			__syncthreads();	// the helper's shared counters are reused
+			append2_multi(f, m, (u32)g0, listFused, listFused, counts + 2);
+		}
+		return;
+	}
+	u32 oA, oB, oF, oM;
+	append2_offsets(a, b, counts, oA, oB);
+	__syncthreads();
+	append2_offsets(f, m, counts + 2, oF, oM);
+#pragma unroll
+	for (int t = 0; t < LIST_ITEMS; ++t)
+	{
+		const u32 g = (u32)g0 + (u32)t;
+		if (a[t]) list[(size_t)mid - 1 - oA++] = g;
+		if (b[t]) listBig[(size_t)mid - 1 - oB++] = g;
+		if (f[t]) listFused[oF++] = g;
+		if (m[t]) { list[(size_t)mid + oM] = g; listBig[(size_t)mid + oM] = g; ++oM; }
 	}
 }
 
@@ -511,13 +543,14 @@ __global__ void __launch_bounds__(DP_WAVES * 64)
 k_chain_dp(ChainParams P, const u32* __restrict__ list, u32 nList, u64 nGroups, u64 nHits,
 		   const u64* __restrict__ groupStart, const u32* __restrict__ groupQuery,
 		   const u32* __restrict__ query, const i32* __restrict__ len, const i32* __restrict__ qLen,
-		   const uint8_t* __restrict__ groupExtSorted,
+		   const uint8_t* __restrict__ groupExtSorted, const u32* __restrict__ dpSize,
 		   const u32* __restrict__ gCur, const u32* __restrict__ gExt,
 		   i32* __restrict__ gScore, i32* __restrict__ gBack)
 {
 	const u32 li = blockIdx.x * DP_WAVES + (threadIdx.x >> 6);
 	if (li >= nList) return;
 	const u64 g = fg_uni(list[li]);
+	if (fg_uni(dpSize[g]) == 0) return;		// listed by its size, dropped by the prefilter (k_group_prep)
 	const u64 g0 = fg_uni(groupStart[g]);
 	const u64 gend = (g + 1 < nGroups) ? fg_uni(groupStart[g + 1]) : nHits;
 	const i32 n = (i32)(gend - g0);
@@ -962,7 +995,7 @@ k_chain_finish(ChainParams P, const u32* __restrict__ list, u32 nList, u64 nGrou
 			   const u32* __restrict__ groupExt,
 			   const u32* __restrict__ gCur, const u32* __restrict__ gExt, i32* __restrict__ gScore,
 			   i32* __restrict__ gBack, u32* __restrict__ gAux /* 4 u32 per hit */, int4* __restrict__ cand,
-			   u32* __restrict__ primCount)
+			   u32* __restrict__ primCount, const u32* __restrict__ dpSize)
 {
 	constexpr bool USE_LDS = CAP > 0;
 	// dynamic LDS: per wave CAP * 20 bytes (score, back, order key, order value, 2 x u16 scratch)
@@ -975,6 +1008,7 @@ k_chain_finish(ChainParams P, const u32* __restrict__ list, u32 nList, u64 nGrou
 	const u32 li = blockIdx.x * FIN_WAVES + wv;
 	if (li >= nList) return;
 	const u64 g = fg_uni(list[li]);
+	if (fg_uni(dpSize[g]) == 0) return;		// dropped by the prefilter: no primaries (primCount[g] stays 0)
 	const u64 g0 = fg_uni(groupStart[g]);
 	const u64 gend = (g + 1 < nGroups) ? fg_uni(groupStart[g + 1]) : nHits;
 	const i32 n = (i32)(gend - g0);
@@ -1126,7 +1160,14 @@ void fgChainStage(fg_ctx* c, const fg_detector_params* p, uint8_t forceLocal, u6
 	u32 minSize = 0;
 	while ((float)minSize < cp.minUnique) ++minSize;
 	if (minSize == 0) minSize = 1;
-	c->dListSmall.reserve(nGroups + 1); c->dListBig.reserve(nGroups + 1); c->dListDp.reserve(nGroups + 1);
+	const u32 fusedMax = fgChainSmallMax();
+	const bool fused = fusedMax != 0;
+	// With the fused kernel at its full cap every other group is above FIN_CAP_S hits, and its class for the DP and the
+	// backtracking follows from its size alone: k_group_list writes those classes, two lists that share their
+	// middle part (see there), each 2 * nGroups long.  Otherwise k_dp_list sorts the prefilter's survivors into classes.
+	const bool classes = fusedMax >= (u32)FIN_CAP_S;
+	c->dListBig.reserve((classes ? 2 : 1) * nGroups + 1); c->dListDp.reserve((classes ? 2 : 1) * nGroups + 1);
+	if (!classes) c->dListSmall.reserve(nGroups + 1);
 	c->dGroupExtSorted.reserve(nGroups + 1);
 	c->dListCnt.reserve(4);
 	const u64 hitCap = std::max<u64>(nHits, c->hitCapHint);	// sized once for the largest sub-range of the chunk
@@ -1135,177 +1176,162 @@ void fgChainStage(fg_ctx* c, const fg_detector_params* p, uint8_t forceLocal, u6
 	c->dTmp32.reserve(4 * hitCap + 16);
 	c->dCand.reserve(hitCap + 1);
 	const unsigned gridG = (unsigned)((nGroups + (u64)WG * LIST_ITEMS - 1) / ((u64)WG * LIST_ITEMS));
-	const u32 fusedMax = fgChainSmallMax();
-	const bool fused = fusedMax != 0;
 	if (fused) c->dListFused.reserve(nGroups + 1);
+	const char* hugeEnv = getenv("FG_CHAIN_HUGE_MIN");
 	HIP_CHECK(hipMemsetAsync(c->dListCnt.p, 0, 16, s));
 	{ ScopedK t(c->timer, "k_group_list");
-	  hipLaunchKernelGGL(k_group_list, gridG, WG, 0, s, nGroups, nHits, c->dGroupStart.p, minSize, c->dGroupFirstCur.p,
-						 c->dGroupLastCur.p, (i32)p->min_overlap, c->dListSmall.p, c->dListBig.p, (u32)PREP_CAP,
-						 c->dListFused.p, fusedMax, c->dListCnt.p, c->dPrimFlag.p, c->dDpSize.p); }
+	  if (classes)		// up to FIN_CAP_M hits / up to 4096 / more; one boundary where the switch names it
+		  hipLaunchKernelGGL(k_group_list<true>, gridG, WG, 0, s, nGroups, nHits, c->dGroupStart.p, minSize, c->dGroupFirstCur.p,
+							 c->dGroupLastCur.p, (i32)p->min_overlap, c->dListDp.p, c->dListBig.p,
+							 hugeEnv ? (u32)atoi(hugeEnv) : (u32)FIN_CAP_M, hugeEnv ? (u32)atoi(hugeEnv) : 4096u, (u32)nGroups,
+							 c->dListFused.p, fusedMax, c->dListCnt.p, c->dPrimFlag.p, c->dDpSize.p);
+	  else
+		  hipLaunchKernelGGL(k_group_list<false>, gridG, WG, 0, s, nGroups, nHits, c->dGroupStart.p, minSize, c->dGroupFirstCur.p,
+							 c->dGroupLastCur.p, (i32)p->min_overlap, c->dListSmall.p, c->dListBig.p, (u32)PREP_CAP, 0u, 0u,
+							 c->dListFused.p, fusedMax, c->dListCnt.p, c->dPrimFlag.p, c->dDpSize.p); }
 	u32 nPrep[4];
 	c->hScalar.reserve(8);
 	HIP_CHECK(hipMemcpyAsync(c->hScalar.p, c->dListCnt.p, 16, hipMemcpyDeviceToHost, s));
 	HIP_CHECK(hipStreamSynchronize(s));
 	memcpy(nPrep, c->hScalar.p, 16);
 	const u32 nFused = fused ? nPrep[2] : 0u;
-	if (!nPrep[0] && !nPrep[1] && !nFused) return;
-	if (fused)
+	if (!nPrep[0] && !nPrep[1] && !nPrep[3] && !nFused) return;
+	const bool sideStreams = !(getenv("FG_CHAIN_STREAMS") && atoi(getenv("FG_CHAIN_STREAMS")) == 1);	// 1: everything on the main stream
+	auto launchSmall = [&]()		// the small groups, start to end in one kernel on the main stream
 	{
-		// Main stream: the small groups, start to end in one kernel.  Beside it on the side streams: the larger groups'
-		// prefilter (stream 2), their size classes listed, then the two classes' DP -> finish chains (streams 2 and 3).
-		const bool others = nPrep[0] || nPrep[1];
-		const bool sideStreams = !(getenv("FG_CHAIN_STREAMS") && atoi(getenv("FG_CHAIN_STREAMS")) == 1);	// 1: everything on the main stream
-		if (others && sideStreams)
-		{
-			HIP_CHECK(hipEventRecord(c->evFork, s));
-			HIP_CHECK(hipStreamWaitEvent(c->stream2, c->evFork, 0));
-		}
-		if (nFused)
-		{
-			ScopedK t(c->timer, "k_chain_small");
+		if (!nFused) return;
+		ScopedK t(c->timer, "k_chain_small");
 #define SMALL_ARGS(view) cp, c->dListFused.p, nFused, nGroups, nHits, c->dGroupStart.p, c->dGroupQuery.p, c->curQuery, c->dLen.p, qLen, \
-			view, c->dGroupExt.p, c->dCur.p, c->dExt.p, c->dBack.p, c->dCand.p, c->dDpSize.p, c->dPrimFlag.p, (int)fusedMax
-			const size_t ldsSmall = (size_t)fusedMax * 28;
-			if (keyMode == 0)
-				hipLaunchKernelGGL(k_chain_small<u32>, nFused, 64, ldsSmall, s, SMALL_ARGS((HitKeyView<u32>{c->dHitKey32.p, c->dHitVal.p, curBits, c->firstId})));
-			else if (keyMode == 1)
-				hipLaunchKernelGGL(k_chain_small<PK>, nFused, 64, ldsSmall, s, SMALL_ARGS((HitKeyView<PK>{(const PK*)c->dHitKey.p, nullptr, curBits, c->firstId})));
-			else
-				hipLaunchKernelGGL(k_chain_small<u64>, nFused, 64, ldsSmall, s, SMALL_ARGS((HitKeyView<u64>{c->dHitKey.p, c->dHitVal.p, curBits, c->firstId})));
+		view, c->dGroupExt.p, c->dCur.p, c->dExt.p, c->dBack.p, c->dCand.p, c->dDpSize.p, c->dPrimFlag.p, (int)fusedMax
+		const size_t ldsSmall = (size_t)fusedMax * 28;
+		if (keyMode == 0)
+			hipLaunchKernelGGL(k_chain_small<u32>, nFused, 64, ldsSmall, s, SMALL_ARGS((HitKeyView<u32>{c->dHitKey32.p, c->dHitVal.p, curBits, c->firstId})));
+		else if (keyMode == 1)
+			hipLaunchKernelGGL(k_chain_small<PK>, nFused, 64, ldsSmall, s, SMALL_ARGS((HitKeyView<PK>{(const PK*)c->dHitKey.p, nullptr, curBits, c->firstId})));
+		else
+			hipLaunchKernelGGL(k_chain_small<u64>, nFused, 64, ldsSmall, s, SMALL_ARGS((HitKeyView<u64>{c->dHitKey.p, c->dHitVal.p, curBits, c->firstId})));
 #undef SMALL_ARGS
-		}
-		if (!others) return;
-		hipStream_t s2 = sideStreams ? c->stream2 : s, s3 = sideStreams ? c->stream3 : s;
-		const u32* prepList[2] = {c->dListSmall.p, c->dListBig.p};
-#define PREP_ARGS(view, cls) cp, prepList[cls], nPrep[cls], nGroups, nHits, c->dGroupStart.p, c->dGroupQuery.p, c->curQuery, c->dLen.p, qLen, \
+	};
+	auto launchPrep = [&](const u32* list, u32 nList, hipStream_t on)
+	{
+		ScopedK t(c->timer, "k_group_prep", on);
+#define PREP_ARGS(view) cp, list, nList, nGroups, nHits, c->dGroupStart.p, c->dGroupQuery.p, c->curQuery, c->dLen.p, qLen, \
 		view, c->dGroupExt.p, c->dCur.p, c->dExt.p, c->dTmp32.p, c->dDpSize.p, c->dGroupExtSorted.p
-		for (int cls = 1; cls >= 0; --cls)
-		{
-			if (!nPrep[cls]) continue;
-			ScopedK t(c->timer, "k_group_prep", s2);
-			const unsigned gridP = (nPrep[cls] + PREP_WAVES - 1) / PREP_WAVES;
-			if (keyMode == 0)
-				hipLaunchKernelGGL(k_group_prep<u32>, gridP, PREP_WAVES * 64, 0, s2,
-								   PREP_ARGS((HitKeyView<u32>{c->dHitKey32.p, c->dHitVal.p, curBits, c->firstId}), cls));
-			else if (keyMode == 1)
-				hipLaunchKernelGGL(k_group_prep<PK>, gridP, PREP_WAVES * 64, 0, s2,
-								   PREP_ARGS((HitKeyView<PK>{(const PK*)c->dHitKey.p, nullptr, curBits, c->firstId}), cls));
-			else
-				hipLaunchKernelGGL(k_group_prep<u64>, gridP, PREP_WAVES * 64, 0, s2,
-								   PREP_ARGS((HitKeyView<u64>{c->dHitKey.p, c->dHitVal.p, curBits, c->firstId}), cls));
-		}
+		const unsigned gridP = (nList + PREP_WAVES - 1) / PREP_WAVES;
+		if (keyMode == 0)
+			hipLaunchKernelGGL(k_group_prep<u32>, gridP, PREP_WAVES * 64, 0, on,
+							   PREP_ARGS((HitKeyView<u32>{c->dHitKey32.p, c->dHitVal.p, curBits, c->firstId})));
+		else if (keyMode == 1)
+			hipLaunchKernelGGL(k_group_prep<PK>, gridP, PREP_WAVES * 64, 0, on,
+							   PREP_ARGS((HitKeyView<PK>{(const PK*)c->dHitKey.p, nullptr, curBits, c->firstId})));
+		else
+			hipLaunchKernelGGL(k_group_prep<u64>, gridP, PREP_WAVES * 64, 0, on,
+							   PREP_ARGS((HitKeyView<u64>{c->dHitKey.p, c->dHitVal.p, curBits, c->firstId})));
 #undef PREP_ARGS
-		// (the group lists of k_group_list are dead once the preps have run: dListSmall is reused for the empty small class)
-		HIP_CHECK(hipMemsetAsync(c->dListCnt.p, 0, 16, s2));
-		const bool smallCall2 = (nPrep[0] + nPrep[1] + nFused) < 65536u && !getenv("FG_CHAIN_NO_SMALL_CALL");
-		const u32 hugeMin2 = getenv("FG_CHAIN_HUGE_MIN") ? (u32)atoi(getenv("FG_CHAIN_HUGE_MIN")) : (smallCall2 ? (u32)FIN_CAP_M : 4096u);
-		{ ScopedK t(c->timer, "k_dp_list", s2);
-		  hipLaunchKernelGGL(k_dp_list, gridG, WG, 0, s2, nGroups, c->dDpSize.p, hugeMin2, fusedMax, c->dListSmall.p, c->dListDp.p,
-							 c->dListBig.p, c->dListCnt.p); }
-		u32 hc2[4];
-		HIP_CHECK(hipMemcpyAsync(c->hScalar.p, c->dListCnt.p, 16, hipMemcpyDeviceToHost, s2));
-		HIP_CHECK(hipStreamSynchronize(s2));		// the side stream only: the small groups' kernel keeps running
-		memcpy(hc2, c->hScalar.p, 16);
-		const u32* lists2[3] = {c->dListSmall.p, c->dListDp.p, c->dListBig.p};
-		if (hc2[2] && sideStreams)
+	};
+#define FIN_ARGS(list, n) cp, list, n, nGroups, nHits, c->dGroupStart.p, c->dGroupQuery.p, c->curQuery, c->dLen.p, \
+		qLen, c->dGroupExt.p, c->dCur.p, c->dExt.p, c->dScore.p, c->dBack.p, c->dTmp32.p, c->dCand.p, c->dPrimFlag.p, c->dDpSize.p
+#define DP_ARGS(list, n) cp, list, n, nGroups, nHits, c->dGroupStart.p, c->dGroupQuery.p, c->curQuery, c->dLen.p, qLen, \
+		c->dGroupExtSorted.p, c->dDpSize.p, c->dCur.p, c->dExt.p, c->dScore.p, c->dBack.p
+	if (classes)
+	{
+		// Three chains behind k_group_list, on disjoint sets of groups (each owns its hit range in every scratch array):
+		// the small groups in one kernel on the main stream, and prefilter -> DP -> backtracking over the mid and the huge
+		// class on a side stream each, with no host round trip in between.  The side chains are the longest dependent
+		// sequence of the stage and are issued first.  A group the prefilter drops keeps dpSize == 0, and its wave returns
+		// at once in the two later kernels.
+		// A small call (a few hundred reads at most: what a caller thread's single request or the start of a read-ahead
+		// ramp looks like) is all latency: its 257..1024-hit groups sort and walk in LDS (k_chain_finish<lds1024>, 20 KB
+		// per wave, which the bulk case cannot afford: occupancy), and everything above is the huge class; a bulk call
+		// draws the line at 4096 hits.  The middle part of the lists (FIN_CAP_M < n <= 4096) joins either side.
+		const bool smallCall = (nPrep[0] + nPrep[1] + nPrep[3] + nFused) < 65536u && !getenv("FG_CHAIN_NO_SMALL_CALL");
+		const u32 nMid = nPrep[0] + (smallCall ? 0u : nPrep[3]), nHuge = nPrep[1] + (smallCall ? nPrep[3] : 0u);
+		const u32* listMid = c->dListDp.p + (nGroups - nPrep[0]);
+		const u32* listHuge = c->dListBig.p + (nGroups - nPrep[1]);
+		const bool midLds = smallCall && (!hugeEnv || (u32)atoi(hugeEnv) <= (u32)FIN_CAP_M);
+		const bool side = sideStreams && (nMid || nHuge);
+		hipStream_t sMid = side ? c->stream2 : s, sHuge = side ? c->stream3 : s;
+		// A bulk call without a huge class (raw reads: no group above 4096 hits) would leave that stream idle: its mid
+		// class is cut in two by list position (group sizes do not depend on it) and the second part runs there.  (Behind
+		// a huge chain the second part only waits: HiFi and D. melanogaster-like workloads lost 5-8 % that way.)  Every kernel of the stage fills the chip alone, so the queues that have
+		// work share the workgroup slots about evenly: with one side queue k_chain_small took half of them and ended
+		// ~4 ms before the side chain, which then ran its last kernels alone; with two the three chains end within a
+		// millisecond of one another ("Side chains").  FG_CHAIN_SPLIT=0: the mid class in one piece.
+		const bool split = side && !smallCall && !nHuge && !(getenv("FG_CHAIN_SPLIT") && atoi(getenv("FG_CHAIN_SPLIT")) == 0);
+		const u32 nMidB = split ? nMid / 2 : 0u, nMidA = nMid - nMidB;	// (other shares for the second part, 28 .. 42 %: no difference seen)
+		auto chain = [&](const u32* list, u32 n, hipStream_t on, bool lds)
 		{
-			HIP_CHECK(hipEventRecord(c->evJoin3, s2));		// (used as a fork here: stream 3 starts behind the lists)
-			HIP_CHECK(hipStreamWaitEvent(s3, c->evJoin3, 0));
-		}
-#define FIN_ARGS2(cls) cp, lists2[cls], hc2[cls], nGroups, nHits, c->dGroupStart.p, c->dGroupQuery.p, c->curQuery, c->dLen.p, \
-		qLen, c->dGroupExt.p, c->dCur.p, c->dExt.p, c->dScore.p, c->dBack.p, c->dTmp32.p, c->dCand.p, c->dPrimFlag.p
-#define DP_ARGS2(cls) cp, lists2[cls], hc2[cls], nGroups, nHits, c->dGroupStart.p, c->dGroupQuery.p, c->curQuery, c->dLen.p, qLen, \
-		c->dGroupExtSorted.p, c->dCur.p, c->dExt.p, c->dScore.p, c->dBack.p
-		for (int cls = 2; cls >= 1; --cls)
-		{
-			if (!hc2[cls]) continue;
-			hipStream_t on = cls == 2 ? s3 : s2;
+			if (!n) return;
+			launchPrep(list, n, on);
 			{ ScopedK t(c->timer, "k_chain_dp", on);
-			  hipLaunchKernelGGL(k_chain_dp, (hc2[cls] + DP_WAVES - 1) / DP_WAVES, DP_WAVES * 64, 0, on, DP_ARGS2(cls)); }
-			if (cls == 1 && smallCall2 && hugeMin2 <= (u32)FIN_CAP_M)
+			  hipLaunchKernelGGL(k_chain_dp, (n + DP_WAVES - 1) / DP_WAVES, DP_WAVES * 64, 0, on, DP_ARGS(list, n)); }
+			if (lds)
 			{
 				ScopedK t(c->timer, "k_chain_finish<lds1024>", on);
-				hipLaunchKernelGGL((k_chain_finish<FIN_CAP_M, 1>), hc2[cls], 64, FIN_CAP_M * 20, on, FIN_ARGS2(cls));
+				hipLaunchKernelGGL((k_chain_finish<FIN_CAP_M, 1>), n, 64, FIN_CAP_M * 20, on, FIN_ARGS(list, n));
 			}
 			else
 			{
 				ScopedK t(c->timer, "k_chain_finish<global>", on);
-				hipLaunchKernelGGL((k_chain_finish<0, FIN_WAVES_G, FIN_BT_CAP>), (hc2[cls] + FIN_WAVES_G - 1) / FIN_WAVES_G, FIN_WAVES_G * 64, 0, on,
-								   FIN_ARGS2(cls));
+				hipLaunchKernelGGL((k_chain_finish<0, FIN_WAVES_G, FIN_BT_CAP>), (n + FIN_WAVES_G - 1) / FIN_WAVES_G, FIN_WAVES_G * 64, 0, on,
+								   FIN_ARGS(list, n));
 			}
-		}
-		if (hc2[0])		// groups above the fused kernel's cap that still fit the 256-hit LDS class (FG_FUSED_CAP < 256)
+		};
+		if (side)
 		{
-			{ ScopedK t(c->timer, "k_chain_dp", s2);
-			  hipLaunchKernelGGL(k_chain_dp, (hc2[0] + DP_WAVES - 1) / DP_WAVES, DP_WAVES * 64, 0, s2, DP_ARGS2(0)); }
-			{ ScopedK t(c->timer, "k_chain_finish<lds256>", s2);
-			  hipLaunchKernelGGL((k_chain_finish<FIN_CAP_S, FIN_WAVES_S>), (hc2[0] + FIN_WAVES_S - 1) / FIN_WAVES_S, FIN_WAVES_S * 64,
-								 FIN_CAP_S * 20 * FIN_WAVES_S, s2, FIN_ARGS2(0)); }
+			HIP_CHECK(hipEventRecord(c->evFork, s));
+			if (nMidA) HIP_CHECK(hipStreamWaitEvent(sMid, c->evFork, 0));
+			if (nHuge || nMidB) HIP_CHECK(hipStreamWaitEvent(sHuge, c->evFork, 0));
 		}
-#undef DP_ARGS2
-#undef FIN_ARGS2
-		if (sideStreams)
+		chain(listHuge, nHuge, sHuge, false);
+		chain(listMid, nMidA, sMid, midLds);
+		chain(listMid + nMidA, nMidB, sHuge, midLds);
+		launchSmall();
+		if (side)
 		{
-			HIP_CHECK(hipEventRecord(c->evJoin, s2));
-			HIP_CHECK(hipStreamWaitEvent(s, c->evJoin, 0));
-			if (hc2[2])
+			if (nMidA)
 			{
-				HIP_CHECK(hipEventRecord(c->evJoin3, s3));
+				HIP_CHECK(hipEventRecord(c->evJoin, sMid));
+				HIP_CHECK(hipStreamWaitEvent(s, c->evJoin, 0));
+			}
+			if (nHuge || nMidB)
+			{
+				HIP_CHECK(hipEventRecord(c->evJoin3, sHuge));
 				HIP_CHECK(hipStreamWaitEvent(s, c->evJoin3, 0));
 			}
 		}
 		return;
 	}
+	// FG_CHAIN_FUSED=0, or a fused kernel below its full cap (FG_FUSED_CAP < 256; it runs first): the prefilter over
+	// every (other) listed group, the survivors sorted into the three classes by k_dp_list.
+	launchSmall();
+	if (!nPrep[0] && !nPrep[1]) return;
 	// Both stages below run their big-group class on the side stream beside the small-group class on the main
 	// one: the classes are disjoint sets of groups, and the big-group kernels end with a handful of waves on an
 	// otherwise idle chip (long serial work per wave).  FG_CHAIN_STREAMS=1 puts everything on the main stream.
-	const bool twoStreams = !(getenv("FG_CHAIN_STREAMS") && atoi(getenv("FG_CHAIN_STREAMS")) == 1);
-	auto fork = [&](bool both) -> hipStream_t
 	{
-		if (!twoStreams || !both) return s;
-		HIP_CHECK(hipEventRecord(c->evFork, s));
-		HIP_CHECK(hipStreamWaitEvent(c->stream2, c->evFork, 0));
-		return c->stream2;
-	};
-	auto join = [&](hipStream_t side)
-	{
-		if (side == s) return;
-		HIP_CHECK(hipEventRecord(c->evJoin, side));
-		HIP_CHECK(hipStreamWaitEvent(s, c->evJoin, 0));
-	};
-	{
-		hipStream_t sBig = fork(nPrep[0] && nPrep[1]);
-		const u32* prepList[2] = {c->dListSmall.p, c->dListBig.p};
-#define PREP_ARGS(view, cls) cp, prepList[cls], nPrep[cls], nGroups, nHits, c->dGroupStart.p, c->dGroupQuery.p, c->curQuery, c->dLen.p, qLen, \
-		view, c->dGroupExt.p, c->dCur.p, c->dExt.p, c->dTmp32.p, c->dDpSize.p, c->dGroupExtSorted.p
-		for (int cls = 1; cls >= 0; --cls)
+		hipStream_t sBig = s;
+		if (sideStreams && nPrep[0] && nPrep[1])
 		{
-			if (!nPrep[cls]) continue;
-			hipStream_t on = cls ? sBig : s;
-			ScopedK t(c->timer, "k_group_prep", on);
-			const unsigned gridP = (nPrep[cls] + PREP_WAVES - 1) / PREP_WAVES;
-			if (keyMode == 0)
-				hipLaunchKernelGGL(k_group_prep<u32>, gridP, PREP_WAVES * 64, 0, on,
-								   PREP_ARGS((HitKeyView<u32>{c->dHitKey32.p, c->dHitVal.p, curBits, c->firstId}), cls));
-			else if (keyMode == 1)
-				hipLaunchKernelGGL(k_group_prep<PK>, gridP, PREP_WAVES * 64, 0, on,
-								   PREP_ARGS((HitKeyView<PK>{(const PK*)c->dHitKey.p, nullptr, curBits, c->firstId}), cls));
-			else
-				hipLaunchKernelGGL(k_group_prep<u64>, gridP, PREP_WAVES * 64, 0, on,
-								   PREP_ARGS((HitKeyView<u64>{c->dHitKey.p, c->dHitVal.p, curBits, c->firstId}), cls));
+			HIP_CHECK(hipEventRecord(c->evFork, s));
+			HIP_CHECK(hipStreamWaitEvent(c->stream2, c->evFork, 0));
+			sBig = c->stream2;
 		}
-#undef PREP_ARGS
-		join(sBig);
+		if (nPrep[1]) launchPrep(c->dListBig.p, nPrep[1], sBig);
+		if (nPrep[0]) launchPrep(c->dListSmall.p, nPrep[0], s);
+		if (sBig != s)
+		{
+			HIP_CHECK(hipEventRecord(c->evJoin, sBig));
+			HIP_CHECK(hipStreamWaitEvent(s, c->evJoin, 0));
+		}
 	}
+	// (the group lists of k_group_list are dead once the preps have run)
 	HIP_CHECK(hipMemsetAsync(c->dListCnt.p, 0, 16, s));
-	// A small call (a few hundred reads at most: what a caller thread's single request or the start of a read-ahead
-	// ramp looks like) is all latency: a handful of 257..1024-hit groups then sort and walk in LDS (20 KB per wave,
-	// which the bulk case cannot afford: occupancy) instead of on global scratch, ~1 ms off such a call.
-	const bool smallCall = (nPrep[0] + nPrep[1]) < 65536u && !getenv("FG_CHAIN_NO_SMALL_CALL");
-	const u32 hugeMin = getenv("FG_CHAIN_HUGE_MIN") ? (u32)atoi(getenv("FG_CHAIN_HUGE_MIN")) : (smallCall ? (u32)FIN_CAP_M : 4096u);
+	// the small-call rule: see the classes above
+	const bool smallCall = (nPrep[0] + nPrep[1] + nFused) < 65536u && !getenv("FG_CHAIN_NO_SMALL_CALL");
+	const u32 hugeMin = hugeEnv ? (u32)atoi(hugeEnv) : (smallCall ? (u32)FIN_CAP_M : 4096u);
 	{ ScopedK t(c->timer, "k_dp_list");
-	  hipLaunchKernelGGL(k_dp_list, gridG, WG, 0, s, nGroups, c->dDpSize.p, hugeMin, 0u, c->dListSmall.p, c->dListDp.p,
+	  hipLaunchKernelGGL(k_dp_list, gridG, WG, 0, s, nGroups, c->dDpSize.p, hugeMin, fusedMax, c->dListSmall.p, c->dListDp.p,
 						 c->dListBig.p, c->dListCnt.p); }
 	u32 hc[4];
 	HIP_CHECK(hipMemcpyAsync(c->hScalar.p, c->dListCnt.p, 16, hipMemcpyDeviceToHost, s));
@@ -1314,7 +1340,7 @@ void fgChainStage(fg_ctx* c, const fg_detector_params* p, uint8_t forceLocal, u6
 	const u32* lists[3] = {c->dListSmall.p, c->dListDp.p, c->dListBig.p};	// <= 256 hits, <= hugeMin, more
 	// three independent chains of two kernels: the <= 256-hit groups on the main stream, the two classes of
 	// larger groups (few groups, long serial work per wave) beside them on side streams
-	const bool side = twoStreams && hc[0] && (hc[1] || hc[2]);
+	const bool side = sideStreams && hc[0] && (hc[1] || hc[2]);
 	hipStream_t sMid = s, sHuge = s;
 	if (side)
 	{
@@ -1323,35 +1349,31 @@ void fgChainStage(fg_ctx* c, const fg_detector_params* p, uint8_t forceLocal, u6
 		HIP_CHECK(hipStreamWaitEvent(c->stream3, c->evFork, 0));
 		sMid = c->stream2; sHuge = c->stream3;
 	}
-#define FIN_ARGS(cls) cp, lists[cls], hc[cls], nGroups, nHits, c->dGroupStart.p, c->dGroupQuery.p, c->curQuery, c->dLen.p, \
-		qLen, c->dGroupExt.p, c->dCur.p, c->dExt.p, c->dScore.p, c->dBack.p, c->dTmp32.p, c->dCand.p, c->dPrimFlag.p
-#define DP_ARGS(cls) cp, lists[cls], hc[cls], nGroups, nHits, c->dGroupStart.p, c->dGroupQuery.p, c->curQuery, c->dLen.p, qLen, \
-		c->dGroupExtSorted.p, c->dCur.p, c->dExt.p, c->dScore.p, c->dBack.p
 	for (int cls = 2; cls >= 1; --cls)	// the longest chains first
 	{
 		if (!hc[cls]) continue;
 		hipStream_t on = cls == 2 ? sHuge : sMid;
 		{ ScopedK t(c->timer, "k_chain_dp", on);
-		  hipLaunchKernelGGL(k_chain_dp, (hc[cls] + DP_WAVES - 1) / DP_WAVES, DP_WAVES * 64, 0, on, DP_ARGS(cls)); }
+		  hipLaunchKernelGGL(k_chain_dp, (hc[cls] + DP_WAVES - 1) / DP_WAVES, DP_WAVES * 64, 0, on, DP_ARGS(lists[cls], hc[cls])); }
 		if (cls == 1 && smallCall && hugeMin <= (u32)FIN_CAP_M)
 		{
 			ScopedK t(c->timer, "k_chain_finish<lds1024>", on);
-			hipLaunchKernelGGL((k_chain_finish<FIN_CAP_M, 1>), hc[cls], 64, FIN_CAP_M * 20, on, FIN_ARGS(cls));
+			hipLaunchKernelGGL((k_chain_finish<FIN_CAP_M, 1>), hc[cls], 64, FIN_CAP_M * 20, on, FIN_ARGS(lists[cls], hc[cls]));
 		}
 		else
 		{
 			ScopedK t(c->timer, "k_chain_finish<global>", on);
 			hipLaunchKernelGGL((k_chain_finish<0, FIN_WAVES_G, FIN_BT_CAP>), (hc[cls] + FIN_WAVES_G - 1) / FIN_WAVES_G, FIN_WAVES_G * 64, 0, on,
-							   FIN_ARGS(cls));
+							   FIN_ARGS(lists[cls], hc[cls]));
 		}
 	}
 	if (hc[0])
 	{
 		{ ScopedK t(c->timer, "k_chain_dp");
-		  hipLaunchKernelGGL(k_chain_dp, (hc[0] + DP_WAVES - 1) / DP_WAVES, DP_WAVES * 64, 0, s, DP_ARGS(0)); }
+		  hipLaunchKernelGGL(k_chain_dp, (hc[0] + DP_WAVES - 1) / DP_WAVES, DP_WAVES * 64, 0, s, DP_ARGS(lists[0], hc[0])); }
 		{ ScopedK t(c->timer, "k_chain_finish<lds256>");
 		  hipLaunchKernelGGL((k_chain_finish<FIN_CAP_S, FIN_WAVES_S>), (hc[0] + FIN_WAVES_S - 1) / FIN_WAVES_S, FIN_WAVES_S * 64,
-							 FIN_CAP_S * 20 * FIN_WAVES_S, s, FIN_ARGS(0)); }
+							 FIN_CAP_S * 20 * FIN_WAVES_S, s, FIN_ARGS(lists[0], hc[0])); }
 	}
 	if (side)
 	{

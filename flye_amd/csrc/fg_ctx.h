@@ -275,7 +275,7 @@ struct fg_ctx {
 	int device = 0;
 	int k = 17;
 	hipStream_t stream = nullptr;
-	// side stream of the chaining stage: the big-group kernels run there beside the small-group ones of the main
+	// side streams of the chaining stage: the big-group chains run there beside the small-group kernel of the main
 	// stream (fork / join by events), so that neither class waits for the other's last waves
 	hipStream_t stream2 = nullptr, stream3 = nullptr;
 	hipEvent_t evFork = nullptr, evJoin = nullptr, evJoin3 = nullptr;
