@@ -14,11 +14,10 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
+from edit_craft import ED_BIG_MIN, ED_EMAX        # mirrored from fg_editdist.hip
 from helpers import GOLDEN, golden_lines, golden_queries, golden_reads, hpc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ED_EMAX = 512           # fg_editdist.hip: O(ND) rounds before the bit-vector kernel takes over
-ED_BIG_MIN = 49152      # ... pairs with a longer substring get the 8-wave workgroup
 
 
 # ---- without a GPU ----------------------------------------------------------------------------------------------------
