@@ -450,6 +450,8 @@ struct fg_ctx {
 	DevBuf<char> dCc[40];
 	// fg_expand_cigars (fg_cigar.hip): the call's contig bytes in the first, then the buffers of one sub-batch
 	DevBuf<char> dCig[20];
+	// fg_divergence_profile (fg_divergence.hip): the buffers of one sub-batch, handed out in call order
+	DevBuf<char> dDv[28];
 	PinnedBuf<char> hPrim;
 	PinnedBuf<u64> hOff;
 	PinnedBuf<u64> hScalar;		// staging of the counts the host reads between kernels (pinned: no bounce buffer)

@@ -1,0 +1,533 @@
+// fg_divergence_profile: Trestle's divergent positions (flye/trestle/divergence.py:55-143, _contig_profile, _count_freqs
+// and _call_position) on the device.  Integers and exact compares only; the three rate tests go through tables the host
+// makes in double.
+//
+// Per sub-batch of whole contigs (FG_DIVERGENCE_BATCH_COLS):
+//   k_bub_shift     (fg_gapshift.h) both shift_gaps passes, every alignment.
+//   k_dv_tiles      one wave per tile of DV_TILE columns of one alignment: its non-gap target columns.  An exclusive scan
+//                   over all tiles gives, minus the value at the alignment's first tile, the tile's first position.
+//   k_dv_count      one wave per tile: positions by ballot prefix counts from the tile's base.  A target-gap column adds
+//                   to insertions[position][rank of the query byte] (a '-' against a '-' too), every other column to
+//                   matches[position][rank] and takes nucl by an atomic max of (alignment + 1) << 40 | column << 8 | target
+//                   byte, as k_cc_profile does.  Beside every count stands the smallest (alignment << 32 | column) that
+//                   added to it (atomic min): the moment the key entered the reference's dict.
+//   k_dv_finish     one thread per position: the eight values of _count_freqs, ties of the largest count to the smallest
+//                   tag (max(d, key=d.get) returns the key inserted first), and the flags of _call_position by integer
+//                   compares against minCt[cov], the smallest count with ct / float(cov) >= thresh.
+//   (scan)          four exclusive sums over the flags; k_dv_compact writes the four ascending lists, k_dv_pick takes the
+//                   lists' starts per contig.
+// Integer atomics only: the result does not depend on the schedule.  The host does work proportional to contigs,
+// alignments and (for the byte check) columns.
+#include "fg_ctx.h"
+#include "fg_devprim.h"
+#include "fg_gapshift.h"
+#include <cmath>
+
+namespace {
+
+#define DV_TILE 1024u		// columns per wave of k_dv_tiles / k_dv_count
+#define DV_NONE 0xffu		// rank of a byte no query column holds
+
+struct DvContig { u64 posOff; i32 len; u32 pad; };
+
+// the last i in [0, n) with off[i] <= x (off ascending, off[0] <= x)
+template <class T>
+__device__ __forceinline__ u32 dv_find(const T* __restrict__ off, u32 n, u64 x)
+{
+	u32 lo = 0, hi = n;
+	while (hi - lo > 1)
+	{
+		const u32 mid = (lo + hi) >> 1;
+		if ((u64)off[mid] <= x) lo = mid; else hi = mid;
+	}
+	return lo;
+}
+
+__global__ void __launch_bounds__(BUB_BLOCK)
+k_dv_tiles(const BubAln* __restrict__ alns, u32 nAln, const u32* __restrict__ tileOff, u32 nTiles, const unsigned char* __restrict__ trg,
+		   u32* __restrict__ tileNg)
+{
+	const int lane = threadIdx.x & 63;
+	const u32 w = blockIdx.x * BUB_WAVES + (threadIdx.x >> 6);
+	if (w >= nTiles) return;
+	const u32 a = dv_find(tileOff, nAln, w);
+	const BubAln al = alns[a];
+	const unsigned char* t = trg + al.colOff;
+	const u32 c0 = (w - tileOff[a]) * DV_TILE, c1 = min(c0 + DV_TILE, al.nCols);
+	u32 cnt = 0;
+	for (u32 c = c0; c < c1; c += 64)
+	{
+		const u32 i = c + lane;
+		cnt += (u32)__popcll(__ballot(i < c1 && t[i] != '-'));
+	}
+	if (lane == 0) tileNg[w] = cnt;
+}
+
+__global__ void __launch_bounds__(BUB_BLOCK)
+k_dv_count(const BubAln* __restrict__ alns, u32 nAln, const DvContig* __restrict__ contigs, const u32* __restrict__ tileOff, u32 nTiles,
+		   const u32* __restrict__ tileBase, const unsigned char* __restrict__ trg, const unsigned char* __restrict__ qry,
+		   const unsigned char* __restrict__ rank, u32 nB, u32* matCnt, u32* insCnt, unsigned long long* matFirst,
+		   unsigned long long* insFirst, unsigned long long* tag)
+{
+	const int lane = threadIdx.x & 63;
+	const u32 w = blockIdx.x * BUB_WAVES + (threadIdx.x >> 6);
+	if (w >= nTiles) return;
+	const u32 a = dv_find(tileOff, nAln, w);
+	const BubAln al = alns[a];
+	const DvContig ct = contigs[al.contig];
+	const long long len = ct.len;
+	const unsigned char* t = trg + al.colOff;
+	const unsigned char* q = qry + al.colOff;
+	const u64 below = bub_below(lane);
+	const u32 c0 = (w - tileOff[a]) * DV_TILE, c1 = min(c0 + DV_TILE, al.nCols);
+	long long base = (long long)(tileBase[w] - tileBase[tileOff[a]]);
+	for (u32 cc = c0; cc < c1; cc += 64)
+	{
+		const u32 i = cc + lane;
+		const bool valid = i < c1;
+		const unsigned char tb = valid ? t[i] : (unsigned char)'-', qb = valid ? q[i] : (unsigned char)'-';
+		const bool ng = valid && tb != '-';
+		const u64 m = __ballot(ng);
+		const long long c = base + __popcll(m & below);
+		// a target gap stands at the position before it; index -1 is Python's last element
+		long long pos = ng ? al.trgStart + c : al.trgStart + c - 1;
+		if (pos >= len) pos -= len;
+		if (pos < 0) pos = len - 1;
+		const u32 r = rank[qb & 127];
+		if (valid && pos >= 0 && pos < len && r < nB)
+		{
+			const u64 at = ct.posOff + (u64)pos;
+			const u64 cell = at * nB + r;
+			const unsigned long long first = ((unsigned long long)a << 32) | i;
+			if (ng)
+			{
+				atomicAdd(&matCnt[cell], 1u);
+				atomicMin(&matFirst[cell], first);
+				atomicMax(&tag[at], ((unsigned long long)(a + 1u) << 40) | ((unsigned long long)i << 8) | tb);
+			}
+			else
+			{
+				atomicAdd(&insCnt[cell], 1u);
+				atomicMin(&insFirst[cell], first);
+			}
+		}
+		base += __popcll(m);
+	}
+}
+
+// the largest count of a row among the ranks that pass, ties to the smallest tag
+#define DV_BEST(cntRow, firstRow, skipA, skipB, bestRank, bestCnt)                                      \
+	{                                                                                                   \
+		unsigned long long bestTag = ~0ULL;                                                             \
+		for (u32 r = 0; r < nB; ++r)                                                                    \
+		{                                                                                               \
+			const u32 v = cntRow[r];                                                                    \
+			if (v == 0 || r == skipA || r == skipB) continue;                                           \
+			const unsigned long long f = firstRow[r];                                                   \
+			if (v > bestCnt || (v == bestCnt && f < bestTag)) { bestCnt = v; bestTag = f; bestRank = r; } \
+		}                                                                                               \
+	}
+
+__global__ void __launch_bounds__(BUB_BLOCK)
+k_dv_finish(u32 nPos, const u32* __restrict__ matCnt,
+			const u32* __restrict__ insCnt, const unsigned long long* __restrict__ matFirst, const unsigned long long* __restrict__ insFirst,
+			const unsigned long long* __restrict__ tag, const unsigned char* __restrict__ rank, const unsigned char* __restrict__ byteOf,
+			u32 nB, const u32* __restrict__ minCt, u32 nCov, i32* __restrict__ cov, unsigned char* __restrict__ nucl, i32* __restrict__ matCt,
+			unsigned char* __restrict__ subBase, i32* __restrict__ subCt, i32* __restrict__ delCt, unsigned char* __restrict__ insBase,
+			i32* __restrict__ insCt, unsigned char* __restrict__ flags, u32* __restrict__ isTotal, u32* __restrict__ isSub,
+			u32* __restrict__ isDel, u32* __restrict__ isIns)
+{
+	const u32 g = blockIdx.x * BUB_BLOCK + threadIdx.x;
+	if (g > nPos) return;
+	if (g == nPos) { isTotal[g] = 0; isSub[g] = 0; isDel[g] = 0; isIns[g] = 0; return; }
+	const u32* mRow = matCnt + (u64)g * nB;
+	const u32* iRow = insCnt + (u64)g * nB;
+	const unsigned long long* mFirst = matFirst + (u64)g * nB;
+	const unsigned long long* iFirst = insFirst + (u64)g * nB;
+	const unsigned long long tg = tag[g];
+	const unsigned char nu = tg ? (unsigned char)(tg & 0xffu) : (unsigned char)'-';
+	const u32 rNucl = rank[nu & 127], rGap = rank['-'];
+	u32 total = 0;
+	for (u32 r = 0; r < nB; ++r) total += mRow[r];
+	u32 sRank = DV_NONE, sCnt = 0, iRank = DV_NONE, iCnt = 0;
+	DV_BEST(mRow, mFirst, rNucl, rGap, sRank, sCnt)
+	DV_BEST(iRow, iFirst, DV_NONE, DV_NONE, iRank, iCnt)
+	const u32 mc = rNucl < nB ? mRow[rNucl] : 0u, dc = rGap < nB ? mRow[rGap] : 0u;
+	// cov <= the alignments of the contig < nCov; a table entry says the smallest count that reaches the threshold
+	unsigned char fl = 0;
+	if (total != 0 && total < nCov)
+	{
+		if (sCnt >= minCt[total]) fl |= 1;
+		if (dc >= minCt[nCov + total]) fl |= 2;
+		if (iCnt >= minCt[2 * nCov + total]) fl |= 4;
+	}
+	cov[g] = (i32)total; nucl[g] = nu; matCt[g] = (i32)mc;
+	subBase[g] = sRank != DV_NONE ? byteOf[sRank] : (unsigned char)0; subCt[g] = (i32)sCnt;
+	delCt[g] = (i32)dc;
+	insBase[g] = iRank != DV_NONE ? byteOf[iRank] : (unsigned char)0; insCt[g] = (i32)iCnt;
+	flags[g] = fl;
+	isTotal[g] = fl ? 1u : 0u; isSub[g] = fl & 1 ? 1u : 0u; isDel[g] = fl & 2 ? 1u : 0u; isIns[g] = fl & 4 ? 1u : 0u;
+}
+
+// the four lists: a flagged position writes its index inside its contig at the scanned place
+__global__ void __launch_bounds__(BUB_BLOCK)
+k_dv_compact(u32 nPos, const u64* __restrict__ ctgAt, u32 nC, const unsigned char* __restrict__ flags, const u32* __restrict__ offTotal,
+			 const u32* __restrict__ offSub, const u32* __restrict__ offDel, const u32* __restrict__ offIns, i32* __restrict__ lTotal,
+			 i32* __restrict__ lSub, i32* __restrict__ lDel, i32* __restrict__ lIns)
+{
+	const u32 g = blockIdx.x * BUB_BLOCK + threadIdx.x;
+	if (g >= nPos) return;
+	const unsigned char fl = flags[g];
+	if (!fl) return;
+	const i32 p = (i32)(g - ctgAt[dv_find(ctgAt, nC, g)]);
+	lTotal[offTotal[g]] = p;
+	if (fl & 1) lSub[offSub[g]] = p;
+	if (fl & 2) lDel[offDel[g]] = p;
+	if (fl & 4) lIns[offIns[g]] = p;
+}
+
+// the lists' starts per contig: row k of out = off_k[ctgAt[i]]
+__global__ void __launch_bounds__(BUB_BLOCK)
+k_dv_pick(u32 n, const u64* __restrict__ at, const u32* __restrict__ off0, const u32* __restrict__ off1, const u32* __restrict__ off2,
+		  const u32* __restrict__ off3, u32* __restrict__ out)
+{
+	const u32 i = blockIdx.x * BUB_BLOCK + threadIdx.x;
+	if (i >= n) return;
+	const u64 p = at[i];
+	out[i] = off0[p]; out[n + i] = off1[p]; out[2 * n + i] = off2[p]; out[3 * n + i] = off3[p];
+}
+
+struct DvBufs {
+	fg_ctx* c;
+	int next = 0;
+	template <class T> T* get(size_t count)
+	{
+		if (next >= (int)(sizeof(c->dDv) / sizeof(c->dDv[0]))) throw FgError{FG_ERR_HIP, "internal: fg_divergence buffer pool too small"};
+		DevBuf<char>& b = c->dDv[next++];
+		b.reserve(count * sizeof(T) + 16);
+		return (T*)b.p;
+	}
+};
+
+struct DivergenceOwner {
+	std::vector<uint64_t> listOff[4], profOff;		// total, sub, del, ins
+	std::vector<int32_t> list[4];
+	std::vector<int32_t> cov, matCt, subCt, delCt, insCt;
+	std::vector<uint8_t> nucl, subBase, insBase, flags;
+};
+
+// the smallest count ct with (double)ct / (double)cov >= thresh, as _call_position divides; 0xffffffff: none a
+// sub-batch can reach (its counts stay below 2^31)
+u32 dvMinCount(double thresh, u32 cov)
+{
+	const double want = thresh * (double)cov;
+	if (!(want < 2147483648.0)) return 0xffffffffu;
+	u64 ct = (u64)std::ceil(want);
+	while (ct > 0 && (double)(ct - 1) / (double)cov >= thresh) --ct;
+	while ((double)ct / (double)cov < thresh) ++ct;
+	return ct < 0xffffffffULL ? (u32)ct : 0xffffffffu;
+}
+
+void dvSubBatch(fg_ctx* c, u32 c0, u32 c1, const double* thresh, const int32_t* contigLen, const uint64_t* contigAlnOff,
+				const int32_t* trgStart, const uint64_t* colOff, const uint8_t* trgCols, const uint8_t* qryCols,
+				const unsigned char* rank, const unsigned char* byteOf, u32 nB, bool wantProfile, DivergenceOwner& own)
+{
+	hipStream_t s = c->stream;
+	const u32 nC = c1 - c0;
+	const u64 a0 = contigAlnOff[c0], a1 = contigAlnOff[c1];
+	const u32 nAln = (u32)(a1 - a0);
+	const u64 col0 = nAln ? colOff[a0] : 0, nCols = nAln ? colOff[a1] - col0 : 0;
+
+	std::vector<DvContig> ctg(nC);
+	std::vector<BubAln> alns(nAln);
+	std::vector<u32> tileOff((size_t)nAln + 1, 0);
+	std::vector<u64> ctgAt((size_t)nC + 1);
+	u64 nPos = 0, nTiles = 0, maxAlns = 0;
+	for (u32 i = 0; i < nC; ++i)
+	{
+		ctg[i] = DvContig{nPos, contigLen[c0 + i], 0};
+		ctgAt[i] = nPos;
+		nPos += (u64)contigLen[c0 + i];
+		maxAlns = std::max<u64>(maxAlns, contigAlnOff[c0 + i + 1] - contigAlnOff[c0 + i]);
+		for (u64 a = contigAlnOff[c0 + i]; a < contigAlnOff[c0 + i + 1]; ++a)
+		{
+			BubAln& al = alns[a - a0];
+			al.colOff = colOff[a] - col0; al.nCols = (u32)(colOff[a + 1] - colOff[a]);
+			al.trgStart = trgStart[a]; al.trgEnd = 0; al.contig = i; al.inProfile = 1; al.pad = 0;
+			tileOff[a - a0] = (u32)nTiles;
+			nTiles += ((u64)al.nCols + DV_TILE - 1) / DV_TILE;
+		}
+	}
+	ctgAt[nC] = nPos;
+	tileOff[nAln] = (u32)nTiles;
+	if (nPos >= (1ULL << 31) || nAln >= (1u << 23) || nCols >= (1ULL << 31))
+		throw FgError{FG_ERR_NOMEM, "fg_divergence_profile: a sub-batch of 2^31 positions or columns or 2^23 alignments; lower FG_DIVERGENCE_BATCH_COLS"};
+	if (nPos * nB >= (1ULL << 32))
+		throw FgError{FG_ERR_NOMEM, "fg_divergence_profile: the count tables of a sub-batch have 2^32 cells (" + std::to_string(nB) +
+										" distinct bytes); lower FG_DIVERGENCE_BATCH_COLS"};
+	// a position's coverage is at most the alignments of its contig: every alignment passes a position once
+	const u32 nCov = (u32)maxAlns + 1;
+	std::vector<u32> minCt((size_t)3 * nCov, 0xffffffffu);
+	for (int k = 0; k < 3; ++k)
+		for (u32 v = 1; v < nCov; ++v) minCt[(size_t)k * nCov + v] = dvMinCount(thresh[k], v);
+
+	const u64 nCell = nPos * nB;
+	DvBufs B{c};
+	BubAln* dAln = B.get<BubAln>(nAln);
+	DvContig* dCtg = B.get<DvContig>(nC);
+	u64* dCtgAt = B.get<u64>((size_t)nC + 1);
+	u32* dTileOff = B.get<u32>((size_t)nAln + 1);
+	u32* dTileNg = B.get<u32>(nTiles + 1);
+	unsigned char* dTrg = B.get<unsigned char>(nCols);
+	unsigned char* dQry = B.get<unsigned char>(nCols);
+	unsigned char* dTrgS = B.get<unsigned char>(nCols);
+	unsigned char* dQryS = B.get<unsigned char>(nCols);
+	unsigned char* dTab = B.get<unsigned char>(256);
+	u32* dMinCt = B.get<u32>((size_t)3 * nCov);
+	u32* dCnt = B.get<u32>(2 * nCell);						// matches, insertions
+	unsigned long long* dFirst = B.get<unsigned long long>(2 * nCell);
+	unsigned long long* dTag = B.get<unsigned long long>(nPos);
+	u32* dScan = B.get<u32>(fgprim::scanScratchElems(std::max<u64>(nPos + 1, nTiles + 1)) + 8);
+	i32* dVal = B.get<i32>(5 * nPos);						// cov, mat_ct, sub_ct, del_ct, ins_ct
+	unsigned char* dBytes = B.get<unsigned char>(4 * nPos);	// nucl, sub_base, ins_base, flags
+	u32* dIs = B.get<u32>(4 * (nPos + 1));					// the four flag arrays, then their sums
+	u32* dListAt = B.get<u32>(4 * ((size_t)nC + 1));
+	u32 *dMat = dCnt, *dIns = dCnt + nCell;
+	unsigned long long *dMatFirst = dFirst, *dInsFirst = dFirst + nCell;
+	unsigned char *dNucl = dBytes, *dSubBase = dBytes + nPos, *dInsBase = dBytes + 2 * nPos, *dFlags = dBytes + 3 * nPos;
+	u32* dOff[4];
+	for (int k = 0; k < 4; ++k) dOff[k] = dIs + (size_t)k * (nPos + 1);
+
+	HIP_CHECK(hipMemcpyAsync(dAln, alns.data(), (size_t)nAln * sizeof(BubAln), hipMemcpyHostToDevice, s));
+	HIP_CHECK(hipMemcpyAsync(dCtg, ctg.data(), (size_t)nC * sizeof(DvContig), hipMemcpyHostToDevice, s));
+	HIP_CHECK(hipMemcpyAsync(dCtgAt, ctgAt.data(), ((size_t)nC + 1) * 8, hipMemcpyHostToDevice, s));
+	HIP_CHECK(hipMemcpyAsync(dTileOff, tileOff.data(), ((size_t)nAln + 1) * 4, hipMemcpyHostToDevice, s));
+	HIP_CHECK(hipMemcpyAsync(dMinCt, minCt.data(), (size_t)3 * nCov * 4, hipMemcpyHostToDevice, s));
+	if (nCols)
+	{
+		HIP_CHECK(hipMemcpyAsync(dTrg, trgCols + col0, nCols, hipMemcpyHostToDevice, s));
+		HIP_CHECK(hipMemcpyAsync(dQry, qryCols + col0, nCols, hipMemcpyHostToDevice, s));
+	}
+	HIP_CHECK(hipMemcpyAsync(dTab, rank, 128, hipMemcpyHostToDevice, s));
+	HIP_CHECK(hipMemcpyAsync(dTab + 128, byteOf, 128, hipMemcpyHostToDevice, s));
+	HIP_CHECK(hipMemsetAsync(dCnt, 0, 2 * nCell * 4 + 4, s));
+	HIP_CHECK(hipMemsetAsync(dFirst, 0xff, 2 * nCell * 8 + 8, s));
+	HIP_CHECK(hipMemsetAsync(dTag, 0, nPos * 8 + 8, s));
+	HIP_CHECK(hipMemsetAsync(dTileNg, 0, (nTiles + 1) * 4, s));
+
+	if (nAln)
+	{
+		ScopedK t(c->timer, "k_bub_shift");
+		hipLaunchKernelGGL(k_bub_shift, bubWaveGrid(nAln), BUB_BLOCK, 0, s, dAln, nAln, dTrg, dQry, dQryS);
+		hipLaunchKernelGGL(k_bub_shift, bubWaveGrid(nAln), BUB_BLOCK, 0, s, dAln, nAln, dQryS, dTrg, dTrgS);
+	}
+	if (nTiles)
+	{
+		{
+			ScopedK t(c->timer, "k_dv_tiles");
+			hipLaunchKernelGGL(k_dv_tiles, bubWaveGrid(nTiles), BUB_BLOCK, 0, s, dAln, nAln, dTileOff, (u32)nTiles, dTrgS, dTileNg);
+		}
+		{
+			ScopedK t(c->timer, "k_dv_scan");
+			fgprim::scan<u32>(s, dTileNg, dTileNg, nTiles + 1, false, dScan);
+		}
+		ScopedK t(c->timer, "k_dv_count");
+		hipLaunchKernelGGL(k_dv_count, bubWaveGrid(nTiles), BUB_BLOCK, 0, s, dAln, nAln, dCtg, dTileOff, (u32)nTiles, dTileNg, dTrgS, dQryS, dTab,
+						   nB, dMat, dIns, dMatFirst, dInsFirst, dTag);
+	}
+	{
+		ScopedK t(c->timer, "k_dv_finish");
+		hipLaunchKernelGGL(k_dv_finish, bubGrid(nPos + 1), BUB_BLOCK, 0, s, (u32)nPos, dMat, dIns, dMatFirst, dInsFirst, dTag,
+						   dTab, dTab + 128, nB, dMinCt, nCov, dVal, dNucl, dVal + nPos, dSubBase, dVal + 2 * nPos,
+						   dVal + 3 * nPos, dInsBase, dVal + 4 * nPos, dFlags, dOff[0], dOff[1], dOff[2], dOff[3]);
+	}
+	{
+		ScopedK t(c->timer, "k_dv_scan");
+		for (int k = 0; k < 4; ++k) fgprim::scan<u32>(s, dOff[k], dOff[k], nPos + 1, false, dScan);
+		hipLaunchKernelGGL(k_dv_pick, bubGrid((u64)nC + 1), BUB_BLOCK, 0, s, nC + 1, dCtgAt, dOff[0], dOff[1], dOff[2], dOff[3], dListAt);
+	}
+	HIP_CHECK(hipGetLastError());
+	std::vector<u32> listAt(4 * ((size_t)nC + 1));
+	HIP_CHECK(hipMemcpyAsync(listAt.data(), dListAt, listAt.size() * 4, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(hipStreamSynchronize(s));
+	u32 nList[4];
+	i32* dList[4];
+	for (int k = 0; k < 4; ++k)
+	{
+		nList[k] = listAt[(size_t)k * (nC + 1) + nC];
+		dList[k] = B.get<i32>(nList[k]);
+	}
+	if (nList[0])
+	{
+		ScopedK t(c->timer, "k_dv_compact");
+		hipLaunchKernelGGL(k_dv_compact, bubGrid(nPos), BUB_BLOCK, 0, s, (u32)nPos, dCtgAt, nC, dFlags, dOff[0], dOff[1], dOff[2], dOff[3],
+						   dList[0], dList[1], dList[2], dList[3]);
+	}
+	HIP_CHECK(hipGetLastError());
+	for (int k = 0; k < 4; ++k)
+	{
+		const size_t base = own.list[k].size();
+		own.list[k].resize(base + nList[k]);
+		if (nList[k]) HIP_CHECK(hipMemcpyAsync(own.list[k].data() + base, dList[k], (size_t)nList[k] * 4, hipMemcpyDeviceToHost, s));
+		for (u32 i = 0; i < nC; ++i) own.listOff[k].push_back(base + listAt[(size_t)k * (nC + 1) + i + 1]);
+	}
+	if (wantProfile)
+	{
+		const size_t at = own.cov.size();
+		for (u32 i = 0; i < nC; ++i) own.profOff.push_back(at + ctgAt[i + 1]);
+		std::vector<int32_t>* v32[5] = {&own.cov, &own.matCt, &own.subCt, &own.delCt, &own.insCt};
+		std::vector<uint8_t>* v8[4] = {&own.nucl, &own.subBase, &own.insBase, &own.flags};
+		for (int k = 0; k < 5; ++k)
+		{
+			v32[k]->resize(at + nPos);
+			if (nPos) HIP_CHECK(hipMemcpyAsync(v32[k]->data() + at, dVal + (size_t)k * nPos, nPos * 4, hipMemcpyDeviceToHost, s));
+		}
+		for (int k = 0; k < 4; ++k)
+		{
+			v8[k]->resize(at + nPos);
+			if (nPos) HIP_CHECK(hipMemcpyAsync(v8[k]->data() + at, dBytes + (size_t)k * nPos, nPos, hipMemcpyDeviceToHost, s));
+		}
+	}
+	HIP_CHECK(hipStreamSynchronize(s));
+}
+
+u64 dvEnvU64(const char* name, u64 dflt)
+{
+	const char* e = getenv(name);
+	return e ? strtoull(e, nullptr, 10) : dflt;
+}
+
+} // namespace
+
+extern "C" {
+
+int fg_divergence_profile(fg_ctx* c, double sub_thresh, double del_thresh, double ins_thresh, uint32_t n_contigs,
+						  const int32_t* contig_len, const uint64_t* contig_aln_off, const int32_t* trg_start, const uint64_t* col_off,
+						  const uint8_t* trg_cols, const uint8_t* qry_cols, uint8_t want_profile, struct fg_divergence_batch* out)
+{
+	if (!c) return FG_ERR_ARG;
+	if (out) memset(out, 0, sizeof(*out));
+	DivergenceOwner* own = nullptr;
+	int rc = FG_OK;
+	try
+	{
+		const std::string name = "fg_divergence_profile";
+		if (!out) throw FgError{FG_ERR_ARG, name + ": null result"};
+		const double thresh[3] = {sub_thresh, del_thresh, ins_thresh};
+		for (double t : thresh)
+			if (!(t >= 0.0)) throw FgError{FG_ERR_ARG, name + ": a threshold that is NaN or negative"};
+		if (n_contigs && (!contig_len || !contig_aln_off)) throw FgError{FG_ERR_ARG, name + ": null contig_len or contig_aln_off"};
+		for (u32 i = 0; i < n_contigs; ++i)
+		{
+			if (contig_len[i] < 0) throw FgError{FG_ERR_ARG, name + ": contig_len < 0 at contig " + std::to_string(i)};
+			if (contig_aln_off[i + 1] < contig_aln_off[i])
+				throw FgError{FG_ERR_ARG, name + ": contig_aln_off decreases at contig " + std::to_string(i)};
+		}
+		const u64 a0 = n_contigs ? contig_aln_off[0] : 0, a1 = n_contigs ? contig_aln_off[n_contigs] : 0;
+		if (a1 > a0 && (!trg_start || !col_off)) throw FgError{FG_ERR_ARG, name + ": null trg_start or col_off"};
+		for (u64 a = a0; a < a1; ++a)
+		{
+			if (col_off[a + 1] < col_off[a]) throw FgError{FG_ERR_ARG, name + ": col_off decreases at alignment " + std::to_string(a)};
+			if (col_off[a + 1] - col_off[a] >= (1ULL << 31)) throw FgError{FG_ERR_ARG, name + ": an alignment of 2^31 columns"};
+		}
+		if (a1 > a0 && col_off[a1] > col_off[a0] && (!trg_cols || !qry_cols)) throw FgError{FG_ERR_ARG, name + ": null trg_cols or qry_cols"};
+		bool present[128] = {};
+		for (u32 i = 0; i < n_contigs; ++i)
+			for (u64 a = contig_aln_off[i]; a < contig_aln_off[i + 1]; ++a)
+			{
+				u64 nonGap = 0;
+				for (u64 k = col_off[a]; k < col_off[a + 1]; ++k)
+				{
+					if ((trg_cols[k] | qry_cols[k]) >= 128) throw FgError{FG_ERR_ARG, name + ": a byte >= 128 in alignment " + std::to_string(a)};
+					nonGap += trg_cols[k] != '-';
+					present[qry_cols[k]] = true;
+				}
+				if (trg_start[a] < 0 || trg_start[a] >= contig_len[i])
+					throw FgError{FG_ERR_ARG, name + ": trg_start outside the contig at alignment " + std::to_string(a)};
+				if (nonGap > (u64)contig_len[i])
+					throw FgError{FG_ERR_ARG, name + ": alignment " + std::to_string(a) + " has more target bases than its contig"};
+			}
+		// the query bytes of the call, ranked in byte order: the width of the count tables
+		unsigned char rank[128], byteOf[128] = {};
+		memset(rank, DV_NONE, sizeof(rank));
+		u32 nB = 0;
+		for (int b = 0; b < 128; ++b)
+			if (present[b]) { rank[b] = (unsigned char)nB; byteOf[nB++] = (unsigned char)b; }
+		if (nB == 0) { rank['-'] = 0; byteOf[0] = '-'; nB = 1; }
+		// a contig counts its columns and a table row per position
+		std::vector<u64> cost(n_contigs, 0);
+		for (u32 i = 0; i < n_contigs; ++i)
+		{
+			cost[i] = (u64)contig_len[i] * nB;
+			if (contig_aln_off[i + 1] > contig_aln_off[i]) cost[i] += col_off[contig_aln_off[i + 1]] - col_off[contig_aln_off[i]];
+		}
+		const u64 budget = dvEnvU64("FG_DIVERGENCE_BATCH_COLS", 1ULL << 27);
+		u64 maxContigs = ~0ULL;			// a switch for tests: contigs per sub-batch
+		if (getenv("FG_DIVERGENCE_BATCH_CONTIGS")) maxContigs = std::max<u64>(1, dvEnvU64("FG_DIVERGENCE_BATCH_CONTIGS", 1));
+		for (u32 i = 0; i < n_contigs; ++i)
+			if (cost[i] > budget)
+				throw FgError{FG_ERR_NOMEM, name + ": contig " + std::to_string(i) + " alone has " + std::to_string(cost[i]) +
+												" columns and table cells, FG_DIVERGENCE_BATCH_COLS is " + std::to_string(budget)};
+		own = new DivergenceOwner;
+		for (auto& v : own->listOff) v.assign(1, 0);
+		if (want_profile) own->profOff.assign(1, 0);
+		HIP_CHECK(hipSetDevice(c->device));
+		c->timer.reset();
+		u32 i = 0;
+		while (i < n_contigs)
+		{
+			u32 j = i;
+			u64 used = 0;
+			while (j < n_contigs && (j == i || (used + cost[j] <= budget && j - i < maxContigs))) used += cost[j++];
+			dvSubBatch(c, i, j, thresh, contig_len, contig_aln_off, trg_start, col_off, trg_cols, qry_cols, rank, byteOf, nB, want_profile != 0, *own);
+			i = j;
+		}
+		c->timer.collect();
+		for (auto& v : own->list)
+			if (v.empty()) v.reserve(1);
+		for (auto* v : {&own->cov, &own->matCt, &own->subCt, &own->delCt, &own->insCt})
+			if (v->empty()) v->reserve(1);
+		for (auto* v : {&own->nucl, &own->subBase, &own->insBase, &own->flags})
+			if (v->empty()) v->reserve(1);
+	}
+	catch (const FgError& e) { c->lastError = e.msg; rc = e.code; }
+	catch (const std::bad_alloc&) { c->lastError = "host allocation failed"; rc = FG_ERR_NOMEM; }
+	catch (const std::exception& e) { c->lastError = e.what(); rc = FG_ERR_HIP; }
+	if (rc != FG_OK)
+	{
+		// launches of a call that failed half way drain before the context's scratch is used again
+		if (c->stream) (void)hipStreamSynchronize(c->stream);
+		c->timer.reset();
+		delete own;
+		return rc;
+	}
+	out->n_contigs = n_contigs;
+	out->total_off = own->listOff[0].data(); out->total_pos = own->list[0].data();
+	out->sub_off = own->listOff[1].data(); out->sub_pos = own->list[1].data();
+	out->del_off = own->listOff[2].data(); out->del_pos = own->list[2].data();
+	out->ins_off = own->listOff[3].data(); out->ins_pos = own->list[3].data();
+	if (want_profile)
+	{
+		out->prof_off = own->profOff.data();
+		out->cov = own->cov.data();
+		out->nucl = own->nucl.data();
+		out->mat_ct = own->matCt.data();
+		out->sub_base = own->subBase.data();
+		out->sub_ct = own->subCt.data();
+		out->del_ct = own->delCt.data();
+		out->ins_base = own->insBase.data();
+		out->ins_ct = own->insCt.data();
+		out->flags = own->flags.data();
+	}
+	out->owner_ = own;
+	return FG_OK;
+}
+
+void fg_release_divergence(struct fg_divergence_batch* b)
+{
+	if (!b) return;
+	delete (DivergenceOwner*)b->owner_;
+	memset(b, 0, sizeof(*b));
+}
+
+} // extern "C"

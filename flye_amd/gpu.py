@@ -20,6 +20,9 @@ like calls into the reference:
   without the SAM reader and the FASTA writer)
 * ``SamAlignments(ctx, sam_path, contigs, max_coverage, use_secondary).chunks() / by_contig()``
   (flye/utils/sam_parser.py:123-404, SynchronizedSamReader: get_chunk on fg_expand_cigars)
+* ``DivergenceFinder(ctx).find_divergence(alignment_path, contigs_path, contigs_info, frequency_path, positions_path,
+  div_sum_path, sub_thresh, del_thresh, ins_thresh)`` / ``profile``  (flye/trestle/divergence.py:55-232, on
+  fg_divergence_profile)
 
 There is no CPU fallback: if the HIP library or a device is missing every entry
 point raises ``FlyeGpuError``.
@@ -60,7 +63,7 @@ ABI_SYMBOLS = ["fg_abi_version", "fg_create", "fg_destroy", "fg_strerror", "fg_l
                "fg_edge_coverage", "fg_release_edge_coverage",
                "fg_subs_matrix_load", "fg_polish_bubbles", "fg_release_polish", "fg_make_bubbles", "fg_release_bubbles",
                "fg_uniform_alignments", "fg_release_uniform", "fg_contig_consensus", "fg_release_consensus",
-               "fg_expand_cigars", "fg_release_expand", "fg_cigar_parse",
+               "fg_expand_cigars", "fg_release_expand", "fg_cigar_parse", "fg_divergence_profile", "fg_release_divergence",
                "fg_index_keep_targets", "fg_index_shard", "fg_probe_hits", "fg_overlaps_from_hits",
                "fg_index_piece_split", "fg_index_scatter_begin", "fg_index_scatter_end", "fg_debug_probe_skip_check",
                "fg_group_create", "fg_group_destroy", "fg_group_size", "fg_group_member", "fg_group_last_error",
@@ -242,6 +245,17 @@ class ExpandBatch(C.Structure):
                 ("matches", C.POINTER(C.c_int64)), ("err_rate", C.POINTER(C.c_double)), ("owner_", C.c_void_p)]
 
 
+class DivergenceBatch(C.Structure):
+    """struct fg_divergence_batch"""
+    _fields_ = [("n_contigs", C.c_uint32), ("pad_", C.c_uint32), ("total_off", C.POINTER(C.c_uint64)),
+                ("total_pos", C.POINTER(C.c_int32)), ("sub_off", C.POINTER(C.c_uint64)), ("sub_pos", C.POINTER(C.c_int32)),
+                ("del_off", C.POINTER(C.c_uint64)), ("del_pos", C.POINTER(C.c_int32)), ("ins_off", C.POINTER(C.c_uint64)),
+                ("ins_pos", C.POINTER(C.c_int32)), ("prof_off", C.POINTER(C.c_uint64)), ("cov", C.POINTER(C.c_int32)),
+                ("nucl", C.POINTER(C.c_uint8)), ("mat_ct", C.POINTER(C.c_int32)), ("sub_base", C.POINTER(C.c_uint8)),
+                ("sub_ct", C.POINTER(C.c_int32)), ("del_ct", C.POINTER(C.c_int32)), ("ins_base", C.POINTER(C.c_uint8)),
+                ("ins_ct", C.POINTER(C.c_int32)), ("flags", C.POINTER(C.c_uint8)), ("owner_", C.c_void_p)]
+
+
 class BridgeStats(C.Structure):
     _fields_ = [("device_calls", C.c_uint64), ("reads_computed", C.c_uint64), ("requests", C.c_uint64),
                 ("cache_hits", C.c_uint64), ("cached_overlaps", C.c_uint64), ("reads_ahead", C.c_uint64),
@@ -381,6 +395,10 @@ def load_library():
         L.fg_release_expand.argtypes = [C.POINTER(ExpandBatch)]
         L.fg_release_expand.restype = None
         L.fg_cigar_parse.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.fg_divergence_profile.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_uint32] + [C.c_void_p] * 6 + \
+            [C.c_uint8, C.POINTER(DivergenceBatch)]
+        L.fg_release_divergence.argtypes = [C.POINTER(DivergenceBatch)]
+        L.fg_release_divergence.restype = None
         L.fg_debug_group_bin_cuts.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         L.fg_debug_freq_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
         L.fg_debug_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int]
@@ -658,6 +676,15 @@ class ExpandResult(BubbleResult):
     def columns(self, a):
         lo, hi = int(self.col_off[a]), int(self.col_off[a + 1])
         return self.trg_cols[lo:hi].tobytes(), self.qry_cols[lo:hi].tobytes()
+
+
+class DivergenceResult(BubbleResult):
+    """fg_divergence_batch copied out of its arena, arrays under the names of the header (the per-position arrays None
+    without want_profile).  positions(i) gives contig i's four lists as the reference's dictionary."""
+
+    def positions(self, i):
+        return {k: [int(p) for p in getattr(self, k + "_pos")[int(getattr(self, k + "_off")[i]):int(getattr(self, k + "_off")[i + 1])]]
+                for k in ("total", "sub", "del", "ins")}
 
 
 def cigar_parse(cigar):
@@ -1162,6 +1189,48 @@ class Context:
             out["ins"] = take(b.ins, int(out["ins_off"][npos]), np.uint8)
         self.L.fg_release_consensus(C.byref(b))
         return ConsensusResult(**out)
+
+    def divergence_profile(self, sub_thresh, del_thresh, ins_thresh, contig_len, contig_aln_off, trg_start, col_off, trg_cols,
+                           qry_cols, want_profile=False):
+        """fg_divergence_profile: _contig_profile, _count_freqs and _call_position of the reference's
+        flye/trestle/divergence.py for a batch of contigs in the layout of make_bubbles; every alignment takes part.
+        Returns a DivergenceResult."""
+        cl = np.ascontiguousarray(contig_len, np.int32)
+        n = len(cl)
+        cao = np.ascontiguousarray(contig_aln_off, np.uint64)
+        ts = np.ascontiguousarray(trg_start, np.int32)
+        co = np.ascontiguousarray(col_off, np.uint64)
+        tc, qc = np.frombuffer(bytes(trg_cols), np.uint8), np.frombuffer(bytes(qry_cols), np.uint8)
+        if len(cao) != n + 1 or len(tc) != len(qc) or (n and int(cao.max()) > len(ts)) or (len(ts) and len(co) != len(ts) + 1) or \
+                (len(co) and int(co.max()) > len(tc)):
+            raise ValueError("divergence_profile: offsets outside their arrays")
+        ptr = lambda a: a.ctypes.data if a is not None and len(a) else None
+        b = DivergenceBatch()
+        t0 = time.perf_counter()
+        self._check(self.L.fg_divergence_profile(self.h, float(sub_thresh), float(del_thresh), float(ins_thresh), n, ptr(cl),
+                                                 cao.ctypes.data, ptr(ts), ptr(co), ptr(tc), ptr(qc), int(bool(want_profile)),
+                                                 C.byref(b)))
+        self.last_divergence_seconds = time.perf_counter() - t0
+
+        def take(p, k, dtype):
+            return np.ctypeslib.as_array(p, (k,)).copy() if k else np.zeros(0, dtype)
+
+        out = {}
+        for k in ("total", "sub", "del", "ins"):
+            out[k + "_off"] = take(getattr(b, k + "_off"), n + 1, np.uint64)
+            out[k + "_pos"] = take(getattr(b, k + "_pos"), int(out[k + "_off"][n]), np.int32)
+        profile = (("cov", np.int32), ("nucl", np.uint8), ("mat_ct", np.int32), ("sub_base", np.uint8), ("sub_ct", np.int32),
+                   ("del_ct", np.int32), ("ins_base", np.uint8), ("ins_ct", np.int32), ("flags", np.uint8))
+        out["prof_off"] = None
+        for k, _ in profile:
+            out[k] = None
+        if want_profile:
+            out["prof_off"] = take(b.prof_off, n + 1, np.uint64)
+            npos = int(out["prof_off"][n])
+            for k, t in profile:
+                out[k] = take(getattr(b, k), npos, t)
+        self.L.fg_release_divergence(C.byref(b))
+        return DivergenceResult(**out)
 
     def expand_cigars(self, contig_off, contig_seq, aln_contig, ctg_pos, run_off, run_op, run_len, read_off, read_seq,
                       want_cols=True):
@@ -2192,6 +2261,122 @@ class ContigConsensus:
             if len(seq) > 0:
                 out[c.id] = seq.decode("latin-1")
         return out, total / (len(self.aln_errors) + 1)
+
+
+class DivergenceFinder:
+    """Mirror of the reference's find_divergence (flye/trestle/divergence.py:146-232) on fg_divergence_profile: the SAM
+    file goes through SamAlignments (with max_read_coverage, as the reference's reader), every contig with records
+    through ONE device call, and the three text files are written with the reference's format strings.  Kept from the
+    reference: each contig's result overwrites the files, so they hold the last contig in chunk order (the reference at
+    num_proc = 1; Trestle passes one template); a file without an aligned record writes nothing.  Where a file is
+    missing the reference ends in ValueError (_get_median of an empty list); so does this, before it writes anything."""
+
+    WINDOW = 1000
+
+    def __init__(self, ctx: Context, max_read_coverage=1000):
+        self.ctx = ctx
+        self.max_read_coverage = max_read_coverage
+        self.result, self.aln_errors = None, []
+
+    # read_sequence_dict hands the reader contigs whose IUPAC codes stand for A, C, G, T in turn, case kept
+    IUPAC = b"URYKMSWBVDHNX"
+    TO_ACGT = bytes.maketrans(IUPAC + IUPAC.lower(), (b"ACGT" * 4)[:13] + (b"acgt" * 4)[:13])
+
+    @classmethod
+    def read_fasta(cls, path):
+        """{header up to the first blank: sequence} of a FASTA file, plain or .gz, as bytes, non-ACGT codes replaced as
+        the reference's read_sequence_dict replaces them"""
+        opener = gzip.open if path.endswith(".gz") else open
+        out, header = {}, None
+        with opener(path, "rb") as f:
+            for line in f:
+                line = line.strip()
+                if line.startswith(b">"):
+                    header = line[1:].split()[0]
+                    out[header] = []
+                elif line and header is not None:
+                    out[header].append(line)
+        return {h: b"".join(s).translate(cls.TO_ACGT) for h, s in out.items() if s}
+
+    def profile(self, alignments_by_contig, contigs, sub_thresh, del_thresh, ins_thresh, want_profile=True):
+        """one device call for the contigs (records with id and length) in order -> DivergenceResult; aln_errors takes
+        the err_rate of every alignment, as _contig_profile returns them"""
+        lists = [alignments_by_contig.get(c.id, []) for c in contigs]
+        alns = [a for lst in lists for a in lst]
+        self.aln_errors = [a.err_rate for a in alns]
+        self.result = self.ctx.divergence_profile(
+            sub_thresh, del_thresh, ins_thresh, [c.length for c in contigs], np.cumsum([0] + [len(lst) for lst in lists]),
+            [a.trg_start for a in alns], np.cumsum([0] + [len(a.trg_seq) for a in alns]),
+            "".join(a.trg_seq for a in alns).encode("latin-1"), "".join(a.qry_seq for a in alns).encode("latin-1"), want_profile)
+        return self.result
+
+    @staticmethod
+    def frequency_text(res, i):
+        """the lines _write_frequency_path writes for contig i of a result with its profile"""
+        lo, hi = int(res.prof_off[i]), int(res.prof_off[i + 1])
+        out = ["Index\tCov\tMatch\tCount\tSub\tCount\tDel\tCount\tIns\tCount\n"]
+        char = [chr(b) for b in range(128)]
+        char[0] = ""
+        for k, (cov, nucl, mat, sb, sc, dc, ib, ic) in enumerate(zip(
+                res.cov[lo:hi].tolist(), res.nucl[lo:hi].tolist(), res.mat_ct[lo:hi].tolist(), res.sub_base[lo:hi].tolist(),
+                res.sub_ct[lo:hi].tolist(), res.del_ct[lo:hi].tolist(), res.ins_base[lo:hi].tolist(), res.ins_ct[lo:hi].tolist())):
+            out.append("%d\t%d\t%s\t%d\t%s\t%d\t-\t%d\t^%s\t%d\n" % (k, cov, char[nucl], mat, char[sb], sc, dc, char[ib], ic))
+        return "".join(out)
+
+    @staticmethod
+    def positions_text(pos, sub_thresh, del_thresh, ins_thresh):
+        """the four headers and lists of _write_positions"""
+        heads = ("Total_positions_{0}_with_thresholds_sub_{1}_del_{2}_ins_{3}".format(len(pos["total"]), sub_thresh, del_thresh, ins_thresh),
+                 "Sub_positions_{0}_with_threshold_sub_{1}".format(len(pos["sub"]), sub_thresh),
+                 "Del_positions_{0}_with_threshold_del_{1}".format(len(pos["del"]), del_thresh),
+                 "Ins_positions_{0}_with_threshold_ins_{1}".format(len(pos["ins"]), ins_thresh))
+        return "".join(">{0}\n{1}\n".format(h, ",".join(str(x) for x in pos[k])) for h, k in zip(heads, ("total", "sub", "del", "ins")))
+
+    @classmethod
+    def summary_text(cls, pos, seq_len):
+        """_write_div_summary: the gaps between called positions and the divergence of windows of 1000"""
+        called = pos["total"]
+        gaps = [b - a for a, b in zip([0] + called, called + [seq_len])]
+        n_win = (seq_len - 1) // cls.WINDOW + 1
+        counts = [0] * max(n_win, 0)
+        for p in called:
+            counts[p // cls.WINDOW] += 1
+        divs = [counts[w] / float(min((w + 1) * cls.WINDOW, seq_len) - w * cls.WINDOW) for w in range(len(counts))]
+        if not divs:
+            raise ValueError("_get_median() arg is an empty sequence")
+        ordered = sorted(divs)
+        mid = len(divs) // 2
+        median = ordered[mid] if len(divs) % 2 else (ordered[mid - 1] + ordered[mid]) / 2
+        rows = (("Sequence Length:", "{1}", seq_len, "\n"), ("Average Divergence:", "{1:.4f}", len(called) / float(seq_len), "\n\n"),
+                ("Total Substitution Positions:", "{1}", len(pos["sub"]), "\n"), ("Total Deletion Positions:", "{1}", len(pos["del"]), "\n"),
+                ("Total Insertion Positions:", "{1}", len(pos["ins"]), "\n"), ("Total Positions:", "{1}", len(called), "\n"),
+                ("Mixed Positions:", "{1}", len(pos["sub"]) + len(pos["del"]) + len(pos["ins"]) - len(called), "\n\n"),
+                ("Mean Position Gap:", "{1:.2f}", sum(gaps) / len(gaps), "\n"), ("Max Position Gap:", "{1}", max(gaps), "\n"),
+                ("Window Length:", "{1}", cls.WINDOW, "\n"), ("Mean Window Divergence:", "{1:.5f}", sum(divs) / len(divs), "\n"),
+                ("Median Window Divergence:", "{1:.5f}", median, "\n"), ("Min Window Divergence:", "{1:.5f}", min(divs), "\n"))
+        return "Tentative Divergent Position Summary\n\n" + "".join(("{0:33}\t" + fmt + end).format(label, value)
+                                                                   for label, fmt, value, end in rows)
+
+    def find_divergence(self, alignment_path, contigs_path, contigs_info, frequency_path, positions_path, div_sum_path,
+                        sub_thresh, del_thresh, ins_thresh):
+        """-> mean_aln_error = sum(err_rate) / (n + 1), which the reference logs.  contigs_info maps contig id to a record
+        with length."""
+        if not os.path.isfile(alignment_path) or not os.path.isfile(contigs_path):
+            raise ValueError("_get_median() arg is an empty sequence")
+        sam = SamAlignments(self.ctx, alignment_path, self.read_fasta(contigs_path), self.max_read_coverage)
+        chunks = sam.chunks()
+        Contig = collections.namedtuple("Contig", ["id", "length"])
+        contigs = [Contig(cid, contigs_info[cid].length) for cid, _ in chunks]
+        res = self.profile(dict(chunks), contigs, sub_thresh, del_thresh, ins_thresh)
+        if contigs:                                     # every contig overwrites the files: the last one stays
+            i = len(contigs) - 1
+            pos = res.positions(i)
+            texts = ((frequency_path, self.frequency_text(res, i)), (positions_path, self.positions_text(pos, sub_thresh, del_thresh, ins_thresh)),
+                     (div_sum_path, self.summary_text(pos, contigs[i].length)))
+            for path, text in texts:
+                with open(path, "w") as f:
+                    f.write(text)
+        return sum(self.aln_errors) / (len(self.aln_errors) + 1)
 
 
 # the reference's Alignment tuple (flye/utils/sam_parser.py:44-48)

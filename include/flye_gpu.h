@@ -973,6 +973,60 @@ void fg_release_expand(struct fg_expand_batch* b);
  * or written. */
 int  fg_cigar_parse(const char* cigar, uint64_t n_bytes, uint8_t* ops, uint32_t* lens, uint64_t cap, uint64_t* n_runs);
 
+/* Trestle's divergent positions (flye/trestle/divergence.py:55-143: _contig_profile, _count_freqs and _call_position) for a
+ * batch of contigs.  The contig and alignment arrays are those of fg_make_bubbles and fg_contig_consensus (offsets need
+ * not start at zero).  Every alignment takes part, in list order: there is no uniform step and no error filter.
+ * Both shift_gaps passes run first (see fg_make_bubbles).  A non-gap target column c lands at trg_start + c, wrapped once
+ * at contig_len; a target-gap column at the position before it, and before position 0 that is contig_len - 1: Python's
+ * index -1 is the last element.  A target-gap column counts insertions[query byte] of its position for that one byte (a
+ * '-' against a '-' counts insertions['-']); every other column sets nucl to the target byte (the last alignment in list
+ * order wins) and counts matches[query byte].  Per position: cov = the sum of matches; mat_ct = matches[nucl]; del_ct =
+ * matches['-']; (sub_base, sub_ct) = the key of the largest count among the keys of matches other than nucl and '-';
+ * (ins_base, ins_ct) likewise among all keys of insertions ('-' included).  Ties of the largest count go to the key that
+ * entered the reference's dict first, as max(d, key=d.get) returns it: the alignment earliest in list order, then the
+ * earliest column -- not the smallest byte.  Without a key sub_base / ins_base are 0 and the count is 0.
+ * A position with cov != 0 is called for substitutions when sub_ct / (double)cov >= sub_thresh in double, and likewise
+ * for deletions (del_ct) and insertions (ins_ct, which may exceed cov): flags = 1 (sub) | 2 (del) | 4 (ins).  The device
+ * does not divide: it compares with the smallest passing count per coverage, tabulated on the host.  The four lists hold
+ * the positions (indices inside the contig, ascending) with any flag, flag 1, flag 2 and flag 4; contig i's part of a
+ * list lies at x_off[i] .. x_off[i+1].  want_profile also returns the values above per position behind prof_off (nucl is
+ * '-' where nothing set it).  Bytes below 128, case kept.
+ * The context lends its device and stream: no reads and no index are needed.  Sub-batches of whole contigs of at most
+ * FG_DIVERGENCE_BATCH_COLS (environment, default 2^27) columns plus positions times the number of distinct query bytes of
+ * the call and, as a switch for tests, FG_DIVERGENCE_BATCH_CONTIGS contigs; the result depends on neither.  FG_ERR_NOMEM:
+ * a contig that alone exceeds the budget.  FG_ERR_ARG, found before any device work: NULL out or a NULL array where
+ * something must be read; an offset array that decreases; a byte >= 128; contig_len < 0; trg_start outside
+ * [0, contig_len); more non-gap target columns than contig_len; a threshold that is NaN or negative.  After an error *out
+ * is all zero.  n_contigs = 0 gives an empty batch (every offset array = {0}). */
+struct fg_divergence_batch {
+	uint32_t  n_contigs;
+	uint32_t  pad_;
+	uint64_t* total_off;          /* n_contigs + 1, likewise sub_off, del_off, ins_off */
+	int32_t*  total_pos;          /* positions with any flag */
+	uint64_t* sub_off;
+	int32_t*  sub_pos;
+	uint64_t* del_off;
+	int32_t*  del_pos;
+	uint64_t* ins_off;
+	int32_t*  ins_pos;
+	uint64_t* prof_off;           /* want_profile: n_contigs + 1, into the arrays below */
+	int32_t*  cov;
+	uint8_t*  nucl;
+	int32_t*  mat_ct;
+	uint8_t*  sub_base;           /* 0: none */
+	int32_t*  sub_ct;
+	int32_t*  del_ct;
+	uint8_t*  ins_base;           /* 0: none */
+	int32_t*  ins_ct;
+	uint8_t*  flags;              /* 1 sub | 2 del | 4 ins */
+	void*     owner_;
+};
+int  fg_divergence_profile(fg_ctx* ctx, double sub_thresh, double del_thresh, double ins_thresh, uint32_t n_contigs,
+                           const int32_t* contig_len, const uint64_t* contig_aln_off, const int32_t* trg_start,
+                           const uint64_t* col_off, const uint8_t* trg_cols, const uint8_t* qry_cols, uint8_t want_profile,
+                           struct fg_divergence_batch* out);
+void fg_release_divergence(struct fg_divergence_batch* b);
+
 #ifdef __cplusplus
 }
 #endif
