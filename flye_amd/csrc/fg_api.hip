@@ -587,6 +587,38 @@ int fg_debug_tie_free(fg_ctx* c, uint32_t* out, uint32_t max_n, uint32_t* first_
 	});
 }
 
+int fg_debug_sort_screen(fg_ctx* c, const uint32_t* keys, const uint64_t* seg_off, uint32_t n_seg, int cur_bits, int rec_bits,
+						 const uint32_t* tie_free, float min_unique, int32_t min_overlap, uint32_t* out_reason)
+{
+	if (!c || !seg_off || (n_seg && (!tie_free || !out_reason)) || (seg_off[n_seg] && !keys) || cur_bits < 0 || rec_bits < 0 ||
+		cur_bits + rec_bits > 32)
+		return FG_ERR_ARG;
+	for (uint32_t i = 0; i < n_seg; ++i)
+		if (seg_off[i] > seg_off[i + 1]) return FG_ERR_ARG;
+	return guarded(c, [&]()
+	{
+		HIP_CHECK(hipSetDevice(c->device));
+		fgDebugSortScreen(c, keys, seg_off, n_seg, cur_bits, rec_bits, tie_free, min_unique, min_overlap, out_reason);
+	});
+}
+
+int fg_debug_order_free(fg_ctx* c, uint32_t* out_reason, uint32_t max_n, uint32_t* first_query, uint32_t* n)
+{
+	if (!c || !first_query || !n || (max_n && !out_reason)) return FG_ERR_ARG;
+	return guarded(c, [&]()
+	{
+		HIP_CHECK(hipSetDevice(c->device));
+		fgDebugOrderFree(c, out_reason, max_n, first_query, n);
+	});
+}
+
+int fg_debug_sort_radix_segments(fg_ctx* c, uint32_t* segments)
+{
+	if (!c || !segments) return FG_ERR_ARG;
+	*segments = c->sortRadixSegs;
+	return FG_OK;
+}
+
 int fg_debug_freq_accumulate(fg_ctx* c, uint32_t* dst, const uint32_t* src, uint64_t n)
 {
 	if (!c || (n && (!dst || !src)) || ((uintptr_t)dst & 3u) || ((uintptr_t)src & 3u)) return FG_ERR_ARG;

@@ -1143,10 +1143,7 @@ void fgChainStage(fg_ctx* c, const fg_detector_params* p, uint8_t forceLocal, u6
 	ChainParams cp;
 	cp.k = c->k; cp.maxJump = p->max_jump; cp.minOverlap = p->min_overlap; cp.maxOverhang = p->max_overhang;
 	cp.checkOverhang = p->max_overhang > 0; cp.forceLocal = forceLocal ? 1 : 0;
-	{
-		const float minKmerSruvivalRate = 0.01;	// overlap.cpp:110
-		cp.minUnique = minKmerSruvivalRate * p->min_overlap;
-	}
+	cp.minUnique = fgChainMinUnique(p);
 	cp.firstId = c->firstId;
 	cp.qFirstId = c->hasQ ? c->qFirstId : c->firstId;
 	cp.onlyMaxExt = p->only_max_ext ? 1 : 0;

@@ -398,6 +398,11 @@ struct fg_ctx {
 	DevBuf<u32> dSortCnt;		// task counts of the sort's level loop, a row per level (fg_overlap.hip)
 	DevBuf<u32> dTieFree;		// per query, written by k_fill: 1 = no two of its hits share (extId, curPos)
 	u32 tieFreeQ0 = 0, tieFreeN = 0;	// the queries of the call dTieFree speaks of (0: the last sub-range had no flags)
+	// per query, written by k_sort_screen: dSortFree = dTieFree | "every tied key lies in a group the chaining prefilter
+	// drops" (what the sort takes the radix path by), dSortReason = its SCREEN_* word (fg_overlap.hip)
+	DevBuf<u32> dSortFree, dSortReason;
+	u32 sortReasonN = 0;				// tieFreeN where the last sub-range was screened, else 0 (fg_debug_order_free)
+	u32 sortRadixSegs = 0;				// segments the last hit sort of this context sent to k_sort_radix
 	DevBuf<int> dEditScratch;
 	DevBuf<u32> dEditList;		// pairs queued for the bit-vector kernel (two lists)
 	DevBuf<char> dEditCnt;
@@ -736,6 +741,13 @@ void fgImportIndex(fg_ctx* c, u64 nKeys, const u64* keys, const u64* keyOff, u64
 				   const u64* repKeys, float sampleRate, int onDevice);
 // keyMode: 0 = 32-bit keys, 1 = packed 64-bit records (PK), 2 = 64-bit keys + values
 u32 fgChainSmallMax();
+// the distinct query positions a group needs, minKmerSruvivalRate * _minOverlap as the reference's float (overlap.cpp:110,
+// :235): the chaining prefilter's bound, and what the hit sort's screen (k_sort_screen) decides by ahead of it
+inline float fgChainMinUnique(const fg_detector_params* p)
+{
+	const float minKmerSruvivalRate = 0.01;
+	return minKmerSruvivalRate * p->min_overlap;
+}
 void fgChainStage(fg_ctx* c, const fg_detector_params* p, uint8_t forceLocal, u64 nGroups, u64 nHits, int keyMode,
 				  int curBits);
 void fgEditDistances(fg_ctx* c, PrimRec* dPrims, u64 nPrim, int useHpc);
@@ -797,6 +809,9 @@ void fgDebugSortPairs(fg_ctx* c, u64* keys, u32* vals, const u64* segOff, u32 nS
 void fgDebugSortPairs32(fg_ctx* c, u32* keys, u32* vals, const u64* segOff, u32 nSeg, int curBits, int recBits,
 						const u32* tieFree, u64* radixSegments, u64* radixHits);
 void fgDebugTieFree(fg_ctx* c, u32* out, u32 maxN, u32* firstQuery, u32* n);
+void fgDebugSortScreen(fg_ctx* c, const u32* keys, const u64* segOff, u32 nSeg, int curBits, int recBits, const u32* tieFree,
+					   float minUnique, i32 minOverlap, u32* outReason);
+void fgDebugOrderFree(fg_ctx* c, u32* out, u32 maxN, u32* firstQuery, u32* n);
 void fgDebugProbeSkipCheck(fg_ctx* c, u64* clearBits, u64* violations);
 #define FG_LAZY_STRIPES 64
 void fgDebugChainLazy(fg_ctx* c, u64 out[6]);

@@ -542,6 +542,9 @@ __global__ void k_recv_place(const u64* __restrict__ vals, u64 n, const fg_seed_
 #define SORT_LEVEL_WAVES 1	// tasks per block of k_sort_level
 #endif
 struct SortTask { u64 start; u32 n; u32 depth; };
+// the segment sizes k_sort_radix takes (k_sort_init lists them, k_sort_screen looks at no other): above the LDS piece,
+// up to FG_SORT_RADIX_MAX
+__device__ __forceinline__ bool sort_radix_size(u64 n, u32 radixMax) { return n > SORT_CAP && n <= radixMax; }
 
 // the value array that goes with a key type: a real u32 array, or nothing for packed records
 template <class KT> struct ValPtr {
@@ -627,7 +630,7 @@ __global__ void k_sort_init(const u64* __restrict__ hitOff, u32 nq, SortLists L,
 	// A segment without tied keys has one sorted order, so it needs no introsort trajectory: k_sort_radix takes it
 	// (count in word [3] of row 0).  Pieces that fit k_sort_lds stay there, and a segment beyond radixMax stays in
 	// the level loop, where it spreads over many waves.
-	const bool isRadix = tieFree && q < nq && t.n > SORT_CAP && t.n <= radixMax && tieFree[q] != 0;
+	const bool isRadix = tieFree && q < nq && sort_radix_size(t.n, radixMax) && tieFree[q] != 0;
 	if (tieFree)		// uniform
 	{
 		const u64 mR = __ballot(isRadix);
@@ -646,6 +649,118 @@ __global__ void k_sort_init(const u64* __restrict__ hitOff, u32 nq, SortLists L,
 	}
 	const u32 wideMin = sort_level_mode(L, nq, levelCnt, blockIdx.x == 0 && threadIdx.x == 0);
 	sort_route(t, q < nq && !isRadix, L, wideMin, big, wide, levelCnt, smallCnt);
+}
+
+// The trajectory of std::sort fixes the order of tied keys, and that order is read only in a target group that reaches
+// the DP: a group the chaining prefilter drops (k_group_list, k_group_prep, k_chain_small: fewer than minUnique distinct
+// query positions, or a query span below minOverlap) returns there before any store.  Both tests are set properties of
+// the group, so they can be made on the hits in emission order, ahead of the sort.  One workgroup per query with tied
+// keys and a size k_sort_radix takes, two sweeps over its keys (record << curBits | curPos, ascending curPos; equal keys
+// are neighbours: the property k_fill's flag rests on):
+//   1. the record of every hit that equals the hit before it goes into a keyed open-addressing set in LDS (SCREEN_SLOTS
+//      slots for at most SCREEN_CAP records; more: the query keeps the emulation);
+//   2. every hit whose record is in the set -- the group's hits in front of its first tie included, which is why one
+//      sweep cannot do it -- adds to the slot's distinct positions and widens its [minCur, maxCur].
+// The query is order-free when no slot passes both tests: every group that holds a tie is dropped, whatever stable or
+// unstable sort orders it.  uniq counts a first position 0 that the reference's count (prevPos starts at 0) does not, and
+// the target-span and overhang tests are left out (they would cost the values): the screen errs towards the emulation
+// only.  sortFree[q] = tieFree[q] | order-free; reason[q]: SCREEN_* below.
+// The set is reached through its named arrays only: DS atomics, ordered with the wave's other DS accesses (§4.3).
+#define SCREEN_SLOTS 512
+#define SCREEN_CAP 256
+#define SCREEN_EMPTY 0xFFFFFFFFu	// no record: curBits >= 1 on this path
+#define SCREEN_ITEMS 4
+#define SCREEN_TILE (WG * SCREEN_ITEMS)
+enum { SCREEN_NONE = 0 /* tie-free, or a size outside the radix path */, SCREEN_FREE = 1, SCREEN_SURVIVOR = 2 /* a tied group may reach the DP */,
+	   SCREEN_FULL = 3 /* more than SCREEN_CAP tied records */ };
+__device__ __forceinline__ u32 screen_hash(u32 rec) { return (rec * 0x9E3779B1u) >> 23; }	// 9 bits: SCREEN_SLOTS
+__global__ void __launch_bounds__(WG)
+k_sort_screen(const u64* __restrict__ hitOff, const u32* __restrict__ hitKey, int curBits, const u32* __restrict__ tieFree,
+			  u32 radixMax, float minUnique, i32 minOverlap, u32* __restrict__ sortFree, u32* __restrict__ reason)
+{
+	static_assert(SCREEN_SLOTS == 2 * WG && SCREEN_SLOTS == 512, "two slots per thread; screen_hash gives 9 bits");
+	__shared__ u32 sRec[SCREEN_SLOTS], sUniq[SCREEN_SLOTS], sMin[SCREEN_SLOTS], sMax[SCREEN_SLOTS];
+	__shared__ u32 sCount;
+	const u32 q = blockIdx.x;
+	const u64 start = hitOff[q];
+	const u64 n64 = hitOff[q + 1] - start;
+	const u32 tf = tieFree[q];
+	if (tf != 0 || !sort_radix_size(n64, radixMax))		// uniform
+	{
+		if (threadIdx.x == 0) { sortFree[q] = tf; reason[q] = SCREEN_NONE; }
+		return;
+	}
+	const u32 n = (u32)n64;
+	const u32* const key = hitKey + start;
+	const int lane = threadIdx.x & 63;
+	for (int s = threadIdx.x; s < SCREEN_SLOTS; s += WG) { sRec[s] = SCREEN_EMPTY; sUniq[s] = 0; sMin[s] = 0xFFFFFFFFu; sMax[s] = 0; }
+	if (threadIdx.x == 0) sCount = 0;
+	__syncthreads();
+	// One walk over the keys, SCREEN_ITEMS steps of the block's stride per thread with their loads in flight together (a
+	// step is one dependent round trip: at one hit per thread the kernel waited on 2 x n / WG of them).  Hit j is held
+	// against hit j - 1, which the lane below has (a DPP wave_shr:1 move; lane 0 keeps what it loaded itself).
+	auto sweep = [&](auto&& hit)
+	{
+		for (u32 j0 = 0; j0 < n; j0 += SCREEN_TILE)
+		{
+			u32 k[SCREEN_ITEMS], front[SCREEN_ITEMS];
+#pragma unroll
+			for (int i = 0; i < SCREEN_ITEMS; ++i)
+			{
+				const u32 j = j0 + (u32)i * WG + threadIdx.x;
+				k[i] = j < n ? key[j] : 0u;
+				front[i] = (lane == 0 && j > 0 && j < n) ? key[j - 1] : 0u;
+			}
+#pragma unroll
+			for (int i = 0; i < SCREEN_ITEMS; ++i)
+			{
+				const u32 j = j0 + (u32)i * WG + threadIdx.x;
+				const u32 below = (u32)__builtin_amdgcn_update_dpp((int)front[i], (int)k[i], 0x138, 0xf, 0xf, false);
+				if (j < n) hit(k[i], j > 0 && below == k[i]);
+			}
+		}
+	};
+	sweep([&](u32 k, bool tie)
+	{
+		if (!tie) return;
+		const u32 rec = k >> curBits;
+		u32 h = screen_hash(rec);
+		// a full set ends the walk: with more than SCREEN_CAP records in it the count says so
+		for (int probe = 0; probe < SCREEN_SLOTS; ++probe, h = (h + 1) & (SCREEN_SLOTS - 1))
+		{
+			const u32 old = atomicCAS(&sRec[h], SCREEN_EMPTY, rec);
+			if (old == SCREEN_EMPTY) atomicAdd(&sCount, 1u);
+			if (old == SCREEN_EMPTY || old == rec || __hip_atomic_load(&sCount, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) > SCREEN_CAP) break;
+		}
+	});
+	__syncthreads();
+	if (sCount > SCREEN_CAP)		// uniform
+	{
+		if (threadIdx.x == 0) { sortFree[q] = 0; reason[q] = SCREEN_FULL; }
+		return;
+	}
+	const u32 curMask = (1u << curBits) - 1u;
+	sweep([&](u32 k, bool tie)
+	{
+		const u32 rec = k >> curBits, cur = k & curMask;
+		// at most SCREEN_CAP of the slots are taken: the walk ends at an empty one
+		for (u32 h = screen_hash(rec);; h = (h + 1) & (SCREEN_SLOTS - 1))
+		{
+			const u32 r = sRec[h];
+			if (r == SCREEN_EMPTY) break;
+			if (r != rec) continue;
+			if (!tie) atomicAdd(&sUniq[h], 1u);
+			atomicMin(&sMin[h], cur);
+			atomicMax(&sMax[h], cur);
+			break;
+		}
+	});
+	__syncthreads();
+	int survivor = 0;
+	for (int s = threadIdx.x; s < SCREEN_SLOTS; s += WG)
+		survivor |= sRec[s] != SCREEN_EMPTY && (float)sUniq[s] >= minUnique && (i32)(sMax[s] - sMin[s]) >= minOverlap;
+	const int any = __syncthreads_or(survivor);
+	if (threadIdx.x == 0) { sortFree[q] = any ? 0u : 1u; reason[q] = any ? SCREEN_SURVIVOR : SCREEN_FREE; }
 }
 
 // Stable least-significant-digit radix sort of one tie-free segment per workgroup, on the record bits of the key only:
@@ -1215,9 +1330,35 @@ struct SortRadixStats { u64 segments, hits; };
 
 // std::sort order of each segment [segOff[i], segOff[i+1]) of device arrays K, V.
 // dTieFree (32-bit keys record << curBits | curPos of recBits record bits, each segment emitted by ascending curPos;
-// null: none): segments flagged there hold no two equal keys; those of SORT_CAP < n <= FG_SORT_RADIX_MAX (65 536) hits
-// are sorted by k_sort_radix instead of the introsort emulation.  FG_SORT_TIEFREE=0 ignores the flags.
+// null: none): segments flagged there hold no two equal keys whose order anybody reads -- none at all (k_fill's flag), or
+// only inside target groups the chaining stage drops (k_sort_screen's verdict, OR-ed in); those of SORT_CAP < n <=
+// FG_SORT_RADIX_MAX (65 536) hits are sorted by k_sort_radix instead of the introsort emulation.  FG_SORT_TIEFREE=0
+// ignores the flags.
 #define SORT_MAX_LEVELS 128		// rows of level counts (the depth budget of 2 log2 n bounds the levels: n < 2^31)
+// whether per-segment flags send segments to k_sort_radix at all: 32-bit keys whose record bits its passes cover, and
+// FG_SORT_TIEFREE not 0
+template <class KT>
+static bool sortRadixUsable(int recBits)
+{
+	const char* e = getenv("FG_SORT_TIEFREE");
+	return std::is_same<KT, u32>::value && recBits > 0 && recBits <= 8 * SORT_RADIX_MAX_PASSES && !(e && atoi(e) == 0);
+}
+static u32 sortRadixMax() { return getenv("FG_SORT_RADIX_MAX") ? (u32)atoi(getenv("FG_SORT_RADIX_MAX")) : 65536u; }
+
+// k_sort_screen over the segments of a 32-bit key array: dSortFree (what sortSegments takes in place of dTieFree) and
+// dReason, a word per segment each.  False, with nothing launched or written: the flags would not be used
+// (sortRadixUsable), FG_SORT_SCREEN=0, or a record that could be SCREEN_EMPTY.
+static bool sortScreen(fg_ctx* c, const u64* dSegOff, u32 nSeg, const u32* dK, int curBits, int recBits, const u32* dTieFree,
+					   float minUnique, i32 minOverlap, u32* dSortFree, u32* dReason)
+{
+	const char* e = getenv("FG_SORT_SCREEN");
+	if (!nSeg || !dTieFree || !sortRadixUsable<u32>(recBits) || curBits < 1 || (e && atoi(e) == 0)) return false;
+	ScopedK t(c->timer, "k_sort_screen");
+	hipLaunchKernelGGL(k_sort_screen, nSeg, WG, 0, c->stream, dSegOff, dK, curBits, dTieFree, sortRadixMax(), minUnique, minOverlap,
+					   dSortFree, dReason);
+	return true;
+}
+
 template <class KT>
 static void sortSegments(fg_ctx* c, const u64* dSegOff, u32 nSeg, KT* dK, u32* dV, u64 nHits, int curBits = 0,
 						 const u32* dTieFree = nullptr, int recBits = 0, SortRadixStats* stats = nullptr)
@@ -1239,11 +1380,8 @@ static void sortSegments(fg_ctx* c, const u64* dSegOff, u32 nSeg, KT* dK, u32* d
 	SortTask* wideB = wideA + bigCap;
 	SortTask* radixT = wideB + bigCap;		// bigCap > nSeg
 	if (stats) *stats = SortRadixStats{0, 0};
-	{
-		const char* e = getenv("FG_SORT_TIEFREE");
-		if (!std::is_same<KT, u32>::value || recBits <= 0 || recBits > 8 * SORT_RADIX_MAX_PASSES || (e && atoi(e) == 0)) dTieFree = nullptr;
-	}
-	const u32 radixMax = getenv("FG_SORT_RADIX_MAX") ? (u32)atoi(getenv("FG_SORT_RADIX_MAX")) : 65536u;
+	if (!sortRadixUsable<KT>(recBits)) dTieFree = nullptr;
+	const u32 radixMax = sortRadixMax();
 	u32* levelCnt = c->dSortCnt.p;							// row l at levelCnt + 4 l
 	u32* smallCnt = c->dSortCnt.p + 4 * (SORT_MAX_LEVELS + 2);
 	const u32 streamMax = getenv("FG_SORT_STREAM_MAX") ? (u32)atoi(getenv("FG_SORT_STREAM_MAX")) : 8192u;
@@ -1275,6 +1413,7 @@ static void sortSegments(fg_ctx* c, const u64* dSegOff, u32 nSeg, KT* dK, u32* d
 		if (lvl == 0) nRadix = row[3];
 	};
 	fetchCounts(0);
+	c->sortRadixSegs = nRadix;
 	if constexpr (std::is_same<KT, u32>::value)
 		if (nRadix)
 		{
@@ -1450,6 +1589,36 @@ void fgDebugTieFree(fg_ctx* c, u32* out, u32 maxN, u32* firstQuery, u32* n)
 	const u32 m = std::min(maxN, c->tieFreeN);
 	if (!m) return;
 	HIP_CHECK(hipMemcpyAsync(out, c->dTieFree.p, m * 4ULL, hipMemcpyDeviceToHost, c->stream));
+	HIP_CHECK(hipStreamSynchronize(c->stream));
+}
+
+// fg_debug_sort_screen: k_sort_screen on the caller's segments; reason words all SCREEN_NONE where the screen is switched
+// off or the key form has none
+void fgDebugSortScreen(fg_ctx* c, const u32* keys, const u64* segOff, u32 nSeg, int curBits, int recBits, const u32* tieFree,
+					   float minUnique, i32 minOverlap, u32* outReason)
+{
+	hipStream_t s = c->stream;
+	const u64 n = segOff[nSeg];
+	for (u32 i = 0; i < nSeg; ++i) outReason[i] = SCREEN_NONE;
+	if (!nSeg) return;
+	DevBuf<u32> dK, dFlag, dFree, dReason; DevBuf<u64> dOff;
+	dK.alloc(n + 1); dOff.alloc(nSeg + 1); dFlag.alloc(nSeg + 1); dFree.alloc(nSeg + 1); dReason.alloc(nSeg + 1);
+	HIP_CHECK(hipMemcpyAsync(dK.p, keys, n * 4, hipMemcpyHostToDevice, s));
+	HIP_CHECK(hipMemcpyAsync(dOff.p, segOff, (nSeg + 1) * 8ULL, hipMemcpyHostToDevice, s));
+	HIP_CHECK(hipMemcpyAsync(dFlag.p, tieFree, nSeg * 4ULL, hipMemcpyHostToDevice, s));
+	if (sortScreen(c, dOff.p, nSeg, dK.p, curBits, recBits, dFlag.p, minUnique, minOverlap, dFree.p, dReason.p))
+		HIP_CHECK(hipMemcpyAsync(outReason, dReason.p, nSeg * 4ULL, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(hipStreamSynchronize(s));
+}
+
+// fg_debug_order_free: k_sort_screen's reason words of the last sub-range this context expanded (fg_debug_tie_free's
+// queries; none where the screen did not run)
+void fgDebugOrderFree(fg_ctx* c, u32* out, u32 maxN, u32* firstQuery, u32* n)
+{
+	*firstQuery = c->tieFreeQ0; *n = c->sortReasonN;
+	const u32 m = std::min(maxN, c->sortReasonN);
+	if (!m) return;
+	HIP_CHECK(hipMemcpyAsync(out, c->dSortReason.p, m * 4ULL, hipMemcpyDeviceToHost, c->stream));
 	HIP_CHECK(hipStreamSynchronize(c->stream));
 }
 
@@ -1661,7 +1830,7 @@ static void deviceSub(fg_ctx* c, const fg_detector_params* p, uint8_t forceLocal
 	while ((1LL << curBits) < (long long)(c->hasQ ? c->qMaxLen : c->maxLen)) ++curBits;
 	while ((1ULL << recBits) < 2ULL * c->nReads) ++recBits;
 	const bool key32 = curBits + recBits <= 32 && !getenv("FG_FORCE_KEY64");
-	c->tieFreeN = 0;
+	c->tieFreeN = 0; c->sortReasonN = 0;
 	// key mode: 0 = 32-bit keys + values; when (record, curPos) need more than 32 bits: 1 = packed 64-bit
 	// records (PK: record, curPos, extPos in one word, 8 bytes per hit in the sort levels instead of 12;
 	// FG_PACKED_KEYS=0 turns it off), else 2 = 64-bit keys + values
@@ -1677,7 +1846,16 @@ static void deviceSub(fg_ctx* c, const fg_detector_params* p, uint8_t forceLocal
 							 c->dProbe.p, c->dEntries.p, c->dHitOff.p, c->dFiltOff.p, c->dHitKey32.p, c->dHitVal.p, c->dFiltPos.p, c->dTieFree.p); }
 		if (!recv) { c->tieFreeQ0 = callQ0 + sub0; c->tieFreeN = nq; }
 		// the receiver path knows no ties: every query goes through the emulation there
-		sortSegments<u32>(c, c->dHitOff.p, nq, c->dHitKey32.p, c->dHitVal.p, nHits, curBits, recv ? nullptr : c->dTieFree.p, recBits);
+		const u32* sortFree = recv ? nullptr : c->dTieFree.p;
+		if (sortFree && nHits)
+		{
+			// queries whose ties all lie in groups the chaining stage will drop take the radix path too
+			c->dSortFree.reserve(nq + 1); c->dSortReason.reserve(nq + 1);
+			if (sortScreen(c, c->dHitOff.p, nq, c->dHitKey32.p, curBits, recBits, c->dTieFree.p, fgChainMinUnique(p), p->min_overlap,
+						   c->dSortFree.p, c->dSortReason.p))
+				{ sortFree = c->dSortFree.p; c->sortReasonN = nq; }
+		}
+		sortSegments<u32>(c, c->dHitOff.p, nq, c->dHitKey32.p, c->dHitVal.p, nHits, curBits, sortFree, recBits);
 	}
 	else if (keyMode == 1)
 	{

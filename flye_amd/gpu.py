@@ -70,7 +70,8 @@ ABI_SYMBOLS = ["fg_abi_version", "fg_create", "fg_destroy", "fg_strerror", "fg_l
                "fg_group_set_reads", "fg_group_set_queries", "fg_group_build_index_solid",
                "fg_group_build_index_minimizers", "fg_group_clear_index", "fg_group_overlaps", "fg_group_stats",
                "fg_group_build_info", "fg_debug_freq_accumulate", "fg_debug_group_bin_cuts", "fg_debug_scan",
-               "fg_debug_radix_sort_pairs", "fg_debug_tie_free", "fg_debug_chain_lazy"]
+               "fg_debug_radix_sort_pairs", "fg_debug_tie_free", "fg_debug_chain_lazy", "fg_debug_sort_screen",
+               "fg_debug_order_free", "fg_debug_sort_radix_segments"]
 
 # struct fg_range_pair: one pair of fg_align_ranges
 RANGE_PAIR_DTYPE = np.dtype([("cur_id", "<u4"), ("ext_id", "<u4"), ("cur_begin", "<i4"), ("cur_end", "<i4"),
@@ -344,6 +345,10 @@ def load_library():
         L.fg_debug_sort_pairs32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int,
                                             C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.fg_debug_tie_free.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.fg_debug_sort_screen.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_void_p,
+                                           C.c_float, C.c_int32, C.c_void_p]
+        L.fg_debug_order_free.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.fg_debug_sort_radix_segments.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.fg_debug_probe_skip_check.argtypes =[C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.fg_debug_chain_lazy.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         L.fg_debug_edit_distances.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -808,6 +813,39 @@ class Context:
         if n.value > max_n:
             raise ValueError(f"{n.value} flags, room for {max_n}")
         return int(q0.value), out[:n.value].copy()
+
+    def debug_sort_screen(self, keys, seg_off, cur_bits, rec_bits, tie_free, min_unique, min_overlap):
+        """The hit sort's screen (k_sort_screen) on segments of 32-bit keys ``record << cur_bits | cur_pos`` in emission
+        order, with the tie-free flag of each: one reason word per segment (0 not screened, 1 order-free, 2 a tied group
+        may pass the chaining prefilter's ``min_unique`` / ``min_overlap``, 3 too many tied records)."""
+        k = np.ascontiguousarray(keys, np.uint32)
+        off = np.ascontiguousarray(seg_off, np.uint64)
+        flags = np.ascontiguousarray(tie_free, np.uint32)
+        if len(flags) != len(off) - 1:
+            raise ValueError("one tie-free flag per segment")
+        if len(k) != int(off[-1]):
+            raise ValueError("seg_off does not end at the number of keys")
+        out = np.zeros(max(len(off) - 1, 1), np.uint32)
+        self._check(self.L.fg_debug_sort_screen(self.h, k.ctypes.data, off.ctypes.data, len(off) - 1, int(cur_bits),
+                                                int(rec_bits), flags.ctypes.data, float(np.float32(min_unique)),
+                                                int(min_overlap), out.ctypes.data))
+        return out[:len(off) - 1].copy()
+
+    def debug_order_free(self, max_n):
+        """The screen's reason words for the queries ``debug_tie_free`` speaks of: (index of the first query in the
+        call's list, reasons).  Empty where the screen did not run."""
+        out = np.zeros(max(int(max_n), 1), np.uint32)
+        q0, n = C.c_uint32(0), C.c_uint32(0)
+        self._check(self.L.fg_debug_order_free(self.h, out.ctypes.data, int(max_n), C.byref(q0), C.byref(n)))
+        if n.value > max_n:
+            raise ValueError(f"{n.value} reason words, room for {max_n}")
+        return int(q0.value), out[:n.value].copy()
+
+    def debug_sort_radix_segments(self):
+        """Segments the last hit sort on this context sent to the radix path."""
+        n = C.c_uint32(0)
+        self._check(self.L.fg_debug_sort_radix_segments(self.h, C.byref(n)))
+        return int(n.value)
 
     def debug_freq_accumulate(self, dst, src):
         """k_freq_accumulate on the device: ``dst += src`` in place over uint32 (wrapping).  The device copies sit at

@@ -444,6 +444,25 @@ int fg_debug_sort_pairs32(fg_ctx* ctx, uint32_t* keys, uint32_t* vals, const uin
  * (i < min(max_n, *n)) = 1 when no two seed hits of query *first_query + i share (ext_id, cur_pos). */
 int fg_debug_tie_free(fg_ctx* ctx, uint32_t* out, uint32_t max_n, uint32_t* first_query, uint32_t* n);
 
+/* Test hook: the hit sort's screen for queries whose tied keys all lie in target groups the chaining prefilter drops, on
+ * the caller's segments (keys as for fg_debug_sort_pairs32, every segment by ascending cur_pos, equal keys neighbours;
+ * tie_free: n_seg words as k_fill writes them).  min_unique / min_overlap: the prefilter's bounds on a group's distinct
+ * query positions (compared as float) and on its query span.  out_reason[i]: 0 = not screened (flagged tie-free, a size
+ * the radix path does not take, or the screen is off: FG_SORT_SCREEN=0, FG_SORT_TIEFREE=0, cur_bits == 0), 1 = order-
+ * free (no tied group can pass both bounds: any sort gives the same overlaps), 2 = a tied group may pass them, 3 =
+ * more than 256 tied records. */
+int fg_debug_sort_screen(fg_ctx* ctx, const uint32_t* keys, const uint64_t* seg_off, uint32_t n_seg, int cur_bits,
+                         int rec_bits, const uint32_t* tie_free, float min_unique, int32_t min_overlap,
+                         uint32_t* out_reason);
+
+/* Test hook: the screen's reason words for the queries fg_debug_tie_free speaks of (same *first_query; *n = 0 where the
+ * screen did not run). */
+int fg_debug_order_free(fg_ctx* ctx, uint32_t* out_reason, uint32_t max_n, uint32_t* first_query, uint32_t* n);
+
+/* Test hook: the number of segments the last hit sort of this context (the last sub-range of an fg_overlaps call, or a
+ * fg_debug_sort_pairs* call) sent to the radix path. */
+int fg_debug_sort_radix_segments(fg_ctx* ctx, uint32_t* segments);
+
 /* Test hook (host only): the key ranges a group build of `world` members cuts from hist[FG_INDEX_BINS]; member r
  * gets the bins [cuts[r], cuts[r + 1]); cuts has world + 1 entries.  They equal dist.balanced_bin_ranges. */
 int fg_debug_group_bin_cuts(const uint64_t* hist, uint32_t world, uint32_t* cuts);
