@@ -457,6 +457,8 @@ struct fg_ctx {
 	DevBuf<char> dCig[20];
 	// fg_divergence_profile (fg_divergence.hip): the buffers of one sub-batch, handed out in call order
 	DevBuf<char> dDv[28];
+	// fg_confirm_positions / fg_classify_reads (fg_partition.hip): the buffers of one sub-batch, handed out in call order
+	DevBuf<char> dPt[36];
 	PinnedBuf<char> hPrim;
 	PinnedBuf<u64> hOff;
 	PinnedBuf<u64> hScalar;		// staging of the counts the host reads between kernels (pinned: no bounce buffer)

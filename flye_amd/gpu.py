@@ -23,6 +23,9 @@ like calls into the reference:
 * ``DivergenceFinder(ctx).find_divergence(alignment_path, contigs_path, contigs_info, frequency_path, positions_path,
   div_sum_path, sub_thresh, del_thresh, ins_thresh)`` / ``profile``  (flye/trestle/divergence.py:55-232, on
   fg_divergence_profile)
+* ``ReadPartitioner(ctx).partition_reads(edges, it, side, position_path, cons_align_path, template, read_align_path,
+  consensuses, confirmed_pos_path, part_file, headers_to_id)`` / ``confirm`` / ``classify``
+  (flye/trestle/trestle.py:1075-1628, on fg_confirm_positions and fg_classify_reads)
 
 There is no CPU fallback: if the HIP library or a device is missing every entry
 point raises ``FlyeGpuError``.
@@ -64,6 +67,7 @@ ABI_SYMBOLS = ["fg_abi_version", "fg_create", "fg_destroy", "fg_strerror", "fg_l
                "fg_subs_matrix_load", "fg_polish_bubbles", "fg_release_polish", "fg_make_bubbles", "fg_release_bubbles",
                "fg_uniform_alignments", "fg_release_uniform", "fg_contig_consensus", "fg_release_consensus",
                "fg_expand_cigars", "fg_release_expand", "fg_cigar_parse", "fg_divergence_profile", "fg_release_divergence",
+               "fg_confirm_positions", "fg_release_confirm", "fg_classify_reads", "fg_release_classify",
                "fg_index_keep_targets", "fg_index_shard", "fg_probe_hits", "fg_overlaps_from_hits",
                "fg_index_piece_split", "fg_index_scatter_begin", "fg_index_scatter_end", "fg_debug_probe_skip_check",
                "fg_group_create", "fg_group_destroy", "fg_group_size", "fg_group_member", "fg_group_last_error",
@@ -257,6 +261,24 @@ class DivergenceBatch(C.Structure):
                 ("ins_ct", C.POINTER(C.c_int32)), ("flags", C.POINTER(C.c_uint8)), ("owner_", C.c_void_p)]
 
 
+CONFIRM_LISTS = ("conf_total", "conf_sub", "conf_del", "conf_ins", "rej_total", "rej_sub", "rej_del", "rej_ins")
+
+
+class ConfirmBatch(C.Structure):
+    """struct fg_confirm_batch"""
+    _fields_ = [("n_jobs", C.c_uint32), ("pad_", C.c_uint32), ("n_edges", C.c_uint64)] + \
+        [f for k in CONFIRM_LISTS for f in ((k + "_off", C.POINTER(C.c_uint64)), (k + "_pos", C.POINTER(C.c_int32)))] + \
+        [("cons_off", C.POINTER(C.c_uint64)), ("cons_pos", C.POINTER(C.c_int32)), ("owner_", C.c_void_p)]
+
+
+class ClassifyBatch(C.Structure):
+    """struct fg_classify_batch"""
+    _fields_ = [("n_jobs", C.c_uint32), ("pad_", C.c_uint32), ("n_alignments", C.c_uint64), ("read_off", C.POINTER(C.c_uint64)),
+                ("status", C.POINTER(C.c_uint8)), ("top_edge", C.POINTER(C.c_int32)), ("top_score", C.POINTER(C.c_int32)),
+                ("total_score", C.POINTER(C.c_int32)), ("aln_score", C.POINTER(C.c_int32)), ("aln_counted", C.POINTER(C.c_uint8)),
+                ("owner_", C.c_void_p)]
+
+
 class BridgeStats(C.Structure):
     _fields_ = [("device_calls", C.c_uint64), ("reads_computed", C.c_uint64), ("requests", C.c_uint64),
                 ("cache_hits", C.c_uint64), ("cached_overlaps", C.c_uint64), ("reads_ahead", C.c_uint64),
@@ -404,6 +426,12 @@ def load_library():
             [C.c_uint8, C.POINTER(DivergenceBatch)]
         L.fg_release_divergence.argtypes = [C.POINTER(DivergenceBatch)]
         L.fg_release_divergence.restype = None
+        L.fg_confirm_positions.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 16 + [C.POINTER(ConfirmBatch)]
+        L.fg_release_confirm.argtypes = [C.POINTER(ConfirmBatch)]
+        L.fg_release_confirm.restype = None
+        L.fg_classify_reads.argtypes = [C.c_void_p, C.c_int32, C.c_uint32] + [C.c_void_p] * 11 + [C.c_uint8, C.POINTER(ClassifyBatch)]
+        L.fg_release_classify.argtypes = [C.POINTER(ClassifyBatch)]
+        L.fg_release_classify.restype = None
         L.fg_debug_group_bin_cuts.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         L.fg_debug_freq_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
         L.fg_debug_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int]
@@ -690,6 +718,28 @@ class DivergenceResult(BubbleResult):
     def positions(self, i):
         return {k: [int(p) for p in getattr(self, k + "_pos")[int(getattr(self, k + "_off")[i]):int(getattr(self, k + "_off")[i + 1])]]
                 for k in ("total", "sub", "del", "ins")}
+
+
+class ConfirmResult(BubbleResult):
+    """fg_confirm_batch copied out of its arena, arrays under the names of the header.  positions(j) gives job j's
+    (confirmed, rejected) as the reference's dictionaries, consensus_pos(i) the list of edge i of the call."""
+
+    def positions(self, j):
+        part = lambda k: [int(p) for p in getattr(self, k + "_pos")[int(getattr(self, k + "_off")[j]):int(getattr(self, k + "_off")[j + 1])]]
+        return tuple({k: part(pre + k) for k in ("total", "sub", "ins", "del")} for pre in ("conf_", "rej_"))
+
+    def consensus_pos(self, i):
+        return [int(p) for p in self.cons_pos[int(self.cons_off[i]):int(self.cons_off[i + 1])]]
+
+
+class ClassifyResult(BubbleResult):
+    """fg_classify_batch copied out of its arena, arrays under the names of the header (aln_score / aln_counted None
+    without want_scores).  reads(j) gives job j's (status, top_edge, top_score, total_score) per read number."""
+
+    def reads(self, j):
+        lo, hi = int(self.read_off[j]), int(self.read_off[j + 1])
+        return list(zip(self.status[lo:hi].tolist(), self.top_edge[lo:hi].tolist(), self.top_score[lo:hi].tolist(),
+                        self.total_score[lo:hi].tolist()))
 
 
 def cigar_parse(cigar):
@@ -1269,6 +1319,66 @@ class Context:
                 out[k] = take(getattr(b, k), npos, t)
         self.L.fg_release_divergence(C.byref(b))
         return DivergenceResult(**out)
+
+    def confirm_positions(self, side, job_edge_off, trg_start, trg_end, qry_start, col_off, trg_cols, qry_cols, total_off, total_pos,
+                          sub_off, sub_pos, del_off, del_pos, ins_off, ins_pos):
+        """fg_confirm_positions: _evaluate_positions of the reference's flye/trestle/trestle.py for a batch of jobs, one
+        collapsed consensus alignment per edge.  Returns a ConfirmResult."""
+        sd = np.ascontiguousarray(side, np.uint8)
+        n = len(sd)
+        jeo, co = np.ascontiguousarray(job_edge_off, np.uint64), np.ascontiguousarray(col_off, np.uint64)
+        ts, te, qs = (np.ascontiguousarray(a, np.int32) for a in (trg_start, trg_end, qry_start))
+        tc, qc = np.frombuffer(bytes(trg_cols), np.uint8), np.frombuffer(bytes(qry_cols), np.uint8)
+        offs = [np.ascontiguousarray(a, np.uint64) for a in (total_off, sub_off, del_off, ins_off)]
+        poss = [np.ascontiguousarray(a, np.int32) for a in (total_pos, sub_pos, del_pos, ins_pos)]
+        if len(jeo) != n + 1 or len(tc) != len(qc) or not len(ts) == len(te) == len(qs) or int(jeo.max()) > len(ts) or \
+                len(co) != len(ts) + 1 or int(co.max()) > len(tc) or any(len(o) != n + 1 or int(o.max()) > len(p) for o, p in zip(offs, poss)):
+            raise ValueError("confirm_positions: offsets outside their arrays")
+        ptr = lambda a: a.ctypes.data if a is not None and len(a) else None
+        b = ConfirmBatch()
+        t0 = time.perf_counter()
+        self._check(self.L.fg_confirm_positions(self.h, n, ptr(sd), jeo.ctypes.data, ptr(ts), ptr(te), ptr(qs), co.ctypes.data, ptr(tc),
+                                                ptr(qc), *[x for o, p in zip(offs, poss) for x in (o.ctypes.data, ptr(p))], C.byref(b)))
+        self.last_confirm_seconds = time.perf_counter() - t0
+        take = lambda p, k, dtype: np.ctypeslib.as_array(p, (k,)).copy() if k else np.zeros(0, dtype)
+        out = {}
+        for k in CONFIRM_LISTS + ("cons",):
+            out[k + "_off"] = take(getattr(b, k + "_off"), (int(b.n_edges) if k == "cons" else n) + 1, np.uint64)
+            out[k + "_pos"] = take(getattr(b, k + "_pos"), int(out[k + "_off"][-1]), np.int32)
+        self.L.fg_release_confirm(C.byref(b))
+        return ConfirmResult(**out)
+
+    def classify_reads(self, buffer_count, job_edge_off, job_n_reads, edge_pos_off, edge_pos, edge_aln_off, read, trg_start, trg_end,
+                       col_off, trg_cols, qry_cols, want_scores=False):
+        """fg_classify_reads: _classify_reads with _index_mapping of the reference's flye/trestle/trestle.py for a batch of
+        jobs.  Returns a ClassifyResult."""
+        jnr = np.ascontiguousarray(job_n_reads, np.uint32)
+        n = len(jnr)
+        jeo, epo, eao, co = (np.ascontiguousarray(a, np.uint64) for a in (job_edge_off, edge_pos_off, edge_aln_off, col_off))
+        ep, rd = np.ascontiguousarray(edge_pos, np.int32), np.ascontiguousarray(read, np.uint32)
+        ts, te = np.ascontiguousarray(trg_start, np.int32), np.ascontiguousarray(trg_end, np.int32)
+        tc, qc = np.frombuffer(bytes(trg_cols), np.uint8), np.frombuffer(bytes(qry_cols), np.uint8)
+        if len(jeo) != n + 1 or len(tc) != len(qc) or not len(ts) == len(te) == len(rd) or len(epo) != len(eao) or \
+                int(jeo.max()) + 1 > len(epo) or int(epo.max()) > len(ep) or int(eao.max()) > len(ts) or len(co) != len(ts) + 1 or \
+                int(co.max()) > len(tc):
+            raise ValueError("classify_reads: offsets outside their arrays")
+        ptr = lambda a: a.ctypes.data if a is not None and len(a) else None
+        b = ClassifyBatch()
+        t0 = time.perf_counter()
+        self._check(self.L.fg_classify_reads(self.h, int(buffer_count), n, jeo.ctypes.data, ptr(jnr), epo.ctypes.data, ptr(ep),
+                                             eao.ctypes.data, ptr(rd), ptr(ts), ptr(te), co.ctypes.data, ptr(tc), ptr(qc),
+                                             int(bool(want_scores)), C.byref(b)))
+        self.last_classify_seconds = time.perf_counter() - t0
+        take = lambda p, k, dtype: np.ctypeslib.as_array(p, (k,)).copy() if k else np.zeros(0, dtype)
+        out = dict(read_off=take(b.read_off, n + 1, np.uint64), aln_score=None, aln_counted=None)
+        nr = int(out["read_off"][n])
+        for k, t in (("status", np.uint8), ("top_edge", np.int32), ("top_score", np.int32), ("total_score", np.int32)):
+            out[k] = take(getattr(b, k), nr, t)
+        if want_scores:
+            out["aln_score"] = take(b.aln_score, int(b.n_alignments), np.int32)
+            out["aln_counted"] = take(b.aln_counted, int(b.n_alignments), np.uint8)
+        self.L.fg_release_classify(C.byref(b))
+        return ClassifyResult(**out)
 
     def expand_cigars(self, contig_off, contig_seq, aln_contig, ctg_pos, run_off, run_op, run_len, read_off, read_seq,
                       want_cols=True):
@@ -2415,6 +2525,223 @@ class DivergenceFinder:
                 with open(path, "w") as f:
                     f.write(text)
         return sum(self.aln_errors) / (len(self.aln_errors) + 1)
+
+
+class ReadPartitioner:
+    """Mirror of the reference's partition_reads (flye/trestle/trestle.py:1075-1142) on fg_confirm_positions and
+    fg_classify_reads: the SAM files go through SamAlignments (first chunk only, as the reference takes [0]), the
+    consensus alignments are collapsed on the host, and the two text files are written with the reference's format
+    strings.  Both skip paths are the reference's: a missing file or an empty alignment gives empty lists at it <= 1 and
+    the confirmed file of it - 1 later, and the partitioning of it - 1 is written again.  confirm and classify take
+    several jobs in ONE device call each."""
+
+    MAX_SUPP_ALIGN_OVERLAP = 100
+    KEYS = ("total", "sub", "del", "ins")
+    STATUS = ("None", "Tied", "Partitioned")
+
+    def __init__(self, ctx: Context, max_read_coverage=1000, buffer_count=3):
+        self.ctx = ctx
+        self.max_read_coverage, self.buffer_count = max_read_coverage, buffer_count
+
+    # ---- the text files --------------------------------------------------------------------------------------------
+    @classmethod
+    def read_positions(cls, path):
+        """divergence.py:362-396: lines 1, 3, 5, 7 are the total, sub, del and ins lists"""
+        pos = {k: [] for k in cls.KEYS}
+        try:
+            with open(path, "r") as f:
+                for i, line in enumerate(f):
+                    line = line.strip()
+                    if i < 8 and i % 2 == 1 and line:
+                        pos[cls.KEYS[i // 2]] = [int(x) for x in line.split(",")]
+                    elif line and not (i < 8 and i % 2 == 0 and line.startswith(">")):
+                        raise ValueError("Not a valid positions file")
+        except IOError as e:
+            raise ValueError(str(e))
+        return pos
+
+    @classmethod
+    def _write_confirmed_positions(cls, confirmed, rejected, pos, out_file):
+        with open(out_file, "w") as f:
+            for label, lists in (("Confirmed", confirmed), ("Rejected", rejected), ("Tentative", pos)):
+                for k in cls.KEYS:
+                    f.write(">{0}_{1}_positions_{2}\n".format(label, k, len(lists[k])))
+                    f.write(",".join([str(x) for x in sorted(lists[k])]) + "\n")
+
+    @classmethod
+    def _read_confirmed_positions(cls, confirmed_file):
+        out = [{k: [] for k in cls.KEYS} for _ in range(3)]
+        with open(confirmed_file, "r") as f:
+            for i, line in enumerate(f):
+                line = line.strip()
+                if i % 2 == 1 and i < 24 and line:
+                    out[i // 8][cls.KEYS[i % 8 // 2]] = [int(x) for x in line.split(",")]
+        return tuple(out)
+
+    @staticmethod
+    def _write_partitioning_file(part_list, part_path):
+        with open(part_path, "w") as f:
+            rows = [["Read_ID", "Status", "Edge", "Top Score", "Total Score", "Header"]] + sorted(part_list)
+            for row in rows:
+                f.write("\t".join(["{:11}".format(h) for h in row]) + "\n")
+
+    @staticmethod
+    def _read_partitioning_file(partitioning_file):
+        part_list = []
+        with open(partitioning_file, "r") as f:
+            for i, line in enumerate(f):
+                if i > 0:
+                    tokens = [t.strip() for t in line.strip().split("\t")]
+                    for k in (0, 3, 4):
+                        tokens[k] = int(tokens[k])
+                    part_list.append(tuple(tokens))
+        return part_list
+
+    # ---- collapsing the consensus alignments (:1160-1331) ----------------------------------------------------------
+    @staticmethod
+    def _axis_overlap(s1, e1, s2, e2):
+        lens = []
+        if s2 <= s1 < e2:
+            lens.append(e2 - s1 if e1 >= e2 else e1 - s1)
+        if s2 < e1 <= e2:
+            lens.append(e1 - s2 if s1 <= s2 else e1 - s1)
+        if s1 <= s2 < e1:
+            lens.append(e1 - s2 if e2 >= e1 else e2 - s2)
+        if s1 < e2 <= e1:
+            lens.append(e2 - s1 if s2 <= s1 else e2 - s2)
+        return min(lens) if lens else 0
+
+    @classmethod
+    def _overlap(cls, one, two):
+        return max(cls._axis_overlap(one.qry_start, one.qry_end, two.qry_start, two.qry_end),
+                   cls._axis_overlap(one.trg_start, one.trg_end, two.trg_start, two.trg_end))
+
+    @staticmethod
+    def _merge_alns(first_start, first_end, first_seq, second_start, second_end, second_seq):
+        if first_end <= second_start:
+            return first_seq + "N" * (second_start - first_end), second_seq, second_end
+        if first_end >= second_end:
+            return first_seq, "", first_end
+        # the second string from behind its first (first_end - second_start) bases on
+        bases, cut = 0, len(second_seq)
+        for i, b in enumerate(second_seq):
+            bases += b != "-"
+            if bases == first_end - second_start:
+                cut = i + 1
+                break
+        return first_seq, second_seq[cut:], second_end
+
+    @classmethod
+    def _collapse(cls, one, two):
+        if one.qry_sign == "-" or two.qry_sign == "-" or cls._overlap(one, two) > cls.MAX_SUPP_ALIGN_OVERLAP:
+            return one
+        if one.qry_start <= two.qry_start and one.trg_start <= two.trg_start:
+            left, right = one, two
+        elif two.qry_start <= one.qry_start and two.trg_start <= one.trg_start:
+            left, right = two, one
+        else:
+            return one
+        lq, rq, qry_end = cls._merge_alns(left.qry_start, left.qry_end, left.qry_seq, right.qry_start, right.qry_end, right.qry_seq)
+        lt, rt, trg_end = cls._merge_alns(left.trg_start, left.trg_end, left.trg_seq, right.trg_start, right.trg_end, right.trg_seq)
+        diff = len(lq) + len(rq) - len(lt) - len(rt)
+        err_rate = (one.err_rate * len(one.trg_seq) + two.err_rate * len(two.trg_seq)) / (len(one.trg_seq) + len(two.trg_seq))
+        return Alignment(one.qry_id, one.trg_id, left.qry_start, qry_end, one.qry_sign, one.qry_len, left.trg_start, trg_end,
+                         one.trg_sign, one.trg_len, lq + "-" * max(-diff, 0) + rq, lt + "-" * max(diff, 0) + rt, err_rate, False)
+
+    @classmethod
+    def _collapse_cons_aln(cls, cons_aligns):
+        coll = None
+        for aln in cons_aligns[0]:
+            if coll is None:
+                coll = aln
+            elif cls._overlap(coll, aln) <= cls.MAX_SUPP_ALIGN_OVERLAP:
+                coll = cls._collapse(coll, aln)
+        return coll
+
+    # ---- the device calls ------------------------------------------------------------------------------------------
+    @staticmethod
+    def _columns(alns):
+        return (np.cumsum([0] + [len(a.trg_seq) for a in alns]), "".join(a.trg_seq for a in alns).encode("latin-1"),
+                "".join(a.qry_seq for a in alns).encode("latin-1"))
+
+    def confirm(self, jobs):
+        """jobs: [(pos, {edge_id: collapsed alignment}, side)] -> [(confirmed, rejected, {edge_id: consensus_pos})], what
+        _evaluate_positions returns per job, in one device call"""
+        alns = [a for _, cons, _ in jobs for a in cons.values()]
+        lists = [x for k in self.KEYS for x in (np.cumsum([0] + [len(pos[k]) for pos, _, _ in jobs]), [p for pos, _, _ in jobs for p in pos[k]])]
+        res = self.ctx.confirm_positions([("in", "out").index(side) for _, _, side in jobs], np.cumsum([0] + [len(cons) for _, cons, _ in jobs]),
+                                         [a.trg_start for a in alns], [a.trg_end for a in alns], [a.qry_start for a in alns],
+                                         *self._columns(alns), *lists)
+        out, e = [], 0
+        for j, (_, cons, _) in enumerate(jobs):
+            confirmed, rejected = res.positions(j)
+            out.append((confirmed, rejected, {edge_id: res.consensus_pos(e + i) for i, edge_id in enumerate(cons)}))
+            e += len(cons)
+        return out
+
+    def classify(self, jobs):
+        """jobs: [(read_aligns {edge_id: [alignments of the first chunk, ...]}, consensus_pos, headers_to_id)] -> the
+        partitioning list of _classify_reads per job, in one device call.  Alignments of reads headers_to_id does not
+        hold take no part: the reference scores them and never reports them."""
+        job_edges, numbers, kept = [], [], []
+        for read_aligns, _, headers_to_id in jobs:
+            number = {h: i for i, h in enumerate(headers_to_id)}
+            numbers.append(number)
+            job_edges.append([[a for a in read_aligns[e][0] if a.trg_id != "*" and a.qry_id in number] for e in read_aligns])
+        edges = [lst for je in job_edges for lst in je]
+        pos = [list(cons_pos[e]) for read_aligns, cons_pos, _ in jobs for e in read_aligns]
+        alns = [a for lst in edges for a in lst]
+        reads = [number[a.qry_id] for je, number in zip(job_edges, numbers) for lst in je for a in lst]
+        res = self.ctx.classify_reads(self.buffer_count, np.cumsum([0] + [len(je) for je in job_edges]), [len(n) for n in numbers],
+                                      np.cumsum([0] + [len(p) for p in pos]), [x for p in pos for x in p],
+                                      np.cumsum([0] + [len(lst) for lst in edges]), reads, [a.trg_start for a in alns],
+                                      [a.trg_end for a in alns], *self._columns(alns))
+        out = []
+        for j, (read_aligns, _, headers_to_id) in enumerate(jobs):
+            ids = list(read_aligns)
+            out.append([(headers_to_id[h], self.STATUS[st], str(ids[edge]) if st == 2 else "NA", top, total, h)
+                        for h, (st, edge, top, total) in zip(headers_to_id, res.reads(j))])
+        return out
+
+    def _read_alignment(self, alignment, target_path):
+        sam = SamAlignments(self.ctx, alignment, DivergenceFinder.read_fasta(target_path), self.max_read_coverage)
+        return [alns for _, alns in sam.chunks()]
+
+    def partition_reads(self, edges, it, side, position_path, cons_align_path, template, read_align_path, consensuses,
+                        confirmed_pos_path, part_file, headers_to_id):
+        skip = False
+        pos = self.read_positions(position_path)
+        cons_aligns = {}
+        for edge_id in edges:
+            if not os.path.isfile(cons_align_path.format(it, side, edge_id)):
+                skip = True
+            else:
+                cons_aligns[edge_id] = self._read_alignment(cons_align_path.format(it, side, edge_id), template)
+            if skip or not cons_aligns or not cons_aligns[edge_id] or not cons_aligns[edge_id][0]:
+                skip = True
+        if skip:
+            if it <= 1:
+                confirmed, rejected = {k: [] for k in self.KEYS}, {k: [] for k in self.KEYS}
+                consensus_pos = pos
+            else:
+                confirmed, rejected, consensus_pos = self._read_confirmed_positions(confirmed_pos_path.format(it - 1, side))
+        else:
+            coll = {edge_id: self._collapse_cons_aln(aln) for edge_id, aln in cons_aligns.items()}
+            (confirmed, rejected, consensus_pos), = self.confirm([(pos, coll, side)])
+        self._write_confirmed_positions(confirmed, rejected, pos, confirmed_pos_path.format(it, side))
+        read_aligns = {}
+        for edge_id in edges:
+            if not os.path.isfile(read_align_path.format(it, side, edge_id)) or not os.path.isfile(consensuses[(it, side, edge_id)]):
+                skip = True
+            elif not skip:
+                read_aligns[edge_id] = self._read_alignment(read_align_path.format(it, side, edge_id), consensuses[(it, side, edge_id)])
+            if skip or not read_aligns or not read_aligns[edge_id] or not read_aligns[edge_id][0]:
+                skip = True
+        if skip:
+            partitioning = self._read_partitioning_file(part_file.format(it - 1, side))
+        else:
+            partitioning, = self.classify([(read_aligns, consensus_pos, headers_to_id)])
+        self._write_partitioning_file(partitioning, part_file.format(it, side))
 
 
 # the reference's Alignment tuple (flye/utils/sam_parser.py:44-48)

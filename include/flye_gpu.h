@@ -1046,6 +1046,104 @@ int  fg_divergence_profile(fg_ctx* ctx, double sub_thresh, double del_thresh, do
                            struct fg_divergence_batch* out);
 void fg_release_divergence(struct fg_divergence_batch* b);
 
+/* Trestle's read partitioning (flye/trestle/trestle.py:1075-1142, partition_reads), two calls for batches of jobs; a job
+ * is one (repeat, side, iteration).  Both lend the context's device and stream only, use integers only, validate on the
+ * host before any device work and leave *out all zero after an error.  Column bytes below 128, case kept, '-' the gap.
+ * Offset arrays need not start at zero.  Sub-batches of whole jobs of at most FG_PARTITION_BATCH_COLS (environment,
+ * default 2^27) columns plus table cells (below) and, as switches for tests, FG_PARTITION_BATCH_JOBS jobs and
+ * FG_PARTITION_TILE columns per tile (a power of two in 64 .. 4096, default 1024); the result depends on none of them.
+ * FG_ERR_NOMEM: a job that alone exceeds the budget.  n_jobs = 0 gives an empty batch (every offset array = {0}).
+ *
+ * fg_confirm_positions = _evaluate_positions (:1360-1473).  Job j has the edges job_edge_off[j] .. job_edge_off[j+1], in
+ * the iteration order of cons_aligns; edge e has ONE alignment of its consensus to the template, collapsed by the caller:
+ * trg_start, trg_end, qry_start and the columns col_off[e] .. col_off[e+1].  Both shift_gaps passes run first
+ * (EdgeAlignment.__init__; see fg_make_bubbles).  The four tentative lists are job j's x_off[j] .. x_off[j+1] of x_pos, in
+ * any order, duplicates allowed; a value outside the walked range never matches.  For edge e and position t in
+ * [trg_start, trg_end) (the edge is "in alignment"): c = the (t - trg_start)-th non-gap target column, nuc = the query
+ * byte at c, qry_ind = qry_start + the non-gap query bytes before c, has_ins = a non-gap query byte strictly between the
+ * previous non-gap target column (or the start) and c.  With min_start / max_end / min_end / max_start over the job's
+ * edges, a position t of [min_start, max_end) that `total` holds is judged when side = 0 ("in") and t < min_end, or
+ * side = 1 ("out") and t >= max_start; otherwise it goes to no list.  Over the edges in alignment, in order: has_ins sets
+ * ins and appends qry_ind - 1 to the edge's cons_pos; ref = nuc of the FIRST such edge, never replaced; a later edge with
+ * nuc != ref, neither of them 'N', sets del when ref is '-' and sub otherwise.  With any flag t goes to confirmed total,
+ * with del or sub every edge in alignment appends its qry_ind (behind its insertion entry), and t goes to confirmed or
+ * rejected ins / del / sub by the matching flag where the tentative list holds t; without a flag t goes to rejected total
+ * and to the rejected lists whose tentative list holds it.  The eight lists are ascending; cons_pos is ascending in t and
+ * may hold duplicates and -1.  The table cells of a job are max_end - min_start.
+ * FG_ERR_ARG: NULL out or NULL where something is read; an offset array that decreases; a byte >= 128; side > 1; a job
+ * without edges; trg_start < 0; an edge whose non-gap target columns are not trg_end - trg_start. */
+struct fg_confirm_batch {
+	uint32_t  n_jobs;
+	uint32_t  pad_;
+	uint64_t  n_edges;
+	uint64_t* conf_total_off;     /* n_jobs + 1, likewise the other seven x_off */
+	int32_t*  conf_total_pos;
+	uint64_t* conf_sub_off;
+	int32_t*  conf_sub_pos;
+	uint64_t* conf_del_off;
+	int32_t*  conf_del_pos;
+	uint64_t* conf_ins_off;
+	int32_t*  conf_ins_pos;
+	uint64_t* rej_total_off;
+	int32_t*  rej_total_pos;
+	uint64_t* rej_sub_off;
+	int32_t*  rej_sub_pos;
+	uint64_t* rej_del_off;
+	int32_t*  rej_del_pos;
+	uint64_t* rej_ins_off;
+	int32_t*  rej_ins_pos;
+	uint64_t* cons_off;           /* n_edges + 1: edge job_edge_off[0] + i has cons_pos[cons_off[i] .. cons_off[i+1]] */
+	int32_t*  cons_pos;
+	void*     owner_;
+};
+int  fg_confirm_positions(fg_ctx* ctx, uint32_t n_jobs, const uint8_t* side, const uint64_t* job_edge_off,
+                          const int32_t* trg_start, const int32_t* trg_end, const int32_t* qry_start, const uint64_t* col_off,
+                          const uint8_t* trg_cols, const uint8_t* qry_cols, const uint64_t* total_off, const int32_t* total_pos,
+                          const uint64_t* sub_off, const int32_t* sub_pos, const uint64_t* del_off, const int32_t* del_pos,
+                          const uint64_t* ins_off, const int32_t* ins_pos, struct fg_confirm_batch* out);
+void fg_release_confirm(struct fg_confirm_batch* b);
+
+/* fg_classify_reads = _classify_reads with _index_mapping (:1539-1628).  Job j has the edges job_edge_off[j] ..
+ * job_edge_off[j+1] in read_aligns order and job_n_reads[j] = len(headers_to_id) reads.  Edge e has its consensus_pos list
+ * edge_pos[edge_pos_off[e] .. edge_pos_off[e+1]] (fg_confirm_positions' cons_pos as it is) and the alignments
+ * edge_aln_off[e] .. edge_aln_off[e+1] in list order; alignment a has read[a] < n_reads (the caller's number of
+ * aln.qry_id; the same number in one job is the same read, across edges), trg_start, trg_end and its columns.  No
+ * shift_gaps: the reference scores the parser's strings.  score(a) = the entries p of the edge's list, with multiplicity,
+ * with trg_start <= p < trg_end and equal bytes in trg_cols and qry_cols at the (p - trg_start)-th non-gap target column.
+ * The reference zeroes read_scores[read][edge] at EVERY alignment and scores a read's first two per edge, so the
+ * (read, edge) score is the score of the LAST alignment in list order when the read has one or two on the edge, and 0 with
+ * three or more.  The edges a read has an alignment on vote, in edge order:
+ *     top_edge = none, top_score = 0, total = 0, tie = false
+ *     s - buffer_count > top_score:                         top_edge = edge, top_score = s, tie = false
+ *     else s - buffer_count <= top_score and s >= top_score: top_score = s, tie = true
+ *     else s >= top_score - buffer_count and s < top_score:  tie = true
+ *     total += s
+ * status = 0 ("None") without an alignment or with total = 0, else 1 ("Tied") with tie, else 2 ("Partitioned");
+ * top_edge = the index within the job, -1 unless status is 2; top_score and total_score as they stand.  want_scores also
+ * returns per alignment (from edge_aln_off[job_edge_off[0]] on) aln_score, its own count, and aln_counted, 1 where it is
+ * the one whose score its edge keeps.  The table cells of a job: per edge, the span from its alignments' smallest
+ * trg_start to their largest trg_end.
+ * FG_ERR_ARG: as fg_confirm_positions (an alignment's non-gap target columns against trg_end - trg_start); also
+ * read[a] >= n_reads, buffer_count < 0, and a job whose edge lists together hold 2^31 entries or more. */
+struct fg_classify_batch {
+	uint32_t  n_jobs;
+	uint32_t  pad_;
+	uint64_t  n_alignments;
+	uint64_t* read_off;           /* n_jobs + 1, into the four arrays below */
+	uint8_t*  status;             /* 0 None, 1 Tied, 2 Partitioned */
+	int32_t*  top_edge;
+	int32_t*  top_score;
+	int32_t*  total_score;
+	int32_t*  aln_score;          /* want_scores: n_alignments */
+	uint8_t*  aln_counted;
+	void*     owner_;
+};
+int  fg_classify_reads(fg_ctx* ctx, int32_t buffer_count, uint32_t n_jobs, const uint64_t* job_edge_off, const uint32_t* job_n_reads,
+                       const uint64_t* edge_pos_off, const int32_t* edge_pos, const uint64_t* edge_aln_off, const uint32_t* read,
+                       const int32_t* trg_start, const int32_t* trg_end, const uint64_t* col_off, const uint8_t* trg_cols,
+                       const uint8_t* qry_cols, uint8_t want_scores, struct fg_classify_batch* out);
+void fg_release_classify(struct fg_classify_batch* b);
+
 #ifdef __cplusplus
 }
 #endif
