@@ -577,6 +577,26 @@ int fg_debug_sort_pairs32(fg_ctx* c, uint32_t* keys, uint32_t* vals, const uint6
 	});
 }
 
+int fg_debug_sort_pairs32_val16(fg_ctx* c, uint32_t* keys, uint16_t* vals, const uint64_t* seg_off, uint32_t n_seg, int cur_bits,
+								int rec_bits, const uint32_t* tie_free, uint64_t* radix_segments, uint64_t* radix_hits)
+{
+	if (!c || !seg_off || !radix_segments || !radix_hits || (seg_off[n_seg] && (!keys || !vals)) || cur_bits < 0 || rec_bits < 0 ||
+		cur_bits + rec_bits > 32)
+		return FG_ERR_ARG;
+	return guarded(c, [&]()
+	{
+		HIP_CHECK(hipSetDevice(c->device));
+		fgDebugSortPairs32v16(c, keys, vals, seg_off, n_seg, cur_bits, rec_bits, tie_free, radix_segments, radix_hits);
+	});
+}
+
+int fg_debug_hit_val16(fg_ctx* c, uint32_t* val16)
+{
+	if (!c || !val16) return FG_ERR_ARG;
+	*val16 = c->hitVal16 ? 1u : 0u;
+	return FG_OK;
+}
+
 int fg_debug_tie_free(fg_ctx* c, uint32_t* out, uint32_t max_n, uint32_t* first_query, uint32_t* n)
 {
 	if (!c || !first_query || !n || (max_n && !out)) return FG_ERR_ARG;

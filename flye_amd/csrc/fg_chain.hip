@@ -1201,7 +1201,9 @@ void fgChainStage(fg_ctx* c, const fg_detector_params* p, uint8_t forceLocal, u6
 #define SMALL_ARGS(view) cp, c->dListFused.p, nFused, nGroups, nHits, c->dGroupStart.p, c->dGroupQuery.p, c->curQuery, c->dLen.p, qLen, \
 		view, c->dGroupExt.p, c->dCur.p, c->dExt.p, c->dBack.p, c->dCand.p, c->dDpSize.p, c->dPrimFlag.p, (int)fusedMax
 		const size_t ldsSmall = (size_t)fusedMax * 28;
-		if (keyMode == 0)
+		if (keyMode == 0 && c->hitVal16)
+			hipLaunchKernelGGL(k_chain_small<K32V16>, nFused, 64, ldsSmall, s, SMALL_ARGS((HitKeyView<K32V16>{c->dHitKey32.p, c->dHitVal16.p, curBits, c->firstId})));
+		else if (keyMode == 0)
 			hipLaunchKernelGGL(k_chain_small<u32>, nFused, 64, ldsSmall, s, SMALL_ARGS((HitKeyView<u32>{c->dHitKey32.p, c->dHitVal.p, curBits, c->firstId})));
 		else if (keyMode == 1)
 			hipLaunchKernelGGL(k_chain_small<PK>, nFused, 64, ldsSmall, s, SMALL_ARGS((HitKeyView<PK>{(const PK*)c->dHitKey.p, nullptr, curBits, c->firstId})));
@@ -1215,7 +1217,10 @@ void fgChainStage(fg_ctx* c, const fg_detector_params* p, uint8_t forceLocal, u6
 #define PREP_ARGS(view) cp, list, nList, nGroups, nHits, c->dGroupStart.p, c->dGroupQuery.p, c->curQuery, c->dLen.p, qLen, \
 		view, c->dGroupExt.p, c->dCur.p, c->dExt.p, c->dTmp32.p, c->dDpSize.p, c->dGroupExtSorted.p
 		const unsigned gridP = (nList + PREP_WAVES - 1) / PREP_WAVES;
-		if (keyMode == 0)
+		if (keyMode == 0 && c->hitVal16)
+			hipLaunchKernelGGL(k_group_prep<K32V16>, gridP, PREP_WAVES * 64, 0, on,
+							   PREP_ARGS((HitKeyView<K32V16>{c->dHitKey32.p, c->dHitVal16.p, curBits, c->firstId})));
+		else if (keyMode == 0)
 			hipLaunchKernelGGL(k_group_prep<u32>, gridP, PREP_WAVES * 64, 0, on,
 							   PREP_ARGS((HitKeyView<u32>{c->dHitKey32.p, c->dHitVal.p, curBits, c->firstId})));
 		else if (keyMode == 1)

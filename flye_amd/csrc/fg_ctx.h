@@ -23,6 +23,7 @@
 
 typedef uint64_t u64;
 typedef uint32_t u32;
+typedef uint16_t u16;
 typedef int32_t i32;
 
 #define FG_EMPTY_KEY 0xFFFFFFFFFFFFFFFFULL
@@ -366,6 +367,8 @@ struct fg_ctx {
 	DevBuf<i32> dFiltPos;
 	DevBuf<u64> dHitKey;		// extId<<32 | curPos
 	DevBuf<u32> dHitVal;		// extPos
+	DevBuf<u16> dHitVal16;		// extPos beside dHitKey32 when every target position fits 16 bits (hitVal16)
+	bool hitVal16 = false;		// the value form of the last sub-range this context expanded (fg_debug_hit_val16)
 	DevBuf<u32> dHitKey32;		// record << curBits | curPos, when that fits 32 bits (sort only)
 	DevBuf<i32> dScore, dBack;
 	DevBuf<int4> dCand;
@@ -520,7 +523,9 @@ struct NoVal {
 };
 
 // the sorted hit keys, typed at compile time: u64 = (extId << 32 | curPos),
-// u32 = ((extId - firstId) << curBits | curPos), PK = the packed record above
+// u32 = ((extId - firstId) << curBits | curPos), PK = the packed record above, K32V16 = the u32 keys with
+// 16-bit values (every target position below 2^16: two bytes less per hit in every pass over the values)
+struct K32V16;
 template <class KT> struct HitKeyView;
 template <> struct HitKeyView<u64> {
 	const u64* k; const u32* v; int curBits; u32 firstId;
@@ -531,6 +536,13 @@ template <> struct HitKeyView<u64> {
 };
 template <> struct HitKeyView<u32> {
 	const u32* k; const u32* v; int curBits; u32 firstId;
+	__device__ __forceinline__ u32 ext(u64 i) const { return (k[i] >> curBits) + firstId; }
+	__device__ __forceinline__ u32 ext_raw(u64 i) const { return k[i] >> curBits; }
+	__device__ __forceinline__ u32 cur(u64 i) const { return k[i] & ((1u << curBits) - 1u); }
+	__device__ __forceinline__ u32 val(u64 i) const { return v[i]; }
+};
+template <> struct HitKeyView<K32V16> {
+	const u32* k; const u16* v; int curBits; u32 firstId;
 	__device__ __forceinline__ u32 ext(u64 i) const { return (k[i] >> curBits) + firstId; }
 	__device__ __forceinline__ u32 ext_raw(u64 i) const { return k[i] >> curBits; }
 	__device__ __forceinline__ u32 cur(u64 i) const { return k[i] & ((1u << curBits) - 1u); }
@@ -810,6 +822,8 @@ void fgPolishBubbles(fg_ctx* c, const int64_t* score36, const uint8_t* cand, con
 void fgDebugSortPairs(fg_ctx* c, u64* keys, u32* vals, const u64* segOff, u32 nSeg);
 void fgDebugSortPairs32(fg_ctx* c, u32* keys, u32* vals, const u64* segOff, u32 nSeg, int curBits, int recBits,
 						const u32* tieFree, u64* radixSegments, u64* radixHits);
+void fgDebugSortPairs32v16(fg_ctx* c, u32* keys, u16* vals, const u64* segOff, u32 nSeg, int curBits, int recBits,
+						   const u32* tieFree, u64* radixSegments, u64* radixHits);
 void fgDebugTieFree(fg_ctx* c, u32* out, u32 maxN, u32* firstQuery, u32* n);
 void fgDebugSortScreen(fg_ctx* c, const u32* keys, const u64* segOff, u32 nSeg, int curBits, int recBits, const u32* tieFree,
 					   float minUnique, i32 minOverlap, u32* outReason);

@@ -283,15 +283,17 @@ __global__ void k_probe_count(const u64* __restrict__ qKmerOff, const u64* __res
 // together): key = record << curBits | curPos -- same order, a third less sort traffic.
 // KT = PK: one 64-bit record per hit (fg_ctx.h), no value array.  Consumers read any of the
 // three through HitKeyView<KT>.  KT = fg_seed_hit: the (curPos, extPos, extId) tuples fg_probe_hits exports.
+// VT = u16 (with KT = u32, every target position below 2^16): the value leaves as a 2-byte store of the thread's own
+// slot -- the other half of its 32-bit word may belong to the next query's block.
 #ifndef FILL_ITEMS
 #define FILL_ITEMS 4
 #endif
-template <class KT>
+template <class KT, class VT = u32>
 __global__ void k_fill(const u32* __restrict__ query, const i32* __restrict__ len, const i32* __restrict__ qLen,
 					   const u64* __restrict__ qKmerOff, int k, u32 firstId, int curBits,
 					   const u64* __restrict__ probe, const u64* __restrict__ entries,
 					   const u64* __restrict__ hitOff, const u64* __restrict__ filtOff,
-					   KT* __restrict__ hitKey, u32* __restrict__ hitVal, i32* __restrict__ filtPos,
+					   KT* __restrict__ hitKey, VT* __restrict__ hitVal, i32* __restrict__ filtPos,
 					   u32* __restrict__ tieFree /* per query, or null: 1 = no two emitted hits share (record, curPos) */)
 {
 	// FILL_ITEMS consecutive positions per thread and step: a step is a chain of barriers, LDS searches and
@@ -399,7 +401,7 @@ __global__ void k_fill(const u32* __restrict__ query, const i32* __restrict__ le
 			{
 				if (sizeof(KT) == 8) hitKey[hbase + o] = (KT)(((u64)(firstId + srec) << 32) | (u32)(p0 + (i32)t));
 				else hitKey[hbase + o] = (KT)((srec << curBits) | (u32)(p0 + (i32)t));
-				hitVal[hbase + o] = (u32)spos;
+				hitVal[hbase + o] = (VT)(u32)spos;
 			}
 		}
 		__syncthreads();
@@ -546,14 +548,16 @@ struct SortTask { u64 start; u32 n; u32 depth; };
 // up to FG_SORT_RADIX_MAX
 __device__ __forceinline__ bool sort_radix_size(u64 n, u32 radixMax) { return n > SORT_CAP && n <= radixMax; }
 
-// the value array that goes with a key type: a real u32 array, or nothing for packed records
-template <class KT> struct ValPtr {
-	typedef u32* type;
-	static __device__ __forceinline__ type at(u32* v, u64 off) { return v + off; }
+// the value array that goes with a key type: a real array of VT (u32, or u16 beside u32 keys when every value fits:
+// an element is read widened to u32 and written as one store of its own 2 bytes, so a piece never touches the half of
+// a 32-bit word that belongs to its neighbour), or nothing for packed records
+template <class KT, class VT = u32> struct ValPtr {
+	typedef VT* type;
+	static __device__ __forceinline__ type at(VT* v, u64 off) { return v + off; }
 };
-template <> struct ValPtr<PK> {
+template <class VT> struct ValPtr<PK, VT> {
 	typedef NoVal type;
-	static __device__ __forceinline__ type at(u32*, u64) { return NoVal{}; }
+	static __device__ __forceinline__ type at(VT*, u64) { return NoVal{}; }
 };
 
 // block-aggregated append (one atomic per list and block).  Lists: big (one wave per task in
@@ -773,8 +777,9 @@ k_sort_screen(const u64* __restrict__ hitOff, const u32* __restrict__ hitKey, in
 #define SORT_RADIX_ITEMS 8
 #define SORT_RADIX_TILE (WG * SORT_RADIX_ITEMS)
 #define SORT_RADIX_MAX_PASSES 4
+template <class VT>
 __global__ void __launch_bounds__(WG)
-k_sort_radix(const SortTask* __restrict__ tasks, u32 nTasks, u32* hitKey, u32* hitVal, u32* scratch /* read and written in turn */,
+k_sort_radix(const SortTask* __restrict__ tasks, u32 nTasks, u32* hitKey, VT* hitVal, u32* scratch /* read and written in turn */,
 			 u64 nHits, int curBits, int recBits)
 {
 	constexpr int IT = SORT_RADIX_ITEMS, TILE = SORT_RADIX_TILE, NW = WG / 64;
@@ -794,8 +799,9 @@ k_sort_radix(const SortTask* __restrict__ tasks, u32 nTasks, u32* hitKey, u32* h
 	const u32 lastMask = recBits % 8 ? (1u << (recBits % 8)) - 1u : 255u;
 	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 	const u64 below = lane == 0 ? 0ULL : (~0ULL >> (64 - lane));
-	u32* const kHome = hitKey + start; u32* const vHome = hitVal + start;
-	u32* const kTmp = scratch + start; u32* const vTmp = scratch + nHits + start;
+	u32* const kHome = hitKey + start; VT* const vHome = hitVal + start;
+	// the values' range of the scratch holds elements of VT: 16-bit values fill the front half of it
+	u32* const kTmp = scratch + start; VT* const vTmp = (VT*)(scratch + nHits) + start;
 
 	for (int p = 0; p < nPasses; ++p) hist[p][threadIdx.x] = 0;
 	__syncthreads();
@@ -816,8 +822,8 @@ k_sort_radix(const SortTask* __restrict__ tasks, u32 nTasks, u32* hitKey, u32* h
 
 	for (int p = 0; p < nPasses; ++p)
 	{
-		const u32* kin = (p & 1) ? kTmp : kHome; const u32* vin = (p & 1) ? vTmp : vHome;
-		u32* kout = (p & 1) ? kHome : kTmp; u32* vout = (p & 1) ? vHome : vTmp;
+		const u32* kin = (p & 1) ? kTmp : kHome; const VT* vin = (p & 1) ? vTmp : vHome;
+		u32* kout = (p & 1) ? kHome : kTmp; VT* vout = (p & 1) ? vHome : vTmp;
 		const int shift = curBits + 8 * p;
 		const u32 mask = p == nPasses - 1 ? lastMask : 255u;
 		for (u32 tb = 0; tb < n; tb += TILE)
@@ -893,7 +899,7 @@ k_sort_radix(const SortTask* __restrict__ tasks, u32 nTasks, u32* hitKey, u32* h
 					const u32 kk = sKey[j];
 					const u32 dst = sOffs[(kk >> shift) & mask] + j;		// < n: the digit's slots lie inside the segment
 					kout[dst] = kk;
-					vout[dst] = sVal[j];
+					vout[dst] = (VT)sVal[j];
 				}
 			}
 			__syncthreads();		// every store of the tile is issued before the LDS tables change
@@ -910,10 +916,10 @@ k_sort_radix(const SortTask* __restrict__ tasks, u32 nTasks, u32* hitKey, u32* h
 #ifndef SORT_WIDE_WAVES
 #define SORT_WIDE_WAVES 8
 #endif
-template <class KT>
+template <class KT, class VT = u32>
 __global__ void __launch_bounds__(SORT_WIDE_WAVES * 64)
 k_sort_wide(const SortTask* __restrict__ tasks, const u32* __restrict__ levelCnt, KT* __restrict__ hitKey,
-			u32* __restrict__ hitVal, u32* __restrict__ posScratch, u64 nHits,
+			VT* __restrict__ hitVal, u32* __restrict__ posScratch, u64 nHits,
 			SortTask* __restrict__ kids)
 {
 	__shared__ int shm[2 * SORT_WIDE_WAVES];
@@ -924,11 +930,11 @@ k_sort_wide(const SortTask* __restrict__ tasks, const u32* __restrict__ levelCnt
 		SortTask t = tasks[ti];
 		t.start = fg_uni(t.start); t.n = fg_uni(t.n); t.depth = fg_uni(t.depth);
 		KT* K = hitKey + t.start;
-		typename ValPtr<KT>::type V = ValPtr<KT>::at(hitVal, t.start);
+		typename ValPtr<KT, VT>::type V = ValPtr<KT, VT>::at(hitVal, t.start);
 		SortTask c0{0, 0, 0}, c1{0, 0, 0};
 		if (t.depth == 0)
 		{
-			if (threadIdx.x == 0) { wsort::PtrAcc<KT, typename ValPtr<KT>::type> acc{K, V}; fgsort::heap_sort_(acc, 0, (int)t.n); }
+			if (threadIdx.x == 0) { wsort::PtrAcc<KT, typename ValPtr<KT, VT>::type> acc{K, V}; fgsort::heap_sort_(acc, 0, (int)t.n); }
 		}
 		else
 		{
@@ -943,9 +949,9 @@ k_sort_wide(const SortTask* __restrict__ tasks, const u32* __restrict__ levelCnt
 }
 
 // one wave per task: one partition (or the depth-limit heapsort); children to slots 2i, 2i+1
-template <class KT>
+template <class KT, class VT = u32>
 __global__ void k_sort_level(const SortTask* __restrict__ tasks, const u32* __restrict__ levelCnt, KT* __restrict__ hitKey,
-							 u32* __restrict__ hitVal, u32* __restrict__ posScratch, u64 nHits,
+							 VT* __restrict__ hitVal, u32* __restrict__ posScratch, u64 nHits,
 							 SortTask* __restrict__ children)
 {
 	const int lane = threadIdx.x & 63;
@@ -956,11 +962,11 @@ __global__ void k_sort_level(const SortTask* __restrict__ tasks, const u32* __re
 		SortTask t = tasks[ti];
 		t.start = fg_uni(t.start); t.n = fg_uni(t.n); t.depth = fg_uni(t.depth);
 		KT* K = hitKey + t.start;
-		typename ValPtr<KT>::type V = ValPtr<KT>::at(hitVal, t.start);
+		typename ValPtr<KT, VT>::type V = ValPtr<KT, VT>::at(hitVal, t.start);
 		SortTask c0{0, 0, 0}, c1{0, 0, 0};
 		if (t.depth == 0)
 		{
-			if (lane == 0) { wsort::PtrAcc<KT, typename ValPtr<KT>::type> acc{K, V}; fgsort::heap_sort_(acc, 0, (int)t.n); }
+			if (lane == 0) { wsort::PtrAcc<KT, typename ValPtr<KT, VT>::type> acc{K, V}; fgsort::heap_sort_(acc, 0, (int)t.n); }
 		}
 		else
 		{
@@ -991,10 +997,10 @@ __global__ void k_sort_route(const SortTask* __restrict__ children, const u32* _
 	}
 }
 
-template <class KT>
+template <class KT, class VT = u32>
 __global__ void __launch_bounds__(SORT_LDS_WAVES * 64)
 k_sort_lds(const SortTask* __restrict__ tasks, u32 nTasks,
-		   KT* __restrict__ hitKey, u32* __restrict__ hitVal, int curBits, u64 narrowMax,
+		   KT* __restrict__ hitKey, VT* __restrict__ hitVal, int curBits, u64 narrowMax,
 		   u32* __restrict__ posScratch, u64 nHits)
 {
 	// the LDS piece always holds 32-bit keys (12 B per hit with the position scratch)
@@ -1010,7 +1016,7 @@ k_sort_lds(const SortTask* __restrict__ tasks, u32 nTasks,
 	SortTask t = tasks[ti];
 	t.start = fg_uni(t.start); t.n = fg_uni(t.n); t.depth = fg_uni(t.depth);
 	KT* K = hitKey + t.start;
-	u32* V = hitVal + t.start;
+	VT* V = hitVal + t.start;
 	const int n = (int)t.n;
 	if constexpr (std::is_same<KT, PK>::value)
 	{
@@ -1074,7 +1080,7 @@ k_sort_lds(const SortTask* __restrict__ tasks, u32 nTasks,
 		for (int i = lane; i < n; i += 64) { sK[wv][i] = (u32)K[i]; sV[wv][i] = V[i]; }
 		wsort::wave_mem_fence();
 		wsort::wave_sort<u32, unsigned short>(sK[wv], sV[wv], n, sPL[wv], sPR[wv], stack[wv], small[wv], 0, (int)t.depth);
-		for (int i = lane; i < n; i += 64) { K[i] = (KT)sK[wv][i]; V[i] = sV[wv][i]; }
+		for (int i = lane; i < n; i += 64) { K[i] = (KT)sK[wv][i]; V[i] = (VT)sV[wv][i]; }
 		continue;
 	}
 	else
@@ -1115,7 +1121,7 @@ k_sort_lds(const SortTask* __restrict__ tasks, u32 nTasks,
 		{
 			const u64 p = (u64)sK[wv][i] + mn;
 			K[i] = (KT)(curBits ? (((p >> curBits) << 32) | (p & lowMask)) : p);
-			V[i] = sV[wv][i];
+			V[i] = (VT)sV[wv][i];
 		}
 		continue;
 	}
@@ -1359,8 +1365,8 @@ static bool sortScreen(fg_ctx* c, const u64* dSegOff, u32 nSeg, const u32* dK, i
 	return true;
 }
 
-template <class KT>
-static void sortSegments(fg_ctx* c, const u64* dSegOff, u32 nSeg, KT* dK, u32* dV, u64 nHits, int curBits = 0,
+template <class KT, class VT = u32>
+static void sortSegments(fg_ctx* c, const u64* dSegOff, u32 nSeg, KT* dK, VT* dV, u64 nHits, int curBits = 0,
 						 const u32* dTieFree = nullptr, int recBits = 0, SortRadixStats* stats = nullptr)
 {
 	hipStream_t s = c->stream;
@@ -1419,7 +1425,7 @@ static void sortSegments(fg_ctx* c, const u64* dSegOff, u32 nSeg, KT* dK, u32* d
 		{
 			// ahead of level 0: its blocks run for as long as a few levels and fill the chip beside their thin tails
 			{ ScopedK t(c->timer, "k_sort_radix");
-			  hipLaunchKernelGGL(k_sort_radix, nRadix, WG, 0, s, radixT, nRadix, dK, dV, c->dTmp32.p, nHits, curBits, recBits); }
+			  hipLaunchKernelGGL(k_sort_radix<VT>, nRadix, WG, 0, s, radixT, nRadix, dK, dV, c->dTmp32.p, nHits, curBits, recBits); }
 			if (stats)
 			{
 				std::vector<SortTask> h(nRadix);
@@ -1453,10 +1459,10 @@ static void sortSegments(fg_ctx* c, const u64* dSegOff, u32 nSeg, KT* dK, u32* d
 			const u32* rowL = levelCnt + 4 * level;
 			u32* rowN = levelCnt + 4 * (level + 1);
 			if (ubWide)	// the long poles first
-				hipLaunchKernelGGL(k_sort_wide<KT>, (unsigned)std::min<u64>(ubWide, 2048), SORT_WIDE_WAVES * 64, 0, s, wideA, rowL, dK, dV,
+				hipLaunchKernelGGL((k_sort_wide<KT, VT>), (unsigned)std::min<u64>(ubWide, 2048), SORT_WIDE_WAVES * 64, 0, s, wideA, rowL, dK, dV,
 								   c->dTmp32.p, nHits, kids);
 			if (ubBig)
-				hipLaunchKernelGGL(k_sort_level<KT>, (unsigned)std::min<u64>((ubBig + SORT_LEVEL_WAVES - 1) / SORT_LEVEL_WAVES, 1u << 20),
+				hipLaunchKernelGGL((k_sort_level<KT, VT>), (unsigned)std::min<u64>((ubBig + SORT_LEVEL_WAVES - 1) / SORT_LEVEL_WAVES, 1u << 20),
 								   SORT_LEVEL_WAVES * 64, 0, s, bigA, rowL, dK, dV, c->dTmp32.p, nHits, kids);
 			const u64 ubKids = 2 * (ubBig + ubWide);
 			hipLaunchKernelGGL(k_sort_route, (unsigned)std::min<u64>((ubKids + WG - 1) / WG, 4096), WG, 0, s, kids, rowL, lists, bigB, wideB,
@@ -1475,7 +1481,7 @@ static void sortSegments(fg_ctx* c, const u64* dSegOff, u32 nSeg, KT* dK, u32* d
 	if (cnt[1])
 	{
 		ScopedK t(c->timer, "k_sort_lds");
-		hipLaunchKernelGGL(k_sort_lds<KT>, (cnt[1] + SORT_LDS_WAVES - 1) / SORT_LDS_WAVES, SORT_LDS_WAVES * 64, 0, s,
+		hipLaunchKernelGGL((k_sort_lds<KT, VT>), (cnt[1] + SORT_LDS_WAVES - 1) / SORT_LDS_WAVES, SORT_LDS_WAVES * 64, 0, s,
 						   smallT, cnt[1], dK, dV, curBits, narrowMax, c->dTmp32.p, nHits);
 	}
 }
@@ -1578,6 +1584,27 @@ void fgDebugSortPairs32(fg_ctx* c, u32* keys, u32* vals, const u64* segOff, u32 
 	if (nSeg && n) sortSegments<u32>(c, dOff.p, nSeg, dK.p, dV.p, n, curBits, tieFree ? dFlag.p : nullptr, recBits, &st);
 	HIP_CHECK(hipMemcpyAsync(keys, dK.p, n * 4, hipMemcpyDeviceToHost, s));
 	HIP_CHECK(hipMemcpyAsync(vals, dV.p, n * 4, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(hipStreamSynchronize(s));
+	*radixSegments = st.segments; *radixHits = st.hits;
+}
+
+// fg_debug_sort_pairs32_val16: the same with 16-bit values, the form deviceSub takes when every target position fits
+void fgDebugSortPairs32v16(fg_ctx* c, u32* keys, u16* vals, const u64* segOff, u32 nSeg, int curBits, int recBits,
+						   const u32* tieFree, u64* radixSegments, u64* radixHits)
+{
+	hipStream_t s = c->stream;
+	const u64 n = segOff[nSeg];
+	*radixSegments = *radixHits = 0;
+	DevBuf<u32> dK, dFlag; DevBuf<u16> dV; DevBuf<u64> dOff;
+	dK.alloc(n + 1); dV.alloc(n + 2); dOff.alloc(nSeg + 1); dFlag.alloc(nSeg + 1);
+	HIP_CHECK(hipMemcpyAsync(dK.p, keys, n * 4, hipMemcpyHostToDevice, s));
+	HIP_CHECK(hipMemcpyAsync(dV.p, vals, n * 2, hipMemcpyHostToDevice, s));
+	HIP_CHECK(hipMemcpyAsync(dOff.p, segOff, (nSeg + 1) * 8ULL, hipMemcpyHostToDevice, s));
+	if (tieFree) HIP_CHECK(hipMemcpyAsync(dFlag.p, tieFree, nSeg * 4ULL, hipMemcpyHostToDevice, s));
+	SortRadixStats st{0, 0};
+	if (nSeg && n) sortSegments<u32, u16>(c, dOff.p, nSeg, dK.p, dV.p, n, curBits, tieFree ? dFlag.p : nullptr, recBits, &st);
+	HIP_CHECK(hipMemcpyAsync(keys, dK.p, n * 4, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(hipMemcpyAsync(vals, dV.p, n * 2, hipMemcpyDeviceToHost, s));
 	HIP_CHECK(hipStreamSynchronize(s));
 	*radixSegments = st.segments; *radixHits = st.hits;
 }
@@ -1837,13 +1864,22 @@ static void deviceSub(fg_ctx* c, const fg_detector_params* p, uint8_t forceLocal
 	const bool canPack = recBits + curBits + FG_PK_VALBITS <= 64 && c->maxLen < (1 << FG_PK_VALBITS);
 	const bool wantPack = !(getenv("FG_PACKED_KEYS") && atoi(getenv("FG_PACKED_KEYS")) == 0);
 	const int keyMode = key32 ? 0 : ((canPack && wantPack) ? 1 : 2);
+	// 32-bit keys with 16-bit values: every target position (below the indexed container's longest read) fits 16 bits.
+	// The option-B receiver writes 32-bit values; FG_VAL16=0 keeps them everywhere (A/B runs, parity tests).
+	const bool val16 = keyMode == 0 && !recv && c->maxLen <= 65536 && !(getenv("FG_VAL16") && atoi(getenv("FG_VAL16")) == 0);
+	c->hitVal16 = val16;
 	if (keyMode == 0)
 	{
-		c->dHitKey32.reserve(hitCap + 1); c->dHitVal.reserve(hitCap + 1); c->dTieFree.reserve(nq + 1);
+		c->dHitKey32.reserve(hitCap + 1); c->dTieFree.reserve(nq + 1);
+		if (val16) c->dHitVal16.reserve(hitCap + 2); else c->dHitVal.reserve(hitCap + 1);
 		if (recv) recvFill<u32>(c, recv, callQ0, sub0, nq, nHits, curBits, c->dHitKey32.p, c->dHitVal.p);
 		else { ScopedK t(c->timer, "k_fill");
-		  hipLaunchKernelGGL(k_fill<u32>, nq, WG, 0, s, dQuery, c->dLen.p, qLen, dQKmerOff, k, c->firstId, curBits,
-							 c->dProbe.p, c->dEntries.p, c->dHitOff.p, c->dFiltOff.p, c->dHitKey32.p, c->dHitVal.p, c->dFiltPos.p, c->dTieFree.p); }
+		  if (val16)
+			  hipLaunchKernelGGL((k_fill<u32, u16>), nq, WG, 0, s, dQuery, c->dLen.p, qLen, dQKmerOff, k, c->firstId, curBits,
+								 c->dProbe.p, c->dEntries.p, c->dHitOff.p, c->dFiltOff.p, c->dHitKey32.p, c->dHitVal16.p, c->dFiltPos.p, c->dTieFree.p);
+		  else
+			  hipLaunchKernelGGL(k_fill<u32>, nq, WG, 0, s, dQuery, c->dLen.p, qLen, dQKmerOff, k, c->firstId, curBits,
+								 c->dProbe.p, c->dEntries.p, c->dHitOff.p, c->dFiltOff.p, c->dHitKey32.p, c->dHitVal.p, c->dFiltPos.p, c->dTieFree.p); }
 		if (!recv) { c->tieFreeQ0 = callQ0 + sub0; c->tieFreeN = nq; }
 		// the receiver path knows no ties: every query goes through the emulation there
 		const u32* sortFree = recv ? nullptr : c->dTieFree.p;
@@ -1855,7 +1891,8 @@ static void deviceSub(fg_ctx* c, const fg_detector_params* p, uint8_t forceLocal
 						   c->dSortFree.p, c->dSortReason.p))
 				{ sortFree = c->dSortFree.p; c->sortReasonN = nq; }
 		}
-		sortSegments<u32>(c, c->dHitOff.p, nq, c->dHitKey32.p, c->dHitVal.p, nHits, curBits, sortFree, recBits);
+		if (val16) sortSegments<u32, u16>(c, c->dHitOff.p, nq, c->dHitKey32.p, c->dHitVal16.p, nHits, curBits, sortFree, recBits);
+		else sortSegments<u32>(c, c->dHitOff.p, nq, c->dHitKey32.p, c->dHitVal.p, nHits, curBits, sortFree, recBits);
 	}
 	else if (keyMode == 1)
 	{
@@ -1981,7 +2018,7 @@ static void stageBudgets(fg_ctx* c, u64& kmerBudget, u64& hitBudget)
 		// the chunk scratch may grow into the free memory plus what it already holds, less a reserve
 		size_t freeB = 0, totalB = 0;
 		HIP_CHECK(hipMemGetInfo(&freeB, &totalB));
-		const u64 held = c->dHitKey.bytes() + c->dHitKey32.bytes() + c->dHitVal.bytes() + c->dCur.bytes() + c->dExt.bytes() +
+		const u64 held = c->dHitKey.bytes() + c->dHitKey32.bytes() + c->dHitVal.bytes() + c->dHitVal16.bytes() + c->dCur.bytes() + c->dExt.bytes() +
 						 c->dScore.bytes() + c->dBack.bytes() + c->dTmp32.bytes() + c->dCand.bytes() + c->dProbe.bytes();
 		const u64 avail = (u64)freeB + held;
 		const u64 usable = avail > (8ULL << 30) ? (avail - (4ULL << 30)) / 10 * 9 : avail / 2;

@@ -7,6 +7,10 @@
 // Used for the three tie-sensitive sorts of getSeqOverlaps (reference
 // src/sequence/overlap.cpp:201-204, :269-275, :331-334).  K / V may live in global
 // memory or in LDS (the functions are inlined; hipcc resolves the address space).
+// The value array of the global-memory partitions is a pointer-like type VP: u32*, u16* (values below 2^16: an element
+// is read widened into a u32 register and written back as ONE 2-byte store of that element -- pieces begin at any hit
+// index, so the other half of its 32-bit word may be a neighbouring wave's; no store here ever covers two elements) or
+// NoVal (packed records).
 //
 // Closed form of the two-pointer Hoare loop used everywhere below: with
 //   l_1 < l_2 < ...  the positions (left to right)  whose key is >= pivot,

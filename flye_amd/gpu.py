@@ -366,6 +366,8 @@ def load_library():
         L.fg_debug_sort_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
         L.fg_debug_sort_pairs32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int,
                                             C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.fg_debug_sort_pairs32_val16.argtypes = L.fg_debug_sort_pairs32.argtypes
+        L.fg_debug_hit_val16.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.fg_debug_tie_free.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.fg_debug_sort_screen.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_void_p,
                                            C.c_float, C.c_int32, C.c_void_p]
@@ -853,6 +855,30 @@ class Context:
                                                  None if flags is None else flags.ctypes.data,
                                                  C.byref(segs), C.byref(hits)))
         return k, v, int(segs.value), int(hits.value)
+
+    def debug_sort_pairs32_val16(self, keys, vals, seg_off, cur_bits, rec_bits, tie_free=None):
+        """``debug_sort_pairs32`` in the 16-bit value form: ``vals`` (uint16, one per key) travel with the keys.
+        Returns (sorted keys, their values, segments on the radix path, hits on the radix path)."""
+        k = np.ascontiguousarray(keys, np.uint32).copy()
+        v = np.ascontiguousarray(vals, np.uint16).copy()
+        off = np.ascontiguousarray(seg_off, np.uint64)
+        if len(v) != len(k) or len(k) != int(off[-1]):
+            raise ValueError("one value per key, seg_off ending at their number")
+        flags = None if tie_free is None else np.ascontiguousarray(tie_free, np.uint32)
+        if flags is not None and len(flags) != len(off) - 1:
+            raise ValueError("one tie-free flag per segment")
+        segs, hits = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.L.fg_debug_sort_pairs32_val16(self.h, k.ctypes.data, v.ctypes.data, off.ctypes.data, len(off) - 1,
+                                                       int(cur_bits), int(rec_bits),
+                                                       None if flags is None else flags.ctypes.data,
+                                                       C.byref(segs), C.byref(hits)))
+        return k, v, int(segs.value), int(hits.value)
+
+    def debug_hit_val16(self):
+        """Whether the last sub-range of queries this context expanded carried 16-bit target positions."""
+        n = C.c_uint32(0)
+        self._check(self.L.fg_debug_hit_val16(self.h, C.byref(n)))
+        return bool(n.value)
 
     def debug_tie_free(self, max_n):
         """The seed expansion's tie-free flags of the last sub-range of queries this context expanded: (index of its

@@ -438,6 +438,17 @@ int fg_debug_sort_pairs32(fg_ctx* ctx, uint32_t* keys, uint32_t* vals, const uin
                           int cur_bits, int rec_bits, const uint32_t* tie_free,
                           uint64_t* radix_segments, uint64_t* radix_hits);
 
+/* Test hook: fg_debug_sort_pairs32 with 16-bit values, the hit form the overlap stage takes when every target position
+ * fits 16 bits (32-bit keys and an indexed container whose longest read has at most 65536 bases; FG_VAL16=0 keeps
+ * 32-bit values).  vals are the caller's, sorted along with the keys. */
+int fg_debug_sort_pairs32_val16(fg_ctx* ctx, uint32_t* keys, uint16_t* vals, const uint64_t* seg_off, uint32_t n_seg,
+                                int cur_bits, int rec_bits, const uint32_t* tie_free,
+                                uint64_t* radix_segments, uint64_t* radix_hits);
+
+/* Test hook: *val16 = 1 when the last sub-range of queries this context expanded in an fg_overlaps call carried its
+ * target positions as 16-bit values, else 0. */
+int fg_debug_hit_val16(fg_ctx* ctx, uint32_t* val16);
+
 /* Test hook: the per-query tie-free flags the seed expansion wrote for the last sub-range of queries this context
  * expanded in an fg_overlaps call (the whole call where it was not cut; none on the option-B receiver path and for
  * 64-bit key forms): *first_query = index of its first query in the call's query list, *n = its queries, out[i]
