@@ -32,9 +32,13 @@
 //   k_bub_fill      one wave per kept bubble: the consensus, the branch offsets and the branch bytes (gaps dropped by
 //                   ballot compaction, to_acgt by table).
 // The host does work proportional to contigs, alignments and bubbles (checks, offsets, the rate table).
+//
+// fg_make_bubbles_cigars takes SAM records where fg_make_bubbles takes columns: a sub-batch expands its own alignments
+// (fg_cigexpand.h) on the context's stream straight into the two column buffers, so no column crosses the bus.
 #include "fg_ctx.h"
 #include "fg_devprim.h"
 #include "fg_gapshift.h"
+#include "fg_cigexpand.h"
 #include <cmath>
 
 namespace {
@@ -534,7 +538,7 @@ struct BubBufs {
 void bubSubBatch(fg_ctx* c, const fg_bubble_params& P, u32 c0, u32 c1, const int32_t* contigLen, const uint8_t* contigCirc,
 				 const uint64_t* contigAlnOff, const int32_t* trgStart, const int32_t* trgEnd, const uint64_t* colOff,
 				 const uint8_t* trgCols, const uint8_t* qryCols, const uint8_t* inProf /* by absolute alignment - first */, u64 aln00,
-				 bool wantProfile, BubbleOwner& own)
+				 bool wantProfile, BubbleOwner& own, const CigSource* cig = nullptr /* the columns are expanded here, not read from the host */)
 {
 	hipStream_t s = c->stream;
 	const u32 nC = c1 - c0;
@@ -580,8 +584,9 @@ void bubSubBatch(fg_ctx* c, const fg_bubble_params& P, u32 c0, u32 c1, const int
 	BubBufs B{c};
 	BubAln* dAln = B.get<BubAln>(nAln);
 	BubContig* dCtg = B.get<BubContig>(nC);
-	unsigned char* dTrg = B.get<unsigned char>(nCols);
-	unsigned char* dQry = B.get<unsigned char>(nCols);
+	// k_cig_expand stores whole words past the last column
+	unsigned char* dTrg = B.get<unsigned char>(nCols + (cig ? CIG_LANE_COLS : 0));
+	unsigned char* dQry = B.get<unsigned char>(nCols + (cig ? CIG_LANE_COLS : 0));
 	unsigned char* dTrgS = B.get<unsigned char>(nCols);
 	unsigned char* dQryS = B.get<unsigned char>(nCols);
 	i32* dCnt = B.get<i32>(4 * nPos);			// coverage, inserts, deletions, mismatches
@@ -601,7 +606,9 @@ void bubSubBatch(fg_ctx* c, const fg_bubble_params& P, u32 c0, u32 c1, const int
 
 	HIP_CHECK(hipMemcpyAsync(dAln, alns.data(), (size_t)nAln * sizeof(BubAln), hipMemcpyHostToDevice, s));
 	HIP_CHECK(hipMemcpyAsync(dCtg, ctg.data(), (size_t)nC * sizeof(BubContig), hipMemcpyHostToDevice, s));
-	if (nCols)
+	CigStaged staged;		// read by the stream until the first wait below
+	if (cig && nAln) (void)cigExpandSource(c, *cig, staged, a0, a1, dTrg, dQry);
+	else if (nCols)
 	{
 		HIP_CHECK(hipMemcpyAsync(dTrg, trgCols + col0, nCols, hipMemcpyHostToDevice, s));
 		HIP_CHECK(hipMemcpyAsync(dQry, qryCols + col0, nCols, hipMemcpyHostToDevice, s));
@@ -795,6 +802,67 @@ void bubSubBatch(fg_ctx* c, const fg_bubble_params& P, u32 c0, u32 c1, const int
 	HIP_CHECK(hipStreamSynchronize(s));
 }
 
+// the finished owner into the caller's struct
+void bubHandOver(struct fg_bubble_batch* out, BubbleOwner* own, uint32_t n_contigs, bool want_profile)
+{
+	out->n_contigs = n_contigs;
+	out->n_bubbles = (uint32_t)own->position.size();
+	out->n_alignments = (uint64_t)own->inProfile.size();
+	out->bubble_off = own->bubbleOff.data();
+	out->position = own->position.data();
+	out->cand = own->cand.data();
+	out->cand_off = own->candOff.data();
+	out->branches = own->branches.data();
+	out->branch_off = own->branchOff.data();
+	out->bubble_branch_off = own->bubbleBranchOff.data();
+	out->n_long_bubbles = own->nLongBubbles.data();
+	out->n_empty = own->nEmpty.data();
+	out->n_long_branch = own->nLongBranch.data();
+	out->mean_cov = own->meanCov.data();
+	out->n_partition = own->nPartition.data();
+	out->in_profile = own->inProfile.data();
+	if (want_profile)
+	{
+		out->part_off = own->partOff.data();
+		out->partition = own->partition.data();
+		out->prof_off = own->profOff.data();
+		out->coverage = own->coverage.data();
+		out->num_inserts = own->numInserts.data();
+		out->num_deletions = own->numDeletions.data();
+		out->num_missmatch = own->numMissmatch.data();
+		out->nucl = own->nucl.data();
+	}
+	out->owner_ = own;
+}
+
+// what both calls check of the parameters
+void bubCheckParams(const std::string& name, const fg_bubble_params& P)
+{
+	if (P.solid_kmer_length <= 0 || P.simple_kmer_length <= 0 || P.max_bubble_length <= 0 || P.max_bubble_branches <= 0 ||
+		P.min_polish_aln_len <= 0)
+		throw FgError{FG_ERR_ARG, name + ": a length or cap <= 0"};
+	for (double r : {P.solid_missmatch, P.solid_indel, P.max_aln_error})
+		if (!(r >= 0.0)) throw FgError{FG_ERR_ARG, name + ": a rate that is NaN or negative"};
+	const long long S = P.simple_kmer_length, K = P.solid_kmer_length;
+	if (S % 2 || S < 2 || S > 2 * K || 3 * S / 2 > K + 1)
+		throw FgError{FG_ERR_UNSUPPORTED, name + ": simple_kmer_length " + std::to_string(S) + " with solid_kmer_length " +
+											  std::to_string(K) + " would slice outside the profile"};
+}
+
+// the call's last offsets and non-null pointers for empty arrays
+void bubClose(BubbleOwner* own)
+{
+	own->candOff.push_back(own->cand.size());
+	own->bubbleBranchOff.push_back(own->branchOff.size());
+	own->branchOff.push_back(own->branches.size());
+	for (auto* v : {&own->cand, &own->branches, &own->inProfile, &own->nucl})
+		if (v->empty()) v->reserve(1);
+	for (auto* v : {&own->position, &own->nLongBubbles, &own->nEmpty, &own->nLongBranch, &own->nPartition, &own->partition,
+					&own->coverage, &own->numInserts, &own->numDeletions, &own->numMissmatch})
+		if (v->empty()) v->reserve(1);
+	if (own->meanCov.empty()) own->meanCov.reserve(1);
+}
+
 } // namespace
 
 extern "C" {
@@ -813,17 +881,7 @@ int fg_make_bubbles(fg_ctx* c, const struct fg_bubble_params* params, uint32_t n
 		const std::string name = "fg_make_bubbles";
 		if (!params || !out) throw FgError{FG_ERR_ARG, name + ": null params or result"};
 		const fg_bubble_params& P = *params;
-		if (P.solid_kmer_length <= 0 || P.simple_kmer_length <= 0 || P.max_bubble_length <= 0 || P.max_bubble_branches <= 0 ||
-			P.min_polish_aln_len <= 0)
-			throw FgError{FG_ERR_ARG, name + ": a length or cap <= 0"};
-		for (double r : {P.solid_missmatch, P.solid_indel, P.max_aln_error})
-			if (!(r >= 0.0)) throw FgError{FG_ERR_ARG, name + ": a rate that is NaN or negative"};
-		{
-			const long long S = P.simple_kmer_length, K = P.solid_kmer_length;
-			if (S % 2 || S < 2 || S > 2 * K || 3 * S / 2 > K + 1)
-				throw FgError{FG_ERR_UNSUPPORTED, name + ": simple_kmer_length " + std::to_string(S) + " with solid_kmer_length " +
-													  std::to_string(K) + " would slice outside the profile"};
-		}
+		bubCheckParams(name, P);
 		if (n_contigs && (!contig_len || !contig_aln_off)) throw FgError{FG_ERR_ARG, name + ": null contig_len or contig_aln_off"};
 		for (u32 i = 0; i < n_contigs; ++i)
 		{
@@ -888,15 +946,7 @@ int fg_make_bubbles(fg_ctx* c, const struct fg_bubble_params* params, uint32_t n
 			i = j;
 		}
 		c->timer.collect();
-		own->candOff.push_back(own->cand.size());
-		own->bubbleBranchOff.push_back(own->branchOff.size());
-		own->branchOff.push_back(own->branches.size());
-		for (auto* v : {&own->cand, &own->branches, &own->inProfile, &own->nucl})
-			if (v->empty()) v->reserve(1);
-		for (auto* v : {&own->position, &own->nLongBubbles, &own->nEmpty, &own->nLongBranch, &own->nPartition, &own->partition,
-						&own->coverage, &own->numInserts, &own->numDeletions, &own->numMissmatch})
-			if (v->empty()) v->reserve(1);
-		if (own->meanCov.empty()) own->meanCov.reserve(1);
+		bubClose(own);
 	}
 	catch (const FgError& e) { c->lastError = e.msg; rc = e.code; }
 	catch (const std::bad_alloc&) { c->lastError = "host allocation failed"; rc = FG_ERR_NOMEM; }
@@ -909,34 +959,94 @@ int fg_make_bubbles(fg_ctx* c, const struct fg_bubble_params* params, uint32_t n
 		delete own;
 		return rc;
 	}
-	out->n_contigs = n_contigs;
-	out->n_bubbles = (uint32_t)own->position.size();
-	out->n_alignments = (uint64_t)own->inProfile.size();
-	out->bubble_off = own->bubbleOff.data();
-	out->position = own->position.data();
-	out->cand = own->cand.data();
-	out->cand_off = own->candOff.data();
-	out->branches = own->branches.data();
-	out->branch_off = own->branchOff.data();
-	out->bubble_branch_off = own->bubbleBranchOff.data();
-	out->n_long_bubbles = own->nLongBubbles.data();
-	out->n_empty = own->nEmpty.data();
-	out->n_long_branch = own->nLongBranch.data();
-	out->mean_cov = own->meanCov.data();
-	out->n_partition = own->nPartition.data();
-	out->in_profile = own->inProfile.data();
-	if (want_profile)
+	bubHandOver(out, own, n_contigs, want_profile != 0);
+	return FG_OK;
+}
+
+int fg_make_bubbles_cigars(fg_ctx* c, const struct fg_bubble_params* params, uint32_t n_contigs, const uint64_t* contig_off,
+						   const uint8_t* contig_seq, const uint8_t* contig_circular, const uint64_t* contig_aln_off, const int32_t* ctg_pos,
+						   const uint64_t* run_off, const uint8_t* run_op, const uint32_t* run_len, const uint64_t* read_off,
+						   const uint8_t* read_seq, const double* err_rate, uint8_t want_profile, struct fg_bubble_batch* out)
+{
+	if (!c) return FG_ERR_ARG;
+	if (out) memset(out, 0, sizeof(*out));
+	BubbleOwner* own = nullptr;
+	int rc = FG_OK;
+	try
 	{
-		out->part_off = own->partOff.data();
-		out->partition = own->partition.data();
-		out->prof_off = own->profOff.data();
-		out->coverage = own->coverage.data();
-		out->num_inserts = own->numInserts.data();
-		out->num_deletions = own->numDeletions.data();
-		out->num_missmatch = own->numMissmatch.data();
-		out->nucl = own->nucl.data();
+		const std::string name = "fg_make_bubbles_cigars";
+		if (!params || !out) throw FgError{FG_ERR_ARG, name + ": null params or result"};
+		const fg_bubble_params& P = *params;
+		bubCheckParams(name, P);
+		if (n_contigs && !contig_aln_off) throw FgError{FG_ERR_ARG, name + ": null contig_aln_off"};
+		for (u32 i = 0; i < n_contigs; ++i)
+			if (contig_aln_off[i + 1] < contig_aln_off[i])
+				throw FgError{FG_ERR_ARG, name + ": contig_aln_off decreases at contig " + std::to_string(i)};
+		const u64 a0 = n_contigs ? contig_aln_off[0] : 0, a1 = n_contigs ? contig_aln_off[n_contigs] : 0;
+		std::vector<uint32_t> alnContig((size_t)a1, 0);
+		for (u32 i = 0; i < n_contigs; ++i)
+			for (u64 a = contig_aln_off[i]; a < contig_aln_off[i + 1]; ++a) alnContig[a] = i;
+		// every check of fg_expand_cigars, then those fg_make_bubbles makes on what the expansion would hand it
+		CigPlan plan;
+		cigCheckRecords(name, n_contigs, contig_off, contig_seq, a0, a1, alnContig.data(), !ctg_pos || !run_off || !read_off || !err_rate,
+						"null ctg_pos, run_off, read_off or err_rate", ctg_pos, run_off, run_op, run_len, read_off, read_seq, plan);
+		for (u64 a = a0; a < a1; ++a)
+			if (!(err_rate[a] >= 0.0)) throw FgError{FG_ERR_ARG, name + ": err_rate NaN or negative at alignment " + std::to_string(a)};
+		own = new BubbleOwner;
+		own->inProfile.assign((size_t)(a1 - a0), 0);
+		std::vector<int32_t> contigLen(n_contigs, 0);
+		std::vector<u64> cost(n_contigs, 0);
+		for (u32 i = 0; i < n_contigs; ++i)
+		{
+			if (contig_off[i + 1] - contig_off[i] > CIG_I32) throw FgError{FG_ERR_ARG, name + ": contig " + std::to_string(i) + " has 2^31 bytes"};
+			contigLen[i] = (int32_t)(contig_off[i + 1] - contig_off[i]);
+			for (u64 a = contig_aln_off[i]; a < contig_aln_off[i + 1]; ++a)
+			{
+				// an alignment of insertions alone may stand behind the last base
+				if (plan.trgStart[a] >= contigLen[i])
+					throw FgError{FG_ERR_ARG, name + ": trg_start outside the contig at alignment " + std::to_string(a)};
+				own->inProfile[a - a0] = !(err_rate[a] > P.max_aln_error) && plan.tot[a].cols >= (u64)P.min_polish_aln_len;
+			}
+			// a contig counts its columns and its positions
+			cost[i] = (u64)contigLen[i] + (plan.colOff[contig_aln_off[i + 1]] - plan.colOff[contig_aln_off[i]]);
+		}
+		u64 budget = 1ULL << 27;
+		if (const char* e = getenv("FG_BUBBLE_BATCH_COLS")) budget = strtoull(e, nullptr, 10);
+		u64 maxContigs = ~0ULL;			// a switch for tests: contigs per sub-batch
+		if (const char* e = getenv("FG_BUBBLE_BATCH_CONTIGS")) maxContigs = std::max<u64>(1, strtoull(e, nullptr, 10));
+		own->bubbleOff.assign(1, 0);
+		if (want_profile) { own->partOff.assign(1, 0); own->profOff.assign(1, 0); }
+		HIP_CHECK(hipSetDevice(c->device));
+		c->timer.reset();
+		for (u32 i = 0; i < n_contigs; ++i)
+			if (cost[i] > budget)
+				throw FgError{FG_ERR_NOMEM, name + ": contig " + std::to_string(i) + " alone has " + std::to_string(cost[i]) +
+												" columns and positions, FG_BUBBLE_BATCH_COLS is " + std::to_string(budget)};
+		// the contig bytes go up once per call; a sub-batch expands its own alignments
+		const CigSource src{&plan, a1 > a0 ? cigUploadContigs(c, plan, contig_seq) : nullptr, run_off, run_op, run_len, read_off, read_seq, cigTile()};
+		u32 i = 0;
+		while (i < n_contigs)
+		{
+			const u32 j = cigCutContigs(name, "FG_BUBBLE_BATCH_COLS", i, n_contigs, cost, budget, maxContigs, contig_aln_off, run_off, read_off);
+			bubSubBatch(c, P, i, j, contigLen.data(), contig_circular, contig_aln_off, plan.trgStart.data(), plan.trgEnd.data(),
+						plan.colOff.data(), nullptr, nullptr, own->inProfile.data(), a0, want_profile != 0, *own, &src);
+			i = j;
+		}
+		c->timer.collect();
+		bubClose(own);
 	}
-	out->owner_ = own;
+	catch (const FgError& e) { c->lastError = e.msg; rc = e.code; }
+	catch (const std::bad_alloc&) { c->lastError = "host allocation failed"; rc = FG_ERR_NOMEM; }
+	catch (const std::exception& e) { c->lastError = e.what(); rc = FG_ERR_HIP; }
+	if (rc != FG_OK)
+	{
+		// launches of a call that failed half way drain before the context's scratch is used again
+		if (c->stream) (void)hipStreamSynchronize(c->stream);
+		c->timer.reset();
+		delete own;
+		return rc;
+	}
+	bubHandOver(out, own, n_contigs, want_profile != 0);
 	return FG_OK;
 }
 

@@ -34,9 +34,16 @@
 //   k_cc_flatten    one thread per position: match_total, max_match (the first rank of the largest count), the accepted
 //                   flag and the bytes the position gives; a scan places them; k_cc_write writes them.
 // The host does work proportional to contigs, alignments and (for the byte check) columns.
+//
+// fg_contig_consensus_cigars takes SAM records where fg_contig_consensus takes columns: a sub-batch expands its own
+// alignments (fg_cigexpand.h) on the context's stream straight into the two column buffers, so no column crosses the bus.
+// The one thing the host read from the columns besides checks, the set of query bytes present, comes from
+//   k_col_present   one wave per alignment in use: a 128-bit mask of its query bytes, ORed over the wave, one atomic per
+//                   wave and word onto four words that the host reads before it sizes the match table.
 #include "fg_ctx.h"
 #include "fg_devprim.h"
 #include "fg_gapshift.h"
+#include "fg_cigexpand.h"
 #include <cmath>
 
 namespace {
@@ -330,6 +337,48 @@ k_cc_pick(u32 n, const u64* __restrict__ at, const u32* __restrict__ off, u32* _
 	if (i < n) out[i] = off[at[i]];
 }
 
+// present[0 .. 4) |= the set of bytes (below 128) among the query columns of the alignments with inProfile set: bit b of
+// the 128 stands for byte b.  One wave per alignment.  A lane takes whole 8-byte words where the address allows (the
+// alignment's first bytes up to the next word boundary and its last bytes go one per lane), ORs into four registers, the
+// wave folds them by a butterfly and lane 0 issues one atomic per word that has a bit.
+__global__ void __launch_bounds__(BUB_BLOCK)
+k_col_present(const BubAln* __restrict__ alns, u32 nAln, const unsigned char* __restrict__ qry, u32* present)
+{
+	const int lane = threadIdx.x & 63;
+	const u32 a = blockIdx.x * BUB_WAVES + (threadIdx.x >> 6);
+	if (a >= nAln) return;
+	const BubAln al = alns[a];
+	if (!al.inProfile) return;
+	const unsigned char* q = qry + al.colOff;
+	const u64 n = al.nCols;
+	u32 m[4] = {0u, 0u, 0u, 0u};
+	const auto mark = [&m](u32 b)
+	{
+		const u32 bit = 1u << (b & 31u), w = (b >> 5) & 3u;
+		m[0] |= w == 0 ? bit : 0u; m[1] |= w == 1 ? bit : 0u; m[2] |= w == 2 ? bit : 0u; m[3] |= w == 3 ? bit : 0u;
+	};
+	const u64 toBoundary = (8 - ((uintptr_t)q & 7)) & 7;
+	const u64 head = toBoundary < n ? toBoundary : n;
+	const u64 nWords = (n - head) / 8, tail0 = head + 8 * nWords;
+	if ((u64)lane < head) mark(q[lane]);
+	const u64* qw = (const u64*)(q + head);
+	for (u64 w = lane; w < nWords; w += 64)
+	{
+		const u64 v = qw[w];
+#pragma unroll
+		for (int i = 0; i < 8; ++i) mark((u32)(v >> (8 * i)) & 0xffu);
+	}
+	if (tail0 + (u64)lane < n) mark(q[tail0 + lane]);
+#pragma unroll
+	for (int k = 0; k < 4; ++k)
+	{
+		u32 v = m[k];
+#pragma unroll
+		for (int sh = 32; sh > 0; sh >>= 1) v |= __shfl_xor(v, sh);
+		if (lane == 0 && v) atomicOr(&present[k], v);
+	}
+}
+
 struct CcBufs {
 	fg_ctx* c;
 	int next = 0;
@@ -463,7 +512,7 @@ void uniSubBatch(fg_ctx* c, u32 c0, u32 c1, const int32_t* contigLen, const uint
 
 void ccSubBatch(fg_ctx* c, u32 c0, u32 c1, const int32_t* contigLen, const uint64_t* contigAlnOff, const int32_t* trgStart,
 				const int32_t* qryId, const uint8_t* use, const uint64_t* colOff, const uint8_t* trgCols, const uint8_t* qryCols,
-				bool wantProfile, ConsensusOwner& own)
+				bool wantProfile, ConsensusOwner& own, const CigSource* cig = nullptr /* the columns are expanded here, not read from the host */)
 {
 	hipStream_t s = c->stream;
 	const u32 nC = c1 - c0;
@@ -488,13 +537,40 @@ void ccSubBatch(fg_ctx* c, u32 c0, u32 c1, const int32_t* contigLen, const uint6
 			al.colOff = colOff[a] - col0; al.nCols = (u32)(colOff[a + 1] - colOff[a]);
 			al.trgStart = trgStart[a]; al.trgEnd = 0; al.contig = i; al.inProfile = !use || use[a] ? 1u : 0u; al.pad = 0;
 			qid[a - a0] = (u32)qryId[a];
-			if (al.inProfile)
+			if (al.inProfile && !cig)
 				for (u64 k = colOff[a]; k < colOff[a + 1]; ++k) present[qryCols[k]] = true;
 		}
 	}
 	ctgAt[nC] = nPos;
 	if (nPos >= (1ULL << 31) || nAln >= (1u << 23) || nCols >= (1ULL << 31))
 		throw FgError{FG_ERR_NOMEM, "fg_contig_consensus: a sub-batch of 2^31 positions or columns or 2^23 alignments; lower FG_CONSENSUS_BATCH_COLS"};
+	CcBufs B{c};
+	BubAln* dAln = B.get<BubAln>(nAln);
+	CcContig* dCtg = B.get<CcContig>(nC);
+	u32* dQid = B.get<u32>(nAln);
+	// k_cig_expand stores whole words past the last column
+	unsigned char* dTrg = B.get<unsigned char>(nCols + (cig ? CIG_LANE_COLS : 0));
+	unsigned char* dQry = B.get<unsigned char>(nCols + (cig ? CIG_LANE_COLS : 0));
+	unsigned char* dTrgS = B.get<unsigned char>(nCols);
+	unsigned char* dQryS = B.get<unsigned char>(nCols);
+	unsigned char* dTab = B.get<unsigned char>(256);
+	CigStaged staged;
+	if (cig && nAln)
+	{
+		HIP_CHECK(hipMemcpyAsync(dAln, alns.data(), (size_t)nAln * sizeof(BubAln), hipMemcpyHostToDevice, s));
+		CigBufs CB = cigExpandSource(c, *cig, staged, a0, a1, dTrg, dQry);
+		u32* dPresent = CB.get<u32>(4);
+		HIP_CHECK(hipMemsetAsync(dPresent, 0, 16, s));
+		{
+			ScopedK t(c->timer, "k_col_present");
+			hipLaunchKernelGGL(k_col_present, bubWaveGrid(nAln), BUB_BLOCK, 0, s, dAln, nAln, dQry, dPresent);
+		}
+		HIP_CHECK(hipGetLastError());
+		u32 mask[4] = {};
+		HIP_CHECK(hipMemcpyAsync(mask, dPresent, 16, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(hipStreamSynchronize(s));
+		for (int b = 0; b < 128; ++b) present[b] = (mask[b >> 5] >> (b & 31)) & 1u;
+	}
 	// the bytes present, ranked in byte order
 	unsigned char rank[128] = {}, byteOf[128] = {};
 	u32 nB = 0;
@@ -505,15 +581,6 @@ void ccSubBatch(fg_ctx* c, u32 c0, u32 c1, const int32_t* contigLen, const uint6
 		throw FgError{FG_ERR_NOMEM, "fg_contig_consensus: the match table of a sub-batch has 2^32 cells (" + std::to_string(nB) +
 										" distinct bytes); lower FG_CONSENSUS_BATCH_COLS"};
 
-	CcBufs B{c};
-	BubAln* dAln = B.get<BubAln>(nAln);
-	CcContig* dCtg = B.get<CcContig>(nC);
-	u32* dQid = B.get<u32>(nAln);
-	unsigned char* dTrg = B.get<unsigned char>(nCols);
-	unsigned char* dQry = B.get<unsigned char>(nCols);
-	unsigned char* dTrgS = B.get<unsigned char>(nCols);
-	unsigned char* dQryS = B.get<unsigned char>(nCols);
-	unsigned char* dTab = B.get<unsigned char>(256);
 	u32* dMatches = B.get<u32>(nPos * nB);
 	unsigned long long* dTag = B.get<unsigned long long>(nPos);
 	u32* dRecOff = B.get<u32>((size_t)nAln + 1);
@@ -529,11 +596,11 @@ void ccSubBatch(fg_ctx* c, u32 c0, u32 c1, const int32_t* contigLen, const uint6
 	i32* dNumIns = (i32*)(dPos32 + 2 * nPos);
 	unsigned char *dNucl = dBytes, *dMaxMatch = dBytes + nPos, *dAccepted = dBytes + 2 * nPos;
 
-	HIP_CHECK(hipMemcpyAsync(dAln, alns.data(), (size_t)nAln * sizeof(BubAln), hipMemcpyHostToDevice, s));
+	if (!cig) HIP_CHECK(hipMemcpyAsync(dAln, alns.data(), (size_t)nAln * sizeof(BubAln), hipMemcpyHostToDevice, s));
 	HIP_CHECK(hipMemcpyAsync(dCtg, ctg.data(), (size_t)nC * sizeof(CcContig), hipMemcpyHostToDevice, s));
 	HIP_CHECK(hipMemcpyAsync(dQid, qid.data(), (size_t)nAln * 4, hipMemcpyHostToDevice, s));
 	HIP_CHECK(hipMemcpyAsync(dCtgAt, ctgAt.data(), ((size_t)nC + 1) * 8, hipMemcpyHostToDevice, s));
-	if (nCols)
+	if (nCols && !cig)
 	{
 		HIP_CHECK(hipMemcpyAsync(dTrg, trgCols + col0, nCols, hipMemcpyHostToDevice, s));
 		HIP_CHECK(hipMemcpyAsync(dQry, qryCols + col0, nCols, hipMemcpyHostToDevice, s));
@@ -661,6 +728,26 @@ u64 envU64(const char* name, u64 dflt)
 {
 	const char* e = getenv(name);
 	return e ? strtoull(e, nullptr, 10) : dflt;
+}
+
+// the finished owner into the caller's struct
+void ccHandOver(struct fg_consensus_batch* out, ConsensusOwner* own, uint32_t n_contigs, bool wantProfile)
+{
+	out->n_contigs = n_contigs;
+	out->seq_off = own->seqOff.data();
+	out->seq = own->seq.data();
+	if (wantProfile)
+	{
+		out->prof_off = own->profOff.data();
+		out->nucl = own->nucl.data();
+		out->match_total = own->matchTotal.data();
+		out->num_ins = own->numIns.data();
+		out->max_match = own->maxMatch.data();
+		out->accepted = own->accepted.data();
+		out->ins_off = own->insOff.data();
+		out->ins = own->ins.data();
+	}
+	out->owner_ = own;
 }
 
 } // namespace
@@ -848,21 +935,93 @@ int fg_contig_consensus(fg_ctx* c, uint32_t n_contigs, const int32_t* contig_len
 		delete own;
 		return rc;
 	}
-	out->n_contigs = n_contigs;
-	out->seq_off = own->seqOff.data();
-	out->seq = own->seq.data();
-	if (want_profile)
+	ccHandOver(out, own, n_contigs, want_profile != 0);
+	return FG_OK;
+}
+
+int fg_contig_consensus_cigars(fg_ctx* c, uint32_t n_contigs, const uint64_t* contig_off, const uint8_t* contig_seq,
+							   const uint64_t* contig_aln_off, const int32_t* ctg_pos, const uint64_t* run_off, const uint8_t* run_op,
+							   const uint32_t* run_len, const uint64_t* read_off, const uint8_t* read_seq, const int32_t* qry_id,
+							   const uint8_t* use, uint8_t want_profile, struct fg_consensus_batch* out)
+{
+	if (!c) return FG_ERR_ARG;
+	if (out) memset(out, 0, sizeof(*out));
+	ConsensusOwner* own = nullptr;
+	int rc = FG_OK;
+	try
 	{
-		out->prof_off = own->profOff.data();
-		out->nucl = own->nucl.data();
-		out->match_total = own->matchTotal.data();
-		out->num_ins = own->numIns.data();
-		out->max_match = own->maxMatch.data();
-		out->accepted = own->accepted.data();
-		out->ins_off = own->insOff.data();
-		out->ins = own->ins.data();
+		const std::string name = "fg_contig_consensus_cigars";
+		if (!out) throw FgError{FG_ERR_ARG, name + ": null result"};
+		if (n_contigs && !contig_aln_off) throw FgError{FG_ERR_ARG, name + ": null contig_aln_off"};
+		for (u32 i = 0; i < n_contigs; ++i)
+			if (contig_aln_off[i + 1] < contig_aln_off[i])
+				throw FgError{FG_ERR_ARG, name + ": contig_aln_off decreases at contig " + std::to_string(i)};
+		const u64 a0 = n_contigs ? contig_aln_off[0] : 0, a1 = n_contigs ? contig_aln_off[n_contigs] : 0;
+		std::vector<uint32_t> alnContig((size_t)a1, 0);
+		for (u32 i = 0; i < n_contigs; ++i)
+			for (u64 a = contig_aln_off[i]; a < contig_aln_off[i + 1]; ++a) alnContig[a] = i;
+		// every check of fg_expand_cigars, then those fg_contig_consensus makes on what the expansion would hand it
+		CigPlan plan;
+		cigCheckRecords(name, n_contigs, contig_off, contig_seq, a0, a1, alnContig.data(), !ctg_pos || !run_off || !read_off || !qry_id,
+						"null ctg_pos, run_off, read_off or qry_id", ctg_pos, run_off, run_op, run_len, read_off, read_seq, plan);
+		std::vector<int32_t> contigLen(n_contigs, 0);
+		std::vector<u64> cost(n_contigs, 0);
+		for (u32 i = 0; i < n_contigs; ++i)
+		{
+			if (contig_off[i + 1] - contig_off[i] > CIG_I32) throw FgError{FG_ERR_ARG, name + ": contig " + std::to_string(i) + " has 2^31 bytes"};
+			contigLen[i] = (int32_t)(contig_off[i + 1] - contig_off[i]);
+			for (u64 a = contig_aln_off[i]; a < contig_aln_off[i + 1]; ++a)
+			{
+				if (use && !use[a]) continue;		// the positions of an alignment that takes no part are not looked at
+				if (contigLen[i] == 0)
+					throw FgError{FG_ERR_ARG, name + ": alignment " + std::to_string(a) + " is in use on a contig of length 0"};
+				// an alignment of insertions alone may stand behind the last base
+				if (plan.trgStart[a] >= contigLen[i])
+					throw FgError{FG_ERR_ARG, name + ": trg_start outside the contig at alignment " + std::to_string(a)};
+			}
+			// a contig counts its columns and its positions
+			cost[i] = (u64)contigLen[i] + (plan.colOff[contig_aln_off[i + 1]] - plan.colOff[contig_aln_off[i]]);
+		}
+		const u64 budget = envU64("FG_CONSENSUS_BATCH_COLS", 1ULL << 27);
+		u64 maxContigs = ~0ULL;			// a switch for tests: contigs per sub-batch
+		if (getenv("FG_CONSENSUS_BATCH_CONTIGS")) maxContigs = std::max<u64>(1, envU64("FG_CONSENSUS_BATCH_CONTIGS", 1));
+		for (u32 i = 0; i < n_contigs; ++i)
+			if (cost[i] > budget)
+				throw FgError{FG_ERR_NOMEM, name + ": contig " + std::to_string(i) + " alone has " + std::to_string(cost[i]) +
+												" columns and positions, FG_CONSENSUS_BATCH_COLS is " + std::to_string(budget)};
+		own = new ConsensusOwner;
+		own->seqOff.assign(1, 0);
+		if (want_profile) { own->profOff.assign(1, 0); own->insOff.assign(1, 0); }
+		HIP_CHECK(hipSetDevice(c->device));
+		c->timer.reset();
+		// the contig bytes go up once per call; a sub-batch expands its own alignments
+		const CigSource src{&plan, a1 > a0 ? cigUploadContigs(c, plan, contig_seq) : nullptr, run_off, run_op, run_len, read_off, read_seq, cigTile()};
+		u32 i = 0;
+		while (i < n_contigs)
+		{
+			const u32 j = cigCutContigs(name, "FG_CONSENSUS_BATCH_COLS", i, n_contigs, cost, budget, maxContigs, contig_aln_off, run_off, read_off);
+			ccSubBatch(c, i, j, contigLen.data(), contig_aln_off, plan.trgStart.data(), qry_id, use, plan.colOff.data(), nullptr, nullptr,
+					   want_profile != 0, *own, &src);
+			i = j;
+		}
+		c->timer.collect();
+		for (auto* v : {&own->seq, &own->nucl, &own->maxMatch, &own->accepted, &own->ins})
+			if (v->empty()) v->reserve(1);
+		for (auto* v : {&own->matchTotal, &own->numIns})
+			if (v->empty()) v->reserve(1);
 	}
-	out->owner_ = own;
+	catch (const FgError& e) { c->lastError = e.msg; rc = e.code; }
+	catch (const std::bad_alloc&) { c->lastError = "host allocation failed"; rc = FG_ERR_NOMEM; }
+	catch (const std::exception& e) { c->lastError = e.what(); rc = FG_ERR_HIP; }
+	if (rc != FG_OK)
+	{
+		// launches of a call that failed half way drain before the context's scratch is used again
+		if (c->stream) (void)hipStreamSynchronize(c->stream);
+		c->timer.reset();
+		delete own;
+		return rc;
+	}
+	ccHandOver(out, own, n_contigs, want_profile != 0);
 	return FG_OK;
 }
 

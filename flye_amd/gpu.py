@@ -19,7 +19,9 @@ like calls into the reference:
 * ``ContigConsensus(ctx).consensus(contigs, alignments_by_contig)``  (flye/polishing/consensus.py:52-181, get_consensus
   without the SAM reader and the FASTA writer)
 * ``SamAlignments(ctx, sam_path, contigs, max_coverage, use_secondary).chunks() / by_contig()``
-  (flye/utils/sam_parser.py:123-404, SynchronizedSamReader: get_chunk on fg_expand_cigars)
+  (flye/utils/sam_parser.py:123-404, SynchronizedSamReader: get_chunk on fg_expand_cigars); with ``want_cols=False`` it
+  keeps runs and SEQ in place of the gapped strings, for ``ContigConsensus.consensus_sam`` and ``BubbleMaker.make_sam`` /
+  ``polish_sam`` (fg_contig_consensus_cigars / fg_make_bubbles_cigars: the columns are made and stay on the device)
 * ``DivergenceFinder(ctx).find_divergence(alignment_path, contigs_path, contigs_info, frequency_path, positions_path,
   div_sum_path, sub_thresh, del_thresh, ins_thresh)`` / ``profile``  (flye/trestle/divergence.py:55-232, on
   fg_divergence_profile)
@@ -66,7 +68,8 @@ ABI_SYMBOLS = ["fg_abi_version", "fg_create", "fg_destroy", "fg_strerror", "fg_l
                "fg_edge_coverage", "fg_release_edge_coverage",
                "fg_subs_matrix_load", "fg_polish_bubbles", "fg_release_polish", "fg_make_bubbles", "fg_release_bubbles",
                "fg_uniform_alignments", "fg_release_uniform", "fg_contig_consensus", "fg_release_consensus",
-               "fg_expand_cigars", "fg_release_expand", "fg_cigar_parse", "fg_divergence_profile", "fg_release_divergence",
+               "fg_expand_cigars", "fg_release_expand", "fg_cigar_parse", "fg_contig_consensus_cigars", "fg_make_bubbles_cigars",
+               "fg_divergence_profile", "fg_release_divergence",
                "fg_confirm_positions", "fg_release_confirm", "fg_classify_reads", "fg_release_classify",
                "fg_index_keep_targets", "fg_index_shard", "fg_probe_hits", "fg_overlaps_from_hits",
                "fg_index_piece_split", "fg_index_scatter_begin", "fg_index_scatter_end", "fg_debug_probe_skip_check",
@@ -423,6 +426,9 @@ def load_library():
             [C.c_uint8, C.POINTER(ExpandBatch)]
         L.fg_release_expand.argtypes = [C.POINTER(ExpandBatch)]
         L.fg_release_expand.restype = None
+        L.fg_contig_consensus_cigars.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 11 + [C.c_uint8, C.POINTER(ConsensusBatch)]
+        L.fg_make_bubbles_cigars.argtypes = [C.c_void_p, C.POINTER(BubbleParams), C.c_uint32] + [C.c_void_p] * 11 + \
+            [C.c_uint8, C.POINTER(BubbleBatch)]
         L.fg_cigar_parse.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         L.fg_divergence_profile.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_uint32] + [C.c_void_p] * 6 + \
             [C.c_uint8, C.POINTER(DivergenceBatch)]
@@ -1208,6 +1214,10 @@ class Context:
                                            ptr(co), ptr(tc), ptr(qc), int(bool(want_profile)), C.byref(b)))
         self.last_bubbles_seconds = time.perf_counter() - t0
 
+        return self._bubble_result(b, n, want_profile)
+
+    def _bubble_result(self, b, n, want_profile):
+        """the arrays of a struct fg_bubble_batch as a BubbleResult; releases the batch"""
         def take(p, k, dtype):
             return np.ctypeslib.as_array(p, (k,)).copy() if k else np.zeros(0, dtype)
 
@@ -1286,6 +1296,10 @@ class Context:
                                                ptr(qc), int(bool(want_profile)), C.byref(b)))
         self.last_consensus_seconds = time.perf_counter() - t0
 
+        return self._consensus_result(b, n, want_profile)
+
+    def _consensus_result(self, b, n, want_profile):
+        """the arrays of a struct fg_consensus_batch as a ConsensusResult; releases the batch"""
         def take(p, k, dtype):
             return np.ctypeslib.as_array(p, (k,)).copy() if k else np.zeros(0, dtype)
 
@@ -1441,6 +1455,63 @@ class Context:
         out["matches"], out["err_rate"] = take(b.matches, n, np.int64), take(b.err_rate, n, np.float64)
         self.L.fg_release_expand(C.byref(b))
         return ExpandResult(**out)
+
+    @staticmethod
+    def _record_arrays(name, contig_off, contig_seq, contig_aln_off, ctg_pos, run_off, run_op, run_len, read_off, read_seq):
+        """the record arguments the two fused calls share, as contiguous arrays of the C types, checked against their
+        offsets"""
+        as_bytes = lambda x: np.ascontiguousarray(x, np.uint8) if isinstance(x, np.ndarray) else np.frombuffer(bytes(x), np.uint8)
+        cto, cao = np.ascontiguousarray(contig_off, np.uint64), np.ascontiguousarray(contig_aln_off, np.uint64)
+        cs, rop, rs = as_bytes(contig_seq), as_bytes(run_op), as_bytes(read_seq)
+        cp = np.ascontiguousarray(ctg_pos, np.int32)
+        ro, rdo = np.ascontiguousarray(run_off, np.uint64), np.ascontiguousarray(read_off, np.uint64)
+        rl = np.ascontiguousarray(run_len, np.uint32)
+        n, na = len(cto) - 1, len(cp)
+        if n < 0 or len(cao) != n + 1 or int(cao.max()) > na or len(ro) != na + 1 or len(rdo) != na + 1 or len(rop) != len(rl) or \
+                int(cto.max()) > len(cs) or int(ro.max()) > len(rl) or int(rdo.max()) > len(rs):
+            raise ValueError(name + ": offsets outside their arrays")
+        return n, na, (cto, cs, cao, cp, ro, rop, rl, rdo, rs)
+
+    def contig_consensus_cigars(self, contig_off, contig_seq, contig_aln_off, ctg_pos, run_off, run_op, run_len, read_off,
+                                read_seq, qry_id, use=None, want_profile=False):
+        """fg_contig_consensus_cigars: expand_cigars and contig_consensus as one call, the columns never leaving the
+        device.  The contigs and records are given as for expand_cigars, but grouped by contig (contig i has the
+        alignments contig_aln_off[i] .. contig_aln_off[i + 1]); qry_id and use as for contig_consensus.  Returns a
+        ConsensusResult equal to the two calls'."""
+        n, na, arrs = self._record_arrays("contig_consensus_cigars", contig_off, contig_seq, contig_aln_off, ctg_pos, run_off,
+                                          run_op, run_len, read_off, read_seq)
+        qi = np.ascontiguousarray(qry_id, np.int32)
+        us = np.ascontiguousarray(use, np.uint8) if use is not None else None
+        if len(qi) != na or (us is not None and len(us) != na):
+            raise ValueError("contig_consensus_cigars: offsets outside their arrays")
+        # an offset array is never empty; the others go as NULL when they are
+        ptr = lambda a: a.ctypes.data if a is not None and len(a) else None
+        b = ConsensusBatch()
+        t0 = time.perf_counter()
+        self._check(self.L.fg_contig_consensus_cigars(self.h, n, *[ptr(a) for a in arrs], ptr(qi), ptr(us), int(bool(want_profile)),
+                                                      C.byref(b)))
+        self.last_consensus_seconds = time.perf_counter() - t0
+        return self._consensus_result(b, n, want_profile)
+
+    def make_bubbles_cigars(self, params, contig_off, contig_seq, contig_circular, contig_aln_off, ctg_pos, run_off, run_op,
+                            run_len, read_off, read_seq, err_rate, want_profile=False):
+        """fg_make_bubbles_cigars: expand_cigars and make_bubbles as one call, the columns never leaving the device.  The
+        contigs and records as for contig_consensus_cigars; err_rate per alignment comes from an earlier
+        expand_cigars(want_cols=False).  Returns a BubbleResult equal to the two calls'."""
+        n, na, arrs = self._record_arrays("make_bubbles_cigars", contig_off, contig_seq, contig_aln_off, ctg_pos, run_off, run_op,
+                                          run_len, read_off, read_seq)
+        cc = np.ascontiguousarray(contig_circular, np.uint8) if contig_circular is not None else np.zeros(n, np.uint8)
+        er = np.ascontiguousarray(err_rate, np.float64)
+        if len(cc) != n or len(er) != na:
+            raise ValueError("make_bubbles_cigars: offsets outside their arrays")
+        ptr = lambda a: a.ctypes.data if len(a) else None
+        cto, cs, cao = arrs[:3]
+        b = BubbleBatch()
+        t0 = time.perf_counter()
+        self._check(self.L.fg_make_bubbles_cigars(self.h, C.byref(params), n, ptr(cto), ptr(cs), ptr(cc), ptr(cao),
+                                                  *[ptr(a) for a in arrs[3:]], ptr(er), int(bool(want_profile)), C.byref(b)))
+        self.last_bubbles_seconds = time.perf_counter() - t0
+        return self._bubble_result(b, n, want_profile)
 
     def edge_coverage(self, window, recs, aln, aln_off, first_ext_id, edge_of, edge_len, want_vectors=True):
         """fg_edge_coverage: the window coverage of MultiplicityInferer::estimateCoverage (multiplicity_inferer.cpp:
@@ -2366,6 +2437,9 @@ class BubbleMaker:
                                     np.cumsum([0] + [len(alignments_by_contig.get(c.id, [])) for c in contigs]),
                                     [a.trg_start for a in alns], [a.trg_end for a in alns], [a.err_rate for a in alns],
                                     np.cumsum([0] + [len(a.trg_seq) for a in alns]), trg, qry, want_profile)
+        return self._finish(contigs, alns, res)
+
+    def _finish(self, contigs, alns, res):
         self.contigs, self.result = list(contigs), res
         self.bubbles = [(c.id,) + b for i, c in enumerate(contigs) for b in res.bubbles(i)]
         self.aln_errors = [a.err_rate for a, f in zip(alns, res.in_profile) if f]
@@ -2383,14 +2457,40 @@ class BubbleMaker:
                 for k, w in enumerate(branches):
                     f.write(b">%d\n%s\n" % (k, w))
 
+    def make_sam(self, contigs, sam, err_mode, want_profile=False, uniform=True):
+        """make() for a SamAlignments made with want_cols=False: fg_uniform_alignments (the reference's make_bubbles
+        starts with get_uniform_alignments), then ONE fg_make_bubbles_cigars on the records it keeps, which expands their
+        CIGARs on the device straight into the bubble kernels' buffers.  Returns what make() returns for
+        sam.by_contig() with every list put through uniform_alignments_device first (uniform=False: for the lists as
+        they are); err_rate is the one the want_cols=False expansion counted."""
+        params = BubbleParams.for_mode(err_mode, **self.overrides)
+        keep = None
+        if uniform:
+            alns, rec = sam.flatten(contigs)
+            keep = self.ctx.uniform_alignments(np.diff(rec["contig_off"]), rec["contig_aln_off"], [a.trg_start for a in alns],
+                                               [a.trg_end for a in alns], [a.err_rate for a in alns],
+                                               [bool(a.is_secondary) for a in alns]).keep
+        alns, rec = sam.flatten(contigs, keep)
+        res = self.ctx.make_bubbles_cigars(params, contig_circular=[c.type == "circular" for c in contigs],
+                                           err_rate=[a.err_rate for a in alns], want_profile=want_profile, **rec)
+        return self._finish(contigs, alns, res)
+
+    def polish_sam(self, contigs, sam, err_mode, matrix, fix_dinucleotides=True, want_steps=False, uniform=True):
+        """polish() on make_sam(): the fused call, then Context.polish_bubbles"""
+        bubbles, _, _ = self.make_sam(contigs, sam, err_mode, uniform=uniform)
+        return bubbles, self._polish_result(matrix, fix_dinucleotides, want_steps)
+
     def polish(self, contigs, alignments_by_contig, err_mode, matrix, fix_dinucleotides=True, want_steps=False):
         """the two device stages as one call: make() -> upper case (the polisher's reader does that, bubble_processor.cpp:
         151-204) -> Context.polish_bubbles.  Returns (bubbles, PolishResult); the branch bytes go back as they came."""
         bubbles, _, _ = self.make(contigs, alignments_by_contig, err_mode)
+        return bubbles, self._polish_result(matrix, fix_dinucleotides, want_steps)
+
+    def _polish_result(self, matrix, fix_dinucleotides, want_steps):
         r = self.result
         upper = lambda a: np.frombuffer(a.tobytes().upper(), np.uint8)
-        return bubbles, self.ctx.polish_bubbles(matrix, upper(r.cand), r.cand_off, upper(r.branches), r.branch_off,
-                                                r.bubble_branch_off, fix_dinucleotides, want_steps)
+        return self.ctx.polish_bubbles(matrix, upper(r.cand), r.cand_off, upper(r.branches), r.branch_off,
+                                       r.bubble_branch_off, fix_dinucleotides, want_steps)
 
 
 class ContigConsensus:
@@ -2424,6 +2524,9 @@ class ContigConsensus:
         res = self.ctx.contig_consensus(lengths, aln_off, starts, qry_id, np.cumsum([0] + [len(a.trg_seq) for a in alns]),
                                         "".join(a.trg_seq for a in alns).encode("latin-1"),
                                         "".join(a.qry_seq for a in alns).encode("latin-1"), use, want_profile)
+        return self._finish(contigs, alns, use, res)
+
+    def _finish(self, contigs, alns, use, res):
         self.result = res
         self.aln_errors = [a.err_rate for k, a in enumerate(alns) if use is None or use[k]]
         total = 0.0
@@ -2435,6 +2538,25 @@ class ContigConsensus:
             if len(seq) > 0:
                 out[c.id] = seq.decode("latin-1")
         return out, total / (len(self.aln_errors) + 1)
+
+    def consensus_sam(self, contigs, sam, uniform=True, want_profile=False):
+        """consensus(contigs, sam.by_contig(), ...) for a SamAlignments made with want_cols=False: one
+        fg_uniform_alignments and one fg_contig_consensus_cigars, which expands the CIGARs on the device straight into
+        the consensus kernels' buffers.  No gapped string exists on the host at any point."""
+        alns, rec = sam.flatten(contigs)
+        aln_off = rec["contig_aln_off"]
+        qry_id = []
+        for i in range(len(contigs)):
+            number = {}
+            qry_id += [number.setdefault(a.qry_id, len(number)) for a in alns[int(aln_off[i]):int(aln_off[i + 1])]]
+        use = None
+        if uniform:
+            self.uniform = self.ctx.uniform_alignments(np.diff(rec["contig_off"]), aln_off, [a.trg_start for a in alns],
+                                                       [a.trg_end for a in alns], [a.err_rate for a in alns],
+                                                       [bool(a.is_secondary) for a in alns])
+            use = self.uniform.keep
+        return self._finish(contigs, alns, use, self.ctx.contig_consensus_cigars(qry_id=qry_id, use=use, want_profile=want_profile,
+                                                                                 **rec))
 
 
 class DivergenceFinder:
@@ -2776,18 +2898,27 @@ Alignment = collections.namedtuple("Alignment", ["qry_id", "trg_id", "qry_start"
                                                  "is_secondary"])
 
 
+# a record of SamAlignments(want_cols=False): the scalars of Alignment, then SAM POS, the CIGAR runs and the SEQ bytes
+SamRecord = collections.namedtuple("SamRecord", ["qry_id", "trg_id", "qry_start", "qry_end", "qry_sign", "qry_len", "trg_start",
+                                                 "trg_end", "trg_sign", "trg_len", "err_rate", "is_secondary", "ctg_pos", "ops",
+                                                 "lens", "seq"])
+
+
 class SamAlignments:
     """Mirror of the reference's SynchronizedSamReader (flye/utils/sam_parser.py:123-404) on fg_expand_cigars: the whole
     SAM file (plain or .gz) is read at once, tokenised on the host (CIGARs through fg_cigar_parse) and every record that
     get_chunk would parse goes into ONE device call.  contigs maps contig id to sequence (str or bytes), as the
     reference's reference_fasta.  max_coverage = None makes no cut (the reference compares with None there, which
-    Python 3 refuses).  Raises ValueError where the reference raises AlignmentException("Alignment file is not sorted")."""
+    Python 3 refuses).  Raises ValueError where the reference raises AlignmentException("Alignment file is not sorted").
+    want_cols=False expands without columns (err_rate and the scalars only) and keeps, per record, a SamRecord with the
+    runs and the SEQ bytes where want_cols=True builds an Alignment with the two gapped strings: what
+    ContigConsensus.consensus_sam and BubbleMaker.make_sam / polish_sam hand to the fused device calls."""
 
     HEADERS = (b"@PG", b"@HD", b"@SQ", b"@RG", b"@CO")
 
-    def __init__(self, ctx, sam_path, contigs, max_coverage=None, use_secondary=False):
+    def __init__(self, ctx, sam_path, contigs, max_coverage=None, use_secondary=False, want_cols=True):
         self.ctx = ctx
-        self.max_coverage, self.use_secondary = max_coverage, use_secondary
+        self.max_coverage, self.use_secondary, self.want_cols = max_coverage, use_secondary, bool(want_cols)
         as_bytes = lambda x: x if isinstance(x, bytes) else x.encode("latin-1")
         self.contigs = {as_bytes(h): as_bytes(s) for h, s in contigs.items()}
         opener = gzip.open if sam_path.endswith(".gz") else open
@@ -2865,12 +2996,19 @@ class SamAlignments:
             [number[r[0][2]] for r in flat], [int(r[0][3]) for r in flat], np.cumsum([0] + [len(r[2]) for r in flat]),
             np.concatenate([r[2] for r in flat]) if flat else np.zeros(0, np.uint8),
             np.concatenate([r[3] for r in flat]) if flat else np.zeros(0, np.uint32),
-            np.cumsum([0] + [len(r[0][9]) for r in flat]), b"".join(r[0][9] for r in flat))
+            np.cumsum([0] + [len(r[0][9]) for r in flat]), b"".join(r[0][9] for r in flat), want_cols=self.want_cols)
         self.result = res
         out, a = [], 0
         for (contig, _), recs in zip(file_chunks, kept):
             alns = []
-            for tokens, flags, _, _ in recs:
+            for tokens, flags, ops, lens in recs:
+                if not self.want_cols:
+                    alns.append(SamRecord(tokens[0].decode(), tokens[2].decode(), int(res.qry_start[a]), int(res.qry_end[a]),
+                                          "-" if flags & 0x16 else "+", int(res.qry_len[a]), int(res.trg_start[a]),
+                                          int(res.trg_end[a]), "+", len(self.contigs[tokens[2]]), float(res.err_rate[a]),
+                                          flags & 0x100, int(tokens[3]), ops, lens, tokens[9]))
+                    a += 1
+                    continue
                 trg, qry = res.columns(a)
                 alns.append(Alignment(tokens[0].decode(), tokens[2].decode(), int(res.qry_start[a]), int(res.qry_end[a]),
                                       "-" if flags & 0x16 else "+", int(res.qry_len[a]), int(res.trg_start[a]),
@@ -2882,9 +3020,33 @@ class SamAlignments:
         return out
 
     def chunks(self):
-        """[(contig id, [Alignment])] in file order: what successive get_chunk calls return"""
+        """[(contig id, [Alignment])] in file order: what successive get_chunk calls return (want_cols=False: SamRecord
+        for Alignment, in the same order)"""
         return self._chunks
 
     def by_contig(self):
         """{contig id: [Alignment]}: what BubbleMaker.make and ContigConsensus.consensus take"""
         return dict(self._chunks)
+
+    def flatten(self, contigs, keep=None):
+        """the SamRecords of the given contigs (records with id), contig by contig, as the arguments the fused calls take:
+        (records, dict(contig_off, contig_seq, contig_aln_off, ctg_pos, run_off, run_op, run_len, read_off, read_seq)).
+        keep (one flag per record of these contigs, in this order) drops records."""
+        if self.want_cols:
+            raise ValueError("SamAlignments.flatten: made with want_cols=True, the records carry no runs")
+        by = dict(self._chunks)
+        lists = [by.get(c.id, []) for c in contigs]
+        if keep is not None:
+            flags, at = np.asarray(keep).astype(bool), 0
+            for k, lst in enumerate(lists):
+                lists[k] = [r for r, f in zip(lst, flags[at:at + len(lst)]) if f]
+                at += len(lst)
+        recs = [r for lst in lists for r in lst]
+        seqs = [self.contigs[c.id.encode("latin-1")] for c in contigs]
+        return recs, dict(
+            contig_off=np.cumsum([0] + [len(x) for x in seqs]), contig_seq=b"".join(seqs),
+            contig_aln_off=np.cumsum([0] + [len(lst) for lst in lists]), ctg_pos=[r.ctg_pos for r in recs],
+            run_off=np.cumsum([0] + [len(r.ops) for r in recs]),
+            run_op=np.concatenate([r.ops for r in recs]) if recs else np.zeros(0, np.uint8),
+            run_len=np.concatenate([r.lens for r in recs]) if recs else np.zeros(0, np.uint32),
+            read_off=np.cumsum([0] + [len(r.seq) for r in recs]), read_seq=b"".join(r.seq for r in recs))

@@ -997,6 +997,51 @@ int  fg_expand_cigars(fg_ctx* ctx, uint32_t n_contigs, const uint64_t* contig_of
                       const uint64_t* run_off, const uint8_t* run_op /* ASCII */, const uint32_t* run_len,
                       const uint64_t* read_off, const uint8_t* read_seq, uint8_t want_cols, struct fg_expand_batch* out);
 void fg_release_expand(struct fg_expand_batch* b);
+
+/* fg_expand_cigars(want_cols = 1) followed by fg_contig_consensus as ONE call: the columns are expanded on the device
+ * straight into the buffers the consensus kernels read and never cross the bus.  The contig bytes are those of
+ * fg_expand_cigars (contig_len[i] = contig_off[i+1] - contig_off[i]); the alignments are grouped by contig in the caller's
+ * order as for fg_contig_consensus: contig i has the alignments contig_aln_off[i] .. contig_aln_off[i+1], which replaces
+ * aln_contig.  ctg_pos, run_off, run_op, run_len, read_off and read_seq describe alignment a as for fg_expand_cigars,
+ * qry_id, use and want_profile are those of fg_contig_consensus; every per-alignment array is indexed by the caller's
+ * alignment number, and no offset array need start at zero.  Every field of *out equals what the two calls give for the
+ * same records; it is released with fg_release_consensus.
+ * Sub-batches of whole contigs under the budgets of fg_contig_consensus (FG_CONSENSUS_BATCH_COLS columns plus positions,
+ * FG_CONSENSUS_BATCH_CONTIGS); a sub-batch also ends where the expansion's numbering does (2^31 - 1 columns, runs and SEQ
+ * bytes, 2^30 - 1 alignments).  Each sub-batch expands its own alignments (FG_CIGAR_TILE applies, FG_CIGAR_BATCH_COLS
+ * and FG_CIGAR_BATCH_ALNS do not); the contig bytes go up once per call.  The set of query bytes that sizes the match
+ * table is found on the device (k_col_present), over the alignments in use only, as the host finds it in the two-step
+ * path.  The result depends on none of the switches.
+ * Errors: every code of fg_expand_cigars for the same records (FG_ERR_UNSUPPORTED for N P = X; FG_ERR_ARG for NULL where
+ * something is read, decreasing offsets, ctg_pos < 1, runs that overrun SEQ or the contig, an alignment without columns,
+ * a byte >= 128, totals beyond int32), then those of fg_contig_consensus that the expansion does not already exclude
+ * (FG_ERR_ARG: an alignment in use whose trg_start is not inside its contig, which only an alignment of insertions alone
+ * behind the last base can be; a contig of 2^31 bytes), all found before any device work.  FG_ERR_NOMEM: a contig that
+ * alone exceeds FG_CONSENSUS_BATCH_COLS or the expansion's numbering (the message names the switch), a match table of
+ * 2^32 cells.  After an error *out is all zero and the context stays usable.  n_contigs = 0 gives an empty batch. */
+int  fg_contig_consensus_cigars(fg_ctx* ctx, uint32_t n_contigs, const uint64_t* contig_off, const uint8_t* contig_seq,
+                                const uint64_t* contig_aln_off, const int32_t* ctg_pos /* SAM POS, 1-based */,
+                                const uint64_t* run_off, const uint8_t* run_op /* ASCII */, const uint32_t* run_len,
+                                const uint64_t* read_off, const uint8_t* read_seq, const int32_t* qry_id, const uint8_t* use,
+                                uint8_t want_profile, struct fg_consensus_batch* out);
+
+/* fg_expand_cigars(want_cols = 1) followed by fg_make_bubbles as ONE call, with the same substitutions as
+ * fg_contig_consensus_cigars: contig bytes for contig_len, contig_aln_off for aln_contig, the records for the columns;
+ * trg_start = ctg_pos - 1 and trg_end = trg_start + the contig bytes the runs consume.  params, contig_circular and
+ * want_profile are those of fg_make_bubbles.  err_rate stays an input (the caller has it from the want_cols = 0 expansion
+ * it made for fg_uniform_alignments): it decides in_profile before any column exists.  Every field of *out equals what the
+ * two calls give for the same records and the same err_rate; it is released with fg_release_bubbles.
+ * Sub-batches of whole contigs under FG_BUBBLE_BATCH_COLS / FG_BUBBLE_BATCH_CONTIGS and the expansion's numbering, as
+ * above.  Errors: those of fg_make_bubbles for the parameters and err_rate, every code of fg_expand_cigars for the
+ * records, FG_ERR_ARG for an alignment whose trg_start is not inside its contig and for a contig of 2^31 bytes;
+ * FG_ERR_NOMEM as above with FG_BUBBLE_BATCH_COLS.  After an error *out is all zero and the context stays usable.
+ * n_contigs = 0 gives an empty batch. */
+int  fg_make_bubbles_cigars(fg_ctx* ctx, const struct fg_bubble_params* params, uint32_t n_contigs, const uint64_t* contig_off,
+                            const uint8_t* contig_seq, const uint8_t* contig_circular, const uint64_t* contig_aln_off,
+                            const int32_t* ctg_pos /* SAM POS, 1-based */, const uint64_t* run_off,
+                            const uint8_t* run_op /* ASCII */, const uint32_t* run_len, const uint64_t* read_off,
+                            const uint8_t* read_seq, const double* err_rate, uint8_t want_profile, struct fg_bubble_batch* out);
+
 /* host only, no context: the tokens of the reference's re "[0-9]+[MIDNSHP=X]" (:140) in order, as findall gives them
  * (bytes that match nothing are skipped).  *n_runs = the number of tokens; at most cap of them are written.  FG_ERR_ARG:
  * more tokens than cap (*n_runs still says how many), a length beyond uint32, NULL n_runs, NULL where something is read
