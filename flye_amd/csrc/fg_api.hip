@@ -2,6 +2,7 @@
 // build/export entry points and the error boundary.  No exception leaves this
 // file; there is no CPU fallback -- without a HIP device fg_create fails.
 #include "fg_ctx.h"
+#include "fg_stage.h"		// guarded
 #include <chrono>
 #include <cmath>
 
@@ -52,25 +53,6 @@ struct RandStreamGuard {
 	}
 	~RandStreamGuard() { if (old) setstate(old); }
 };
-
-template <class F>
-int guarded(fg_ctx* c, F f)
-{
-	int rc = FG_OK;
-	try { f(); return FG_OK; }
-	catch (const FgError& e) { if (c) c->lastError = e.msg; rc = e.code; }
-	catch (const std::bad_alloc&) { if (c) c->lastError = "host allocation failed"; rc = FG_ERR_NOMEM; }
-	catch (const std::exception& e) { if (c) c->lastError = e.what(); rc = FG_ERR_HIP; }
-	// a call that failed half way may have left launches behind on either stream: nothing of the context's
-	// scratch is reused before they have drained
-	for (fg_ctx* x : {c, c ? c->lane2.get() : (fg_ctx*)nullptr})		// the second lane of fg_overlaps has streams of its own
-	{
-		if (x && x->stream2) (void)hipStreamSynchronize(x->stream2);
-		if (x && x->stream3) (void)hipStreamSynchronize(x->stream3);
-		if (x && x->stream) (void)hipStreamSynchronize(x->stream);
-	}
-	return rc;
-}
 
 } // namespace
 

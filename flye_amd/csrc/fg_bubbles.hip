@@ -36,6 +36,7 @@
 // fg_make_bubbles_cigars takes SAM records where fg_make_bubbles takes columns: a sub-batch expands its own alignments
 // (fg_cigexpand.h) on the context's stream straight into the two column buffers, so no column crosses the bus.
 #include "fg_ctx.h"
+#include "fg_stage.h"
 #include "fg_devprim.h"
 #include "fg_gapshift.h"
 #include "fg_cigexpand.h"
@@ -523,18 +524,6 @@ i32 bubMaxNumerator(double rate, u32 cov)
 	return (i32)n;
 }
 
-struct BubBufs {
-	fg_ctx* c;
-	int next = 0;
-	template <class T> T* get(size_t count)
-	{
-		if (next >= (int)(sizeof(c->dBub) / sizeof(c->dBub[0]))) throw FgError{FG_ERR_HIP, "internal: fg_make_bubbles buffer pool too small"};
-		DevBuf<char>& b = c->dBub[next++];
-		b.reserve(count * sizeof(T) + 16);
-		return (T*)b.p;
-	}
-};
-
 void bubSubBatch(fg_ctx* c, const fg_bubble_params& P, u32 c0, u32 c1, const int32_t* contigLen, const uint8_t* contigCirc,
 				 const uint64_t* contigAlnOff, const int32_t* trgStart, const int32_t* trgEnd, const uint64_t* colOff,
 				 const uint8_t* trgCols, const uint8_t* qryCols, const uint8_t* inProf /* by absolute alignment - first */, u64 aln00,
@@ -581,7 +570,7 @@ void bubSubBatch(fg_ctx* c, const fg_bubble_params& P, u32 c0, u32 c1, const int
 		for (int i = 0; from[i]; ++i) acgt[(int)from[i]] = (unsigned char)to[i];
 	}
 
-	BubBufs B{c};
+	DevPool B{c->dBub, "fg_make_bubbles"};
 	BubAln* dAln = B.get<BubAln>(nAln);
 	BubContig* dCtg = B.get<BubContig>(nC);
 	// k_cig_expand stores whole words past the last column
@@ -855,12 +844,8 @@ void bubClose(BubbleOwner* own)
 	own->candOff.push_back(own->cand.size());
 	own->bubbleBranchOff.push_back(own->branchOff.size());
 	own->branchOff.push_back(own->branches.size());
-	for (auto* v : {&own->cand, &own->branches, &own->inProfile, &own->nucl})
-		if (v->empty()) v->reserve(1);
-	for (auto* v : {&own->position, &own->nLongBubbles, &own->nEmpty, &own->nLongBranch, &own->nPartition, &own->partition,
-					&own->coverage, &own->numInserts, &own->numDeletions, &own->numMissmatch})
-		if (v->empty()) v->reserve(1);
-	if (own->meanCov.empty()) own->meanCov.reserve(1);
+	stageKeep(own->cand, own->branches, own->inProfile, own->nucl, own->position, own->nLongBubbles, own->nEmpty, own->nLongBranch,
+			  own->nPartition, own->partition, own->coverage, own->numInserts, own->numDeletions, own->numMissmatch, own->meanCov);
 }
 
 } // namespace
@@ -872,33 +857,20 @@ int fg_make_bubbles(fg_ctx* c, const struct fg_bubble_params* params, uint32_t n
 					const double* err_rate, const uint64_t* col_off, const uint8_t* trg_cols, const uint8_t* qry_cols,
 					uint8_t want_profile, struct fg_bubble_batch* out)
 {
-	if (!c) return FG_ERR_ARG;
-	if (out) memset(out, 0, sizeof(*out));
-	BubbleOwner* own = nullptr;
-	int rc = FG_OK;
-	try
+	return stageCall<BubbleOwner>(c, out, [&](BubbleOwner*& own)
 	{
 		const std::string name = "fg_make_bubbles";
 		if (!params || !out) throw FgError{FG_ERR_ARG, name + ": null params or result"};
 		const fg_bubble_params& P = *params;
 		bubCheckParams(name, P);
-		if (n_contigs && (!contig_len || !contig_aln_off)) throw FgError{FG_ERR_ARG, name + ": null contig_len or contig_aln_off"};
-		for (u32 i = 0; i < n_contigs; ++i)
-		{
-			if (contig_len[i] < 0) throw FgError{FG_ERR_ARG, name + ": contig_len < 0 at contig " + std::to_string(i)};
-			if (contig_aln_off[i + 1] < contig_aln_off[i])
-				throw FgError{FG_ERR_ARG, name + ": contig_aln_off decreases at contig " + std::to_string(i)};
-		}
+		stageContigTable(name, n_contigs, contig_len, contig_aln_off);
 		const u64 a0 = n_contigs ? contig_aln_off[0] : 0, a1 = n_contigs ? contig_aln_off[n_contigs] : 0;
 		if (a1 > a0 && (!trg_start || !trg_end || !err_rate || !col_off))
 			throw FgError{FG_ERR_ARG, name + ": null trg_start, trg_end, err_rate or col_off"};
-		for (u64 a = a0; a < a1; ++a)
+		stageColOff(name, col_off, a0, a1, trg_cols, qry_cols, [&](u64 a)
 		{
-			if (col_off[a + 1] < col_off[a]) throw FgError{FG_ERR_ARG, name + ": col_off decreases at alignment " + std::to_string(a)};
-			if (col_off[a + 1] - col_off[a] >= (1ULL << 31)) throw FgError{FG_ERR_ARG, name + ": an alignment of 2^31 columns"};
 			if (!(err_rate[a] >= 0.0)) throw FgError{FG_ERR_ARG, name + ": err_rate NaN or negative at alignment " + std::to_string(a)};
-		}
-		if (a1 > a0 && col_off[a1] > col_off[a0] && (!trg_cols || !qry_cols)) throw FgError{FG_ERR_ARG, name + ": null trg_cols or qry_cols"};
+		});
 		own = new BubbleOwner;
 		own->inProfile.assign((size_t)(a1 - a0), 0);
 		std::vector<u64> cost(n_contigs, 0);
@@ -906,16 +878,10 @@ int fg_make_bubbles(fg_ctx* c, const struct fg_bubble_params* params, uint32_t n
 		{
 			for (u64 a = contig_aln_off[i]; a < contig_aln_off[i + 1]; ++a)
 			{
-				if (trg_start[a] < 0 || trg_start[a] >= contig_len[i])
-					throw FgError{FG_ERR_ARG, name + ": trg_start outside the contig at alignment " + std::to_string(a)};
-				u64 nonGap = 0;
-				for (u64 k = col_off[a]; k < col_off[a + 1]; ++k)
-				{
-					if ((trg_cols[k] | qry_cols[k]) >= 128) throw FgError{FG_ERR_ARG, name + ": a byte >= 128 in alignment " + std::to_string(a)};
-					nonGap += trg_cols[k] != '-';
-				}
-				if (nonGap > (u64)contig_len[i])
-					throw FgError{FG_ERR_ARG, name + ": alignment " + std::to_string(a) + " has more target bases than its contig"};
+				// the order of the reports is part of the call: trg_start first, then the bytes (fg_contig_consensus and
+				// fg_divergence_profile: the bytes first)
+				stageStartOnContig(name, a, trg_start[a], contig_len[i]);
+				stageBasesOnContig(name, a, stageColumnWalk(name, a, col_off, trg_cols, qry_cols), contig_len[i]);
 				const u64 nCols = col_off[a + 1] - col_off[a];
 				own->inProfile[a - a0] = !(err_rate[a] > P.max_aln_error) && nCols >= (u64)P.min_polish_aln_len;
 			}
@@ -923,44 +889,24 @@ int fg_make_bubbles(fg_ctx* c, const struct fg_bubble_params* params, uint32_t n
 			cost[i] = (u64)contig_len[i];
 			if (contig_aln_off[i + 1] > contig_aln_off[i]) cost[i] += col_off[contig_aln_off[i + 1]] - col_off[contig_aln_off[i]];
 		}
-		u64 budget = 1ULL << 27;
-		if (const char* e = getenv("FG_BUBBLE_BATCH_COLS")) budget = strtoull(e, nullptr, 10);
-		u64 maxContigs = ~0ULL;			// a switch for tests: contigs per sub-batch
-		if (const char* e = getenv("FG_BUBBLE_BATCH_CONTIGS")) maxContigs = std::max<u64>(1, strtoull(e, nullptr, 10));
+		const u64 budget = stageEnvU64("FG_BUBBLE_BATCH_COLS", 1ULL << 27);
+		const u64 maxContigs = stageEnvCap("FG_BUBBLE_BATCH_CONTIGS");		// a switch for tests: contigs per sub-batch
 		own->bubbleOff.assign(1, 0);
 		if (want_profile) { own->partOff.assign(1, 0); own->profOff.assign(1, 0); }
 		HIP_CHECK(hipSetDevice(c->device));
 		c->timer.reset();
-		for (u32 i = 0; i < n_contigs; ++i)
-			if (cost[i] > budget)
-				throw FgError{FG_ERR_NOMEM, name + ": contig " + std::to_string(i) + " alone has " + std::to_string(cost[i]) +
-												" columns and positions, FG_BUBBLE_BATCH_COLS is " + std::to_string(budget)};
-		u32 i = 0;
-		while (i < n_contigs)
+		stageAllFit(name, "contig", cost, budget, "columns and positions", "FG_BUBBLE_BATCH_COLS");
+		for (u32 i = 0; i < n_contigs;)
 		{
-			u32 j = i;
-			u64 used = 0;
-			while (j < n_contigs && (j == i || (used + cost[j] <= budget && j - i < maxContigs))) used += cost[j++];
+			const u32 j = stageCut(i, n_contigs, cost, budget, maxContigs);
 			bubSubBatch(c, P, i, j, contig_len, contig_circular, contig_aln_off, trg_start, trg_end, col_off, trg_cols, qry_cols,
 						own->inProfile.data(), a0, want_profile != 0, *own);
 			i = j;
 		}
 		c->timer.collect();
 		bubClose(own);
-	}
-	catch (const FgError& e) { c->lastError = e.msg; rc = e.code; }
-	catch (const std::bad_alloc&) { c->lastError = "host allocation failed"; rc = FG_ERR_NOMEM; }
-	catch (const std::exception& e) { c->lastError = e.what(); rc = FG_ERR_HIP; }
-	if (rc != FG_OK)
-	{
-		// launches of a call that failed half way drain before the context's scratch is used again
-		if (c->stream) (void)hipStreamSynchronize(c->stream);
-		c->timer.reset();
-		delete own;
-		return rc;
-	}
-	bubHandOver(out, own, n_contigs, want_profile != 0);
-	return FG_OK;
+		bubHandOver(out, own, n_contigs, want_profile != 0);
+	});
 }
 
 int fg_make_bubbles_cigars(fg_ctx* c, const struct fg_bubble_params* params, uint32_t n_contigs, const uint64_t* contig_off,
@@ -968,20 +914,14 @@ int fg_make_bubbles_cigars(fg_ctx* c, const struct fg_bubble_params* params, uin
 						   const uint64_t* run_off, const uint8_t* run_op, const uint32_t* run_len, const uint64_t* read_off,
 						   const uint8_t* read_seq, const double* err_rate, uint8_t want_profile, struct fg_bubble_batch* out)
 {
-	if (!c) return FG_ERR_ARG;
-	if (out) memset(out, 0, sizeof(*out));
-	BubbleOwner* own = nullptr;
-	int rc = FG_OK;
-	try
+	return stageCall<BubbleOwner>(c, out, [&](BubbleOwner*& own)
 	{
 		const std::string name = "fg_make_bubbles_cigars";
 		if (!params || !out) throw FgError{FG_ERR_ARG, name + ": null params or result"};
 		const fg_bubble_params& P = *params;
 		bubCheckParams(name, P);
 		if (n_contigs && !contig_aln_off) throw FgError{FG_ERR_ARG, name + ": null contig_aln_off"};
-		for (u32 i = 0; i < n_contigs; ++i)
-			if (contig_aln_off[i + 1] < contig_aln_off[i])
-				throw FgError{FG_ERR_ARG, name + ": contig_aln_off decreases at contig " + std::to_string(i)};
+		stageOffsets(name, "contig_aln_off", "contig ", contig_aln_off, 0, n_contigs);
 		const u64 a0 = n_contigs ? contig_aln_off[0] : 0, a1 = n_contigs ? contig_aln_off[n_contigs] : 0;
 		std::vector<uint32_t> alnContig((size_t)a1, 0);
 		for (u32 i = 0; i < n_contigs; ++i)
@@ -1003,29 +943,22 @@ int fg_make_bubbles_cigars(fg_ctx* c, const struct fg_bubble_params* params, uin
 			for (u64 a = contig_aln_off[i]; a < contig_aln_off[i + 1]; ++a)
 			{
 				// an alignment of insertions alone may stand behind the last base
-				if (plan.trgStart[a] >= contigLen[i])
-					throw FgError{FG_ERR_ARG, name + ": trg_start outside the contig at alignment " + std::to_string(a)};
+				stageStartOnContig(name, a, plan.trgStart[a], contigLen[i]);
 				own->inProfile[a - a0] = !(err_rate[a] > P.max_aln_error) && plan.tot[a].cols >= (u64)P.min_polish_aln_len;
 			}
 			// a contig counts its columns and its positions
 			cost[i] = (u64)contigLen[i] + (plan.colOff[contig_aln_off[i + 1]] - plan.colOff[contig_aln_off[i]]);
 		}
-		u64 budget = 1ULL << 27;
-		if (const char* e = getenv("FG_BUBBLE_BATCH_COLS")) budget = strtoull(e, nullptr, 10);
-		u64 maxContigs = ~0ULL;			// a switch for tests: contigs per sub-batch
-		if (const char* e = getenv("FG_BUBBLE_BATCH_CONTIGS")) maxContigs = std::max<u64>(1, strtoull(e, nullptr, 10));
+		const u64 budget = stageEnvU64("FG_BUBBLE_BATCH_COLS", 1ULL << 27);
+		const u64 maxContigs = stageEnvCap("FG_BUBBLE_BATCH_CONTIGS");		// a switch for tests: contigs per sub-batch
 		own->bubbleOff.assign(1, 0);
 		if (want_profile) { own->partOff.assign(1, 0); own->profOff.assign(1, 0); }
 		HIP_CHECK(hipSetDevice(c->device));
 		c->timer.reset();
-		for (u32 i = 0; i < n_contigs; ++i)
-			if (cost[i] > budget)
-				throw FgError{FG_ERR_NOMEM, name + ": contig " + std::to_string(i) + " alone has " + std::to_string(cost[i]) +
-												" columns and positions, FG_BUBBLE_BATCH_COLS is " + std::to_string(budget)};
+		stageAllFit(name, "contig", cost, budget, "columns and positions", "FG_BUBBLE_BATCH_COLS");
 		// the contig bytes go up once per call; a sub-batch expands its own alignments
 		const CigSource src{&plan, a1 > a0 ? cigUploadContigs(c, plan, contig_seq) : nullptr, run_off, run_op, run_len, read_off, read_seq, cigTile()};
-		u32 i = 0;
-		while (i < n_contigs)
+		for (u32 i = 0; i < n_contigs;)
 		{
 			const u32 j = cigCutContigs(name, "FG_BUBBLE_BATCH_COLS", i, n_contigs, cost, budget, maxContigs, contig_aln_off, run_off, read_off);
 			bubSubBatch(c, P, i, j, contigLen.data(), contig_circular, contig_aln_off, plan.trgStart.data(), plan.trgEnd.data(),
@@ -1034,27 +967,10 @@ int fg_make_bubbles_cigars(fg_ctx* c, const struct fg_bubble_params* params, uin
 		}
 		c->timer.collect();
 		bubClose(own);
-	}
-	catch (const FgError& e) { c->lastError = e.msg; rc = e.code; }
-	catch (const std::bad_alloc&) { c->lastError = "host allocation failed"; rc = FG_ERR_NOMEM; }
-	catch (const std::exception& e) { c->lastError = e.what(); rc = FG_ERR_HIP; }
-	if (rc != FG_OK)
-	{
-		// launches of a call that failed half way drain before the context's scratch is used again
-		if (c->stream) (void)hipStreamSynchronize(c->stream);
-		c->timer.reset();
-		delete own;
-		return rc;
-	}
-	bubHandOver(out, own, n_contigs, want_profile != 0);
-	return FG_OK;
+		bubHandOver(out, own, n_contigs, want_profile != 0);
+	});
 }
 
-void fg_release_bubbles(struct fg_bubble_batch* b)
-{
-	if (!b) return;
-	delete (BubbleOwner*)b->owner_;
-	memset(b, 0, sizeof(*b));
-}
+void fg_release_bubbles(struct fg_bubble_batch* b) { stageRelease<BubbleOwner>(b); }
 
 } // extern "C"

@@ -47,7 +47,7 @@ void cigSubBatch(fg_ctx* c, u64 a0, u64 a1, const std::vector<CigTotals>& tot, c
 	const u32 nAln = (u32)(a1 - a0);
 	u64 nCols = 0;
 	for (u64 a = a0; a < a1; ++a) nCols += tot[a].cols;
-	CigBufs B{c, 1};
+	DevPool B = cigPool(c, 1);
 	// whole words: the lane that holds the last column stores all of its 8
 	unsigned char* dTrgOut = wantCols ? B.get<unsigned char>(nCols + CIG_LANE_COLS) : nullptr;
 	unsigned char* dQryOut = wantCols ? B.get<unsigned char>(nCols + CIG_LANE_COLS) : nullptr;
@@ -109,11 +109,7 @@ int fg_expand_cigars(fg_ctx* c, uint32_t n_contigs, const uint64_t* contig_off, 
 					 const uint32_t* run_len, const uint64_t* read_off, const uint8_t* read_seq, uint8_t want_cols,
 					 struct fg_expand_batch* out)
 {
-	if (!c) return FG_ERR_ARG;
-	if (out) memset(out, 0, sizeof(*out));
-	ExpandOwner* own = nullptr;
-	int rc = FG_OK;
-	try
+	return stageCall<ExpandOwner>(c, out, [&](ExpandOwner*& own)
 	{
 		const std::string name = "fg_expand_cigars";
 		const u64 nA = n_alignments;
@@ -130,13 +126,9 @@ int fg_expand_cigars(fg_ctx* c, uint32_t n_contigs, const uint64_t* contig_off, 
 		own->qryStart = std::move(plan.qryStart); own->qryEnd = std::move(plan.qryEnd); own->qryLen = std::move(plan.qryLen);
 		own->matches.assign((size_t)nA, 0);
 		own->errRate.assign((size_t)nA, 0.0);
-		const u64 budget = std::min<u64>(cigEnv("FG_CIGAR_BATCH_COLS", 1ULL << 27), I32);
-		u64 maxAlns = CIG_ALN_MASK;			// a record carries the alignment's number in 30 bits
-		if (getenv("FG_CIGAR_BATCH_ALNS")) maxAlns = std::min<u64>(maxAlns, std::max<u64>(1, cigEnv("FG_CIGAR_BATCH_ALNS", 1)));
-		for (u64 a = 0; a < nA; ++a)
-			if (tot[a].cols > budget)
-				throw FgError{FG_ERR_NOMEM, name + ": alignment " + std::to_string(a) + " alone has " + std::to_string(tot[a].cols) +
-												" columns, FG_CIGAR_BATCH_COLS is " + std::to_string(budget)};
+		const u64 budget = std::min<u64>(stageEnvU64("FG_CIGAR_BATCH_COLS", 1ULL << 27), I32);
+		const u64 maxAlns = std::min<u64>(CIG_ALN_MASK, stageEnvCap("FG_CIGAR_BATCH_ALNS"));		// a record carries the alignment's number in 30 bits
+		for (u64 a = 0; a < nA; ++a) stageFits(name, "alignment", a, tot[a].cols, budget, "columns", "FG_CIGAR_BATCH_COLS");
 		if (want_cols)
 		{
 			own->trgCols.resize((size_t)own->colOff[nA]);
@@ -148,7 +140,7 @@ int fg_expand_cigars(fg_ctx* c, uint32_t n_contigs, const uint64_t* contig_off, 
 		if (nA)
 		{
 			// the contig bytes go up once per call
-			CigBufs B{c, 0};
+			DevPool B = cigPool(c, 0);
 			unsigned char* dContig = B.get<unsigned char>(nCtgBytes);
 			if (nCtgBytes) HIP_CHECK(hipMemcpyAsync(dContig, contig_seq + ctg0, nCtgBytes, hipMemcpyHostToDevice, c->stream));
 			u64 i = 0;
@@ -166,47 +158,26 @@ int fg_expand_cigars(fg_ctx* c, uint32_t n_contigs, const uint64_t* contig_off, 
 		}
 		c->timer.collect();
 		for (u64 a = 0; a < nA; ++a) own->errRate[a] = 1.0 - (double)own->matches[a] / (double)tot[a].cols;
-		for (auto* v : {&own->trgCols, &own->qryCols})
-			if (v->empty()) v->reserve(1);
-		for (auto* v : {&own->trgStart, &own->trgEnd, &own->qryStart, &own->qryEnd, &own->qryLen})
-			if (v->empty()) v->reserve(1);
-		if (own->matches.empty()) own->matches.reserve(1);
-		if (own->errRate.empty()) own->errRate.reserve(1);
-	}
-	catch (const FgError& e) { c->lastError = e.msg; rc = e.code; }
-	catch (const std::bad_alloc&) { c->lastError = "host allocation failed"; rc = FG_ERR_NOMEM; }
-	catch (const std::exception& e) { c->lastError = e.what(); rc = FG_ERR_HIP; }
-	if (rc != FG_OK)
-	{
-		// launches of a call that failed half way drain before the context's scratch is used again
-		if (c->stream) (void)hipStreamSynchronize(c->stream);
-		c->timer.reset();
-		delete own;
-		return rc;
-	}
-	out->n_alignments = n_alignments;
-	out->col_off = own->colOff.data();
-	if (want_cols)
-	{
-		out->trg_cols = own->trgCols.data();
-		out->qry_cols = own->qryCols.data();
-	}
-	out->trg_start = own->trgStart.data();
-	out->trg_end = own->trgEnd.data();
-	out->qry_start = own->qryStart.data();
-	out->qry_end = own->qryEnd.data();
-	out->qry_len = own->qryLen.data();
-	out->matches = own->matches.data();
-	out->err_rate = own->errRate.data();
-	out->owner_ = own;
-	return FG_OK;
+		stageKeep(own->trgCols, own->qryCols, own->trgStart, own->trgEnd, own->qryStart, own->qryEnd, own->qryLen, own->matches, own->errRate);
+
+		out->n_alignments = n_alignments;
+		out->col_off = own->colOff.data();
+		if (want_cols)
+		{
+			out->trg_cols = own->trgCols.data();
+			out->qry_cols = own->qryCols.data();
+		}
+		out->trg_start = own->trgStart.data();
+		out->trg_end = own->trgEnd.data();
+		out->qry_start = own->qryStart.data();
+		out->qry_end = own->qryEnd.data();
+		out->qry_len = own->qryLen.data();
+		out->matches = own->matches.data();
+		out->err_rate = own->errRate.data();
+		out->owner_ = own;
+	});
 }
 
-void fg_release_expand(struct fg_expand_batch* b)
-{
-	if (!b) return;
-	delete (ExpandOwner*)b->owner_;
-	memset(b, 0, sizeof(*b));
-}
+void fg_release_expand(struct fg_expand_batch* b) { stageRelease<ExpandOwner>(b); }
 
 } // extern "C"

@@ -7,6 +7,7 @@
 //   cigCutContigs       where a sub-batch of whole contigs ends for a caller that expands per sub-batch.
 #pragma once
 #include "fg_ctx.h"
+#include "fg_stage.h"
 #include "fg_devprim.h"
 
 namespace {		// kernels of a header shared by several translation units: one internal copy each
@@ -162,29 +163,13 @@ k_cig_expand(u32 nCols, u32 tile, const CigRun* __restrict__ runs, u32 nRec, con
 	}
 }
 
-// the scratch of the expansion: the call's contig bytes in the context's first buffer, then the buffers of one sub-batch
-struct CigBufs {
-	fg_ctx* c;
-	int next;
-	template <class T> T* get(size_t count)
-	{
-		if (next >= (int)(sizeof(c->dCig) / sizeof(c->dCig[0]))) throw FgError{FG_ERR_HIP, "internal: fg_cigar buffer pool too small"};
-		DevBuf<char>& b = c->dCig[next++];
-		b.reserve(count * sizeof(T) + 16);
-		return (T*)b.p;
-	}
-};
-
-inline u64 cigEnv(const char* name, u64 dflt)
-{
-	const char* e = getenv(name);
-	return e ? strtoull(e, nullptr, 10) : dflt;
-}
+// the scratch of the expansion: the call's contig bytes in the pool's first buffer, then the buffers of one sub-batch
+inline DevPool cigPool(fg_ctx* c, int start) { return DevPool{c->dCig, "fg_cigar", start}; }
 
 // FG_CIGAR_TILE: a power of two in 64 .. 4096 (other values: the power of two below, inside that range)
 inline u32 cigTile()
 {
-	u64 t = cigEnv("FG_CIGAR_TILE", CIG_DEFAULT_TILE);
+	u64 t = stageEnvU64("FG_CIGAR_TILE", CIG_DEFAULT_TILE);
 	t = std::min<u64>(std::max<u64>(t, 64), CIG_MAX_TILE);
 	u32 p = 64;
 	while ((u64)p * 2 <= t) p *= 2;
@@ -213,8 +198,7 @@ inline void cigCheckRecords(const std::string& name, u32 n_contigs, const uint64
 {
 	const u64 nA = aEnd - aFirst;
 	if (n_contigs && !contig_off) throw FgError{FG_ERR_ARG, name + ": null contig_off"};
-	for (u32 i = 0; i < n_contigs; ++i)
-		if (contig_off[i + 1] < contig_off[i]) throw FgError{FG_ERR_ARG, name + ": contig_off decreases at contig " + std::to_string(i)};
+	stageOffsets(name, "contig_off", "contig ", contig_off, 0, n_contigs);
 	const u64 ctg0 = n_contigs ? contig_off[0] : 0, nCtgBytes = n_contigs ? contig_off[n_contigs] - ctg0 : 0;
 	if (nCtgBytes && !contig_seq) throw FgError{FG_ERR_ARG, name + ": null contig_seq"};
 	if (nA && perAlnNull) throw FgError{FG_ERR_ARG, name + ": " + nullMsg};
@@ -294,7 +278,7 @@ struct CigStaged { std::vector<u32> runBegin, alnRead; std::vector<u64> alnTrg; 
 // CIG_LANE_COLS bytes (both NULL: the equal columns are counted and nothing is stored).  trgBase[a] is the alignment's
 // first contig byte in dContig.  Returns the equal columns per alignment, on the device; nothing is waited for, so
 // `staged` stays alive until the caller has synchronised the stream.
-inline u32* cigExpandOnDevice(fg_ctx* c, CigBufs& B, CigStaged& staged, u64 a0, u64 a1, const std::vector<CigTotals>& tot, const std::vector<u64>& trgBase,
+inline u32* cigExpandOnDevice(fg_ctx* c, DevPool& B, CigStaged& staged, u64 a0, u64 a1, const std::vector<CigTotals>& tot, const std::vector<u64>& trgBase,
 							  const unsigned char* dContig, const uint64_t* runOff, const uint8_t* runOp, const uint32_t* runLen,
 							  const uint64_t* readOff, const uint8_t* readSeq, u32 tile, unsigned char* dTrgOut, unsigned char* dQryOut)
 {
@@ -370,17 +354,17 @@ struct CigSource {
 // the contig bytes of a fused call go up once, into the first buffer of the expansion's pool
 inline const unsigned char* cigUploadContigs(fg_ctx* c, const CigPlan& plan, const uint8_t* contigSeq)
 {
-	CigBufs B{c, 0};
+	DevPool B = cigPool(c, 0);
 	unsigned char* dContig = B.get<unsigned char>(plan.nCtgBytes);
 	if (plan.nCtgBytes) HIP_CHECK(hipMemcpyAsync(dContig, contigSeq + plan.ctg0, plan.nCtgBytes, hipMemcpyHostToDevice, c->stream));
 	return dContig;
 }
 
 // the columns of the alignments a0 .. a1 (a0 < a1) into dTrg / dQry (columns + CIG_LANE_COLS bytes each); the returned
-// CigBufs hands out the pool's buffers behind those the expansion uses
-inline CigBufs cigExpandSource(fg_ctx* c, const CigSource& src, CigStaged& staged, u64 a0, u64 a1, unsigned char* dTrg, unsigned char* dQry)
+// DevPool hands out the pool's buffers behind those the expansion uses
+inline DevPool cigExpandSource(fg_ctx* c, const CigSource& src, CigStaged& staged, u64 a0, u64 a1, unsigned char* dTrg, unsigned char* dQry)
 {
-	CigBufs B{c, 1};
+	DevPool B = cigPool(c, 1);
 	(void)cigExpandOnDevice(c, B, staged, a0, a1, src.plan->tot, src.plan->trgBase, src.dContig, src.runOff, src.runOp, src.runLen, src.readOff,
 							src.readSeq, src.tile, dTrg, dQry);
 	return B;

@@ -41,6 +41,7 @@
 //   k_col_present   one wave per alignment in use: a 128-bit mask of its query bytes, ORed over the wave, one atomic per
 //                   wave and word onto four words that the host reads before it sizes the match table.
 #include "fg_ctx.h"
+#include "fg_stage.h"
 #include "fg_devprim.h"
 #include "fg_gapshift.h"
 #include "fg_cigexpand.h"
@@ -379,18 +380,6 @@ k_col_present(const BubAln* __restrict__ alns, u32 nAln, const unsigned char* __
 	}
 }
 
-struct CcBufs {
-	fg_ctx* c;
-	int next = 0;
-	template <class T> T* get(size_t count)
-	{
-		if (next >= (int)(sizeof(c->dCc) / sizeof(c->dCc[0]))) throw FgError{FG_ERR_HIP, "internal: fg_contigcons buffer pool too small"};
-		DevBuf<char>& b = c->dCc[next++];
-		b.reserve(count * sizeof(T) + 16);
-		return (T*)b.p;
-	}
-};
-
 struct UniformOwner {
 	std::vector<uint8_t> keep;
 	std::vector<int32_t> covThr;
@@ -435,7 +424,7 @@ void uniSubBatch(fg_ctx* c, u32 c0, u32 c1, const int32_t* contigLen, const uint
 	pairOff[nAln] = (u32)nPairs;
 	const u32 nWin = winBase[nC];
 
-	CcBufs B{c};
+	DevPool B{c->dCc, "fg_contigcons"};
 	UniAln* dAln = B.get<UniAln>(nAln);
 	u32* dPairOff = B.get<u32>((size_t)nAln + 1);
 	u64* dErr = B.get<u64>(nAln);
@@ -544,7 +533,7 @@ void ccSubBatch(fg_ctx* c, u32 c0, u32 c1, const int32_t* contigLen, const uint6
 	ctgAt[nC] = nPos;
 	if (nPos >= (1ULL << 31) || nAln >= (1u << 23) || nCols >= (1ULL << 31))
 		throw FgError{FG_ERR_NOMEM, "fg_contig_consensus: a sub-batch of 2^31 positions or columns or 2^23 alignments; lower FG_CONSENSUS_BATCH_COLS"};
-	CcBufs B{c};
+	DevPool B{c->dCc, "fg_contigcons"};
 	BubAln* dAln = B.get<BubAln>(nAln);
 	CcContig* dCtg = B.get<CcContig>(nC);
 	u32* dQid = B.get<u32>(nAln);
@@ -558,7 +547,7 @@ void ccSubBatch(fg_ctx* c, u32 c0, u32 c1, const int32_t* contigLen, const uint6
 	if (cig && nAln)
 	{
 		HIP_CHECK(hipMemcpyAsync(dAln, alns.data(), (size_t)nAln * sizeof(BubAln), hipMemcpyHostToDevice, s));
-		CigBufs CB = cigExpandSource(c, *cig, staged, a0, a1, dTrg, dQry);
+		DevPool CB = cigExpandSource(c, *cig, staged, a0, a1, dTrg, dQry);
 		u32* dPresent = CB.get<u32>(4);
 		HIP_CHECK(hipMemsetAsync(dPresent, 0, 16, s));
 		{
@@ -724,12 +713,6 @@ void ccSubBatch(fg_ctx* c, u32 c0, u32 c1, const int32_t* contigLen, const uint6
 	HIP_CHECK(hipStreamSynchronize(s));
 }
 
-u64 envU64(const char* name, u64 dflt)
-{
-	const char* e = getenv(name);
-	return e ? strtoull(e, nullptr, 10) : dflt;
-}
-
 // the finished owner into the caller's struct
 void ccHandOver(struct fg_consensus_batch* out, ConsensusOwner* own, uint32_t n_contigs, bool wantProfile)
 {
@@ -758,21 +741,11 @@ int fg_uniform_alignments(fg_ctx* c, uint32_t n_contigs, const int32_t* contig_l
 						  const int32_t* trg_start, const int32_t* trg_end, const double* err_rate, const uint8_t* is_secondary,
 						  uint8_t want_thresholds, struct fg_uniform_result* out)
 {
-	if (!c) return FG_ERR_ARG;
-	if (out) memset(out, 0, sizeof(*out));
-	UniformOwner* own = nullptr;
-	int rc = FG_OK;
-	try
+	return stageCall<UniformOwner>(c, out, [&](UniformOwner*& own)
 	{
 		const std::string name = "fg_uniform_alignments";
 		if (!out) throw FgError{FG_ERR_ARG, name + ": null result"};
-		if (n_contigs && (!contig_len || !contig_aln_off)) throw FgError{FG_ERR_ARG, name + ": null contig_len or contig_aln_off"};
-		for (u32 i = 0; i < n_contigs; ++i)
-		{
-			if (contig_len[i] < 0) throw FgError{FG_ERR_ARG, name + ": contig_len < 0 at contig " + std::to_string(i)};
-			if (contig_aln_off[i + 1] < contig_aln_off[i])
-				throw FgError{FG_ERR_ARG, name + ": contig_aln_off decreases at contig " + std::to_string(i)};
-		}
+		stageContigTable(name, n_contigs, contig_len, contig_aln_off);
 		const u64 a0 = n_contigs ? contig_aln_off[0] : 0, a1 = n_contigs ? contig_aln_off[n_contigs] : 0;
 		if (a1 > a0 && (!trg_start || !trg_end || !err_rate)) throw FgError{FG_ERR_ARG, name + ": null trg_start, trg_end or err_rate"};
 		std::vector<u64> cost(n_contigs, 0);
@@ -786,11 +759,8 @@ int fg_uniform_alignments(fg_ctx* c, uint32_t n_contigs, const int32_t* contig_l
 				if (!(err_rate[a] >= 0.0)) throw FgError{FG_ERR_ARG, name + ": err_rate NaN or negative at alignment " + std::to_string(a)};
 				if (trg_end[a] / 100 > trg_start[a] / 100) cost[i] += (u64)(trg_end[a] / 100 - trg_start[a] / 100);
 			}
-		const u64 budget = std::min<u64>(envU64("FG_UNIFORM_BATCH_PAIRS", 1ULL << 26), fgprim::RS_MAX_N);
-		for (u32 i = 0; i < n_contigs; ++i)
-			if (cost[i] > budget)
-				throw FgError{FG_ERR_NOMEM, name + ": contig " + std::to_string(i) + " alone has " + std::to_string(cost[i]) +
-												" (alignment, window) pairs, FG_UNIFORM_BATCH_PAIRS is " + std::to_string(budget)};
+		const u64 budget = std::min<u64>(stageEnvU64("FG_UNIFORM_BATCH_PAIRS", 1ULL << 26), fgprim::RS_MAX_N);
+		stageAllFit(name, "contig", cost, budget, "(alignment, window) pairs", "FG_UNIFORM_BATCH_PAIRS");
 		own = new UniformOwner;
 		own->keep.assign((size_t)(a1 - a0), 0);
 		if (want_thresholds) own->wndOff.assign(1, 0);
@@ -813,130 +783,70 @@ int fg_uniform_alignments(fg_ctx* c, uint32_t n_contigs, const int32_t* contig_l
 			i = j;
 		}
 		c->timer.collect();
-		if (own->keep.empty()) own->keep.reserve(1);
-		if (own->covThr.empty()) own->covThr.reserve(1);
-		if (own->wndThr.empty()) own->wndThr.reserve(1);
-	}
-	catch (const FgError& e) { c->lastError = e.msg; rc = e.code; }
-	catch (const std::bad_alloc&) { c->lastError = "host allocation failed"; rc = FG_ERR_NOMEM; }
-	catch (const std::exception& e) { c->lastError = e.what(); rc = FG_ERR_HIP; }
-	if (rc != FG_OK)
-	{
-		// launches of a call that failed half way drain before the context's scratch is used again
-		if (c->stream) (void)hipStreamSynchronize(c->stream);
-		c->timer.reset();
-		delete own;
-		return rc;
-	}
-	out->n_contigs = n_contigs;
-	out->n_alignments = (uint64_t)own->keep.size();
-	out->keep = own->keep.data();
-	out->cov_threshold = own->covThr.data();
-	if (want_thresholds)
-	{
-		out->wnd_off = own->wndOff.data();
-		out->wnd_threshold = own->wndThr.data();
-	}
-	out->owner_ = own;
-	return FG_OK;
+		stageKeep(own->keep, own->covThr, own->wndThr);
+		out->n_contigs = n_contigs;
+		out->n_alignments = (uint64_t)own->keep.size();
+		out->keep = own->keep.data();
+		out->cov_threshold = own->covThr.data();
+		if (want_thresholds)
+		{
+			out->wnd_off = own->wndOff.data();
+			out->wnd_threshold = own->wndThr.data();
+		}
+		out->owner_ = own;
+	});
 }
 
-void fg_release_uniform(struct fg_uniform_result* r)
-{
-	if (!r) return;
-	delete (UniformOwner*)r->owner_;
-	memset(r, 0, sizeof(*r));
-}
+void fg_release_uniform(struct fg_uniform_result* r) { stageRelease<UniformOwner>(r); }
 
 int fg_contig_consensus(fg_ctx* c, uint32_t n_contigs, const int32_t* contig_len, const uint64_t* contig_aln_off,
 						const int32_t* trg_start, const int32_t* qry_id, const uint8_t* use, const uint64_t* col_off,
 						const uint8_t* trg_cols, const uint8_t* qry_cols, uint8_t want_profile, struct fg_consensus_batch* out)
 {
-	if (!c) return FG_ERR_ARG;
-	if (out) memset(out, 0, sizeof(*out));
-	ConsensusOwner* own = nullptr;
-	int rc = FG_OK;
-	try
+	return stageCall<ConsensusOwner>(c, out, [&](ConsensusOwner*& own)
 	{
 		const std::string name = "fg_contig_consensus";
 		if (!out) throw FgError{FG_ERR_ARG, name + ": null result"};
-		if (n_contigs && (!contig_len || !contig_aln_off)) throw FgError{FG_ERR_ARG, name + ": null contig_len or contig_aln_off"};
-		for (u32 i = 0; i < n_contigs; ++i)
-		{
-			if (contig_len[i] < 0) throw FgError{FG_ERR_ARG, name + ": contig_len < 0 at contig " + std::to_string(i)};
-			if (contig_aln_off[i + 1] < contig_aln_off[i])
-				throw FgError{FG_ERR_ARG, name + ": contig_aln_off decreases at contig " + std::to_string(i)};
-		}
+		stageContigTable(name, n_contigs, contig_len, contig_aln_off);
 		const u64 a0 = n_contigs ? contig_aln_off[0] : 0, a1 = n_contigs ? contig_aln_off[n_contigs] : 0;
 		if (a1 > a0 && (!trg_start || !qry_id || !col_off)) throw FgError{FG_ERR_ARG, name + ": null trg_start, qry_id or col_off"};
-		for (u64 a = a0; a < a1; ++a)
-		{
-			if (col_off[a + 1] < col_off[a]) throw FgError{FG_ERR_ARG, name + ": col_off decreases at alignment " + std::to_string(a)};
-			if (col_off[a + 1] - col_off[a] >= (1ULL << 31)) throw FgError{FG_ERR_ARG, name + ": an alignment of 2^31 columns"};
-		}
-		if (a1 > a0 && col_off[a1] > col_off[a0] && (!trg_cols || !qry_cols)) throw FgError{FG_ERR_ARG, name + ": null trg_cols or qry_cols"};
+		stageColOff(name, col_off, a0, a1, trg_cols, qry_cols);
 		std::vector<u64> cost(n_contigs, 0);
 		for (u32 i = 0; i < n_contigs; ++i)
 		{
 			for (u64 a = contig_aln_off[i]; a < contig_aln_off[i + 1]; ++a)
 			{
-				u64 nonGap = 0;
-				for (u64 k = col_off[a]; k < col_off[a + 1]; ++k)
-				{
-					if ((trg_cols[k] | qry_cols[k]) >= 128) throw FgError{FG_ERR_ARG, name + ": a byte >= 128 in alignment " + std::to_string(a)};
-					nonGap += trg_cols[k] != '-';
-				}
+				// the order of the reports is part of the call: the bytes of every alignment first, then, for those in use,
+				// trg_start (fg_make_bubbles: trg_start first)
+				const u64 nonGap = stageColumnWalk(name, a, col_off, trg_cols, qry_cols);
 				if (use && !use[a]) continue;		// the positions of an alignment that takes no part are not looked at
 				if (contig_len[i] == 0)
 					throw FgError{FG_ERR_ARG, name + ": alignment " + std::to_string(a) + " is in use on a contig of length 0"};
-				if (trg_start[a] < 0 || trg_start[a] >= contig_len[i])
-					throw FgError{FG_ERR_ARG, name + ": trg_start outside the contig at alignment " + std::to_string(a)};
-				if (nonGap > (u64)contig_len[i])
-					throw FgError{FG_ERR_ARG, name + ": alignment " + std::to_string(a) + " has more target bases than its contig"};
+				stageStartOnContig(name, a, trg_start[a], contig_len[i]);
+				stageBasesOnContig(name, a, nonGap, contig_len[i]);
 			}
 			// a contig counts its columns and its positions
 			cost[i] = (u64)contig_len[i];
 			if (contig_aln_off[i + 1] > contig_aln_off[i]) cost[i] += col_off[contig_aln_off[i + 1]] - col_off[contig_aln_off[i]];
 		}
-		const u64 budget = envU64("FG_CONSENSUS_BATCH_COLS", 1ULL << 27);
-		u64 maxContigs = ~0ULL;			// a switch for tests: contigs per sub-batch
-		if (getenv("FG_CONSENSUS_BATCH_CONTIGS")) maxContigs = std::max<u64>(1, envU64("FG_CONSENSUS_BATCH_CONTIGS", 1));
-		for (u32 i = 0; i < n_contigs; ++i)
-			if (cost[i] > budget)
-				throw FgError{FG_ERR_NOMEM, name + ": contig " + std::to_string(i) + " alone has " + std::to_string(cost[i]) +
-												" columns and positions, FG_CONSENSUS_BATCH_COLS is " + std::to_string(budget)};
+		const u64 budget = stageEnvU64("FG_CONSENSUS_BATCH_COLS", 1ULL << 27);
+		const u64 maxContigs = stageEnvCap("FG_CONSENSUS_BATCH_CONTIGS");		// a switch for tests: contigs per sub-batch
+		stageAllFit(name, "contig", cost, budget, "columns and positions", "FG_CONSENSUS_BATCH_COLS");
 		own = new ConsensusOwner;
 		own->seqOff.assign(1, 0);
 		if (want_profile) { own->profOff.assign(1, 0); own->insOff.assign(1, 0); }
 		HIP_CHECK(hipSetDevice(c->device));
 		c->timer.reset();
-		u32 i = 0;
-		while (i < n_contigs)
+		for (u32 i = 0; i < n_contigs;)
 		{
-			u32 j = i;
-			u64 used = 0;
-			while (j < n_contigs && (j == i || (used + cost[j] <= budget && j - i < maxContigs))) used += cost[j++];
+			const u32 j = stageCut(i, n_contigs, cost, budget, maxContigs);
 			ccSubBatch(c, i, j, contig_len, contig_aln_off, trg_start, qry_id, use, col_off, trg_cols, qry_cols, want_profile != 0, *own);
 			i = j;
 		}
 		c->timer.collect();
-		for (auto* v : {&own->seq, &own->nucl, &own->maxMatch, &own->accepted, &own->ins})
-			if (v->empty()) v->reserve(1);
-		for (auto* v : {&own->matchTotal, &own->numIns})
-			if (v->empty()) v->reserve(1);
-	}
-	catch (const FgError& e) { c->lastError = e.msg; rc = e.code; }
-	catch (const std::bad_alloc&) { c->lastError = "host allocation failed"; rc = FG_ERR_NOMEM; }
-	catch (const std::exception& e) { c->lastError = e.what(); rc = FG_ERR_HIP; }
-	if (rc != FG_OK)
-	{
-		if (c->stream) (void)hipStreamSynchronize(c->stream);
-		c->timer.reset();
-		delete own;
-		return rc;
-	}
-	ccHandOver(out, own, n_contigs, want_profile != 0);
-	return FG_OK;
+		stageKeep(own->seq, own->nucl, own->maxMatch, own->accepted, own->ins, own->matchTotal, own->numIns);
+		ccHandOver(out, own, n_contigs, want_profile != 0);
+	});
 }
 
 int fg_contig_consensus_cigars(fg_ctx* c, uint32_t n_contigs, const uint64_t* contig_off, const uint8_t* contig_seq,
@@ -944,18 +854,12 @@ int fg_contig_consensus_cigars(fg_ctx* c, uint32_t n_contigs, const uint64_t* co
 							   const uint32_t* run_len, const uint64_t* read_off, const uint8_t* read_seq, const int32_t* qry_id,
 							   const uint8_t* use, uint8_t want_profile, struct fg_consensus_batch* out)
 {
-	if (!c) return FG_ERR_ARG;
-	if (out) memset(out, 0, sizeof(*out));
-	ConsensusOwner* own = nullptr;
-	int rc = FG_OK;
-	try
+	return stageCall<ConsensusOwner>(c, out, [&](ConsensusOwner*& own)
 	{
 		const std::string name = "fg_contig_consensus_cigars";
 		if (!out) throw FgError{FG_ERR_ARG, name + ": null result"};
 		if (n_contigs && !contig_aln_off) throw FgError{FG_ERR_ARG, name + ": null contig_aln_off"};
-		for (u32 i = 0; i < n_contigs; ++i)
-			if (contig_aln_off[i + 1] < contig_aln_off[i])
-				throw FgError{FG_ERR_ARG, name + ": contig_aln_off decreases at contig " + std::to_string(i)};
+		stageOffsets(name, "contig_aln_off", "contig ", contig_aln_off, 0, n_contigs);
 		const u64 a0 = n_contigs ? contig_aln_off[0] : 0, a1 = n_contigs ? contig_aln_off[n_contigs] : 0;
 		std::vector<uint32_t> alnContig((size_t)a1, 0);
 		for (u32 i = 0; i < n_contigs; ++i)
@@ -976,19 +880,14 @@ int fg_contig_consensus_cigars(fg_ctx* c, uint32_t n_contigs, const uint64_t* co
 				if (contigLen[i] == 0)
 					throw FgError{FG_ERR_ARG, name + ": alignment " + std::to_string(a) + " is in use on a contig of length 0"};
 				// an alignment of insertions alone may stand behind the last base
-				if (plan.trgStart[a] >= contigLen[i])
-					throw FgError{FG_ERR_ARG, name + ": trg_start outside the contig at alignment " + std::to_string(a)};
+				stageStartOnContig(name, a, plan.trgStart[a], contigLen[i]);
 			}
 			// a contig counts its columns and its positions
 			cost[i] = (u64)contigLen[i] + (plan.colOff[contig_aln_off[i + 1]] - plan.colOff[contig_aln_off[i]]);
 		}
-		const u64 budget = envU64("FG_CONSENSUS_BATCH_COLS", 1ULL << 27);
-		u64 maxContigs = ~0ULL;			// a switch for tests: contigs per sub-batch
-		if (getenv("FG_CONSENSUS_BATCH_CONTIGS")) maxContigs = std::max<u64>(1, envU64("FG_CONSENSUS_BATCH_CONTIGS", 1));
-		for (u32 i = 0; i < n_contigs; ++i)
-			if (cost[i] > budget)
-				throw FgError{FG_ERR_NOMEM, name + ": contig " + std::to_string(i) + " alone has " + std::to_string(cost[i]) +
-												" columns and positions, FG_CONSENSUS_BATCH_COLS is " + std::to_string(budget)};
+		const u64 budget = stageEnvU64("FG_CONSENSUS_BATCH_COLS", 1ULL << 27);
+		const u64 maxContigs = stageEnvCap("FG_CONSENSUS_BATCH_CONTIGS");		// a switch for tests: contigs per sub-batch
+		stageAllFit(name, "contig", cost, budget, "columns and positions", "FG_CONSENSUS_BATCH_COLS");
 		own = new ConsensusOwner;
 		own->seqOff.assign(1, 0);
 		if (want_profile) { own->profOff.assign(1, 0); own->insOff.assign(1, 0); }
@@ -1005,31 +904,11 @@ int fg_contig_consensus_cigars(fg_ctx* c, uint32_t n_contigs, const uint64_t* co
 			i = j;
 		}
 		c->timer.collect();
-		for (auto* v : {&own->seq, &own->nucl, &own->maxMatch, &own->accepted, &own->ins})
-			if (v->empty()) v->reserve(1);
-		for (auto* v : {&own->matchTotal, &own->numIns})
-			if (v->empty()) v->reserve(1);
-	}
-	catch (const FgError& e) { c->lastError = e.msg; rc = e.code; }
-	catch (const std::bad_alloc&) { c->lastError = "host allocation failed"; rc = FG_ERR_NOMEM; }
-	catch (const std::exception& e) { c->lastError = e.what(); rc = FG_ERR_HIP; }
-	if (rc != FG_OK)
-	{
-		// launches of a call that failed half way drain before the context's scratch is used again
-		if (c->stream) (void)hipStreamSynchronize(c->stream);
-		c->timer.reset();
-		delete own;
-		return rc;
-	}
-	ccHandOver(out, own, n_contigs, want_profile != 0);
-	return FG_OK;
+		stageKeep(own->seq, own->nucl, own->maxMatch, own->accepted, own->ins, own->matchTotal, own->numIns);
+		ccHandOver(out, own, n_contigs, want_profile != 0);
+	});
 }
 
-void fg_release_consensus(struct fg_consensus_batch* b)
-{
-	if (!b) return;
-	delete (ConsensusOwner*)b->owner_;
-	memset(b, 0, sizeof(*b));
-}
+void fg_release_consensus(struct fg_consensus_batch* b) { stageRelease<ConsensusOwner>(b); }
 
 } // extern "C"

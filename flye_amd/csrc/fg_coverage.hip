@@ -23,6 +23,7 @@
 // Cost per target of n windows, r intervals and tiles of T: r * ceil(n / T) interval reads, n window updates and
 // n * ceil(log2(max + 1)) <= 31 n value reads for the selection.
 #include "fg_ctx.h"
+#include "fg_stage.h"
 #include "fg_devprim.h"
 
 namespace {
@@ -300,7 +301,7 @@ CovSwitches covSwitches()
 	CovSwitches s{COV_WG_CAP, COV_WAVE_CAP, 1ULL << 20};
 	if (const char* e = getenv("FG_COVERAGE_TILE")) s.tile = atoi(e);
 	if (const char* e = getenv("FG_COVERAGE_WAVE_MAX")) s.waveMax = atoi(e);
-	if (const char* e = getenv("FG_COVERAGE_BATCH_RECS")) s.batchRecs = strtoull(e, nullptr, 10);
+	s.batchRecs = stageEnvU64("FG_COVERAGE_BATCH_RECS", s.batchRecs);
 	s.tile = std::min(std::max(s.tile, 64), COV_WG_CAP);
 	s.waveMax = std::min(std::max(s.waveMax, 0), COV_WAVE_CAP);
 	s.batchRecs = std::min<u64>(std::max<u64>(s.batchRecs, 1), 1ULL << 28);

@@ -20,6 +20,7 @@
 #include <algorithm>
 
 #include "../../include/flye_gpu.h"
+#include "fg_error.h"
 
 typedef uint64_t u64;
 typedef uint32_t u32;
@@ -48,8 +49,6 @@ struct FgTable {
 	unsigned long long keyBase[FG_TABLE_MAX_PARTS];
 	unsigned groups[FG_TABLE_MAX_PARTS];				// 8-slot groups of part p
 };
-
-struct FgError { int code; std::string msg; };
 
 #define HIP_CHECK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { \
 	throw FgError{FG_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_) + \

@@ -19,6 +19,7 @@
 // Integer atomics only: the result does not depend on the schedule.  The host does work proportional to contigs,
 // alignments and (for the byte check) columns.
 #include "fg_ctx.h"
+#include "fg_stage.h"
 #include "fg_devprim.h"
 #include "fg_gapshift.h"
 #include <cmath>
@@ -197,18 +198,6 @@ k_dv_pick(u32 n, const u64* __restrict__ at, const u32* __restrict__ off0, const
 	out[i] = off0[p]; out[n + i] = off1[p]; out[2 * n + i] = off2[p]; out[3 * n + i] = off3[p];
 }
 
-struct DvBufs {
-	fg_ctx* c;
-	int next = 0;
-	template <class T> T* get(size_t count)
-	{
-		if (next >= (int)(sizeof(c->dDv) / sizeof(c->dDv[0]))) throw FgError{FG_ERR_HIP, "internal: fg_divergence buffer pool too small"};
-		DevBuf<char>& b = c->dDv[next++];
-		b.reserve(count * sizeof(T) + 16);
-		return (T*)b.p;
-	}
-};
-
 struct DivergenceOwner {
 	std::vector<uint64_t> listOff[4], profOff;		// total, sub, del, ins
 	std::vector<int32_t> list[4];
@@ -272,7 +261,7 @@ void dvSubBatch(fg_ctx* c, u32 c0, u32 c1, const double* thresh, const int32_t* 
 		for (u32 v = 1; v < nCov; ++v) minCt[(size_t)k * nCov + v] = dvMinCount(thresh[k], v);
 
 	const u64 nCell = nPos * nB;
-	DvBufs B{c};
+	DevPool B{c->dDv, "fg_divergence"};
 	BubAln* dAln = B.get<BubAln>(nAln);
 	DvContig* dCtg = B.get<DvContig>(nC);
 	u64* dCtgAt = B.get<u64>((size_t)nC + 1);
@@ -391,12 +380,6 @@ void dvSubBatch(fg_ctx* c, u32 c0, u32 c1, const double* thresh, const int32_t* 
 	HIP_CHECK(hipStreamSynchronize(s));
 }
 
-u64 dvEnvU64(const char* name, u64 dflt)
-{
-	const char* e = getenv(name);
-	return e ? strtoull(e, nullptr, 10) : dflt;
-}
-
 } // namespace
 
 extern "C" {
@@ -405,47 +388,25 @@ int fg_divergence_profile(fg_ctx* c, double sub_thresh, double del_thresh, doubl
 						  const int32_t* contig_len, const uint64_t* contig_aln_off, const int32_t* trg_start, const uint64_t* col_off,
 						  const uint8_t* trg_cols, const uint8_t* qry_cols, uint8_t want_profile, struct fg_divergence_batch* out)
 {
-	if (!c) return FG_ERR_ARG;
-	if (out) memset(out, 0, sizeof(*out));
-	DivergenceOwner* own = nullptr;
-	int rc = FG_OK;
-	try
+	return stageCall<DivergenceOwner>(c, out, [&](DivergenceOwner*& own)
 	{
 		const std::string name = "fg_divergence_profile";
 		if (!out) throw FgError{FG_ERR_ARG, name + ": null result"};
 		const double thresh[3] = {sub_thresh, del_thresh, ins_thresh};
 		for (double t : thresh)
 			if (!(t >= 0.0)) throw FgError{FG_ERR_ARG, name + ": a threshold that is NaN or negative"};
-		if (n_contigs && (!contig_len || !contig_aln_off)) throw FgError{FG_ERR_ARG, name + ": null contig_len or contig_aln_off"};
-		for (u32 i = 0; i < n_contigs; ++i)
-		{
-			if (contig_len[i] < 0) throw FgError{FG_ERR_ARG, name + ": contig_len < 0 at contig " + std::to_string(i)};
-			if (contig_aln_off[i + 1] < contig_aln_off[i])
-				throw FgError{FG_ERR_ARG, name + ": contig_aln_off decreases at contig " + std::to_string(i)};
-		}
+		stageContigTable(name, n_contigs, contig_len, contig_aln_off);
 		const u64 a0 = n_contigs ? contig_aln_off[0] : 0, a1 = n_contigs ? contig_aln_off[n_contigs] : 0;
 		if (a1 > a0 && (!trg_start || !col_off)) throw FgError{FG_ERR_ARG, name + ": null trg_start or col_off"};
-		for (u64 a = a0; a < a1; ++a)
-		{
-			if (col_off[a + 1] < col_off[a]) throw FgError{FG_ERR_ARG, name + ": col_off decreases at alignment " + std::to_string(a)};
-			if (col_off[a + 1] - col_off[a] >= (1ULL << 31)) throw FgError{FG_ERR_ARG, name + ": an alignment of 2^31 columns"};
-		}
-		if (a1 > a0 && col_off[a1] > col_off[a0] && (!trg_cols || !qry_cols)) throw FgError{FG_ERR_ARG, name + ": null trg_cols or qry_cols"};
+		stageColOff(name, col_off, a0, a1, trg_cols, qry_cols);
 		bool present[128] = {};
 		for (u32 i = 0; i < n_contigs; ++i)
 			for (u64 a = contig_aln_off[i]; a < contig_aln_off[i + 1]; ++a)
 			{
-				u64 nonGap = 0;
-				for (u64 k = col_off[a]; k < col_off[a + 1]; ++k)
-				{
-					if ((trg_cols[k] | qry_cols[k]) >= 128) throw FgError{FG_ERR_ARG, name + ": a byte >= 128 in alignment " + std::to_string(a)};
-					nonGap += trg_cols[k] != '-';
-					present[qry_cols[k]] = true;
-				}
-				if (trg_start[a] < 0 || trg_start[a] >= contig_len[i])
-					throw FgError{FG_ERR_ARG, name + ": trg_start outside the contig at alignment " + std::to_string(a)};
-				if (nonGap > (u64)contig_len[i])
-					throw FgError{FG_ERR_ARG, name + ": alignment " + std::to_string(a) + " has more target bases than its contig"};
+				// the order of the reports is part of the call: the bytes first, then trg_start (fg_make_bubbles: trg_start first)
+				const u64 nonGap = stageColumnWalk(name, a, col_off, trg_cols, qry_cols, present);
+				stageStartOnContig(name, a, trg_start[a], contig_len[i]);
+				stageBasesOnContig(name, a, nonGap, contig_len[i]);
 			}
 		// the query bytes of the call, ranked in byte order: the width of the count tables
 		unsigned char rank[128], byteOf[128] = {};
@@ -461,73 +422,46 @@ int fg_divergence_profile(fg_ctx* c, double sub_thresh, double del_thresh, doubl
 			cost[i] = (u64)contig_len[i] * nB;
 			if (contig_aln_off[i + 1] > contig_aln_off[i]) cost[i] += col_off[contig_aln_off[i + 1]] - col_off[contig_aln_off[i]];
 		}
-		const u64 budget = dvEnvU64("FG_DIVERGENCE_BATCH_COLS", 1ULL << 27);
-		u64 maxContigs = ~0ULL;			// a switch for tests: contigs per sub-batch
-		if (getenv("FG_DIVERGENCE_BATCH_CONTIGS")) maxContigs = std::max<u64>(1, dvEnvU64("FG_DIVERGENCE_BATCH_CONTIGS", 1));
-		for (u32 i = 0; i < n_contigs; ++i)
-			if (cost[i] > budget)
-				throw FgError{FG_ERR_NOMEM, name + ": contig " + std::to_string(i) + " alone has " + std::to_string(cost[i]) +
-												" columns and table cells, FG_DIVERGENCE_BATCH_COLS is " + std::to_string(budget)};
+		const u64 budget = stageEnvU64("FG_DIVERGENCE_BATCH_COLS", 1ULL << 27);
+		const u64 maxContigs = stageEnvCap("FG_DIVERGENCE_BATCH_CONTIGS");
+		stageAllFit(name, "contig", cost, budget, "columns and table cells", "FG_DIVERGENCE_BATCH_COLS");
 		own = new DivergenceOwner;
 		for (auto& v : own->listOff) v.assign(1, 0);
 		if (want_profile) own->profOff.assign(1, 0);
 		HIP_CHECK(hipSetDevice(c->device));
 		c->timer.reset();
-		u32 i = 0;
-		while (i < n_contigs)
+		for (u32 i = 0; i < n_contigs;)
 		{
-			u32 j = i;
-			u64 used = 0;
-			while (j < n_contigs && (j == i || (used + cost[j] <= budget && j - i < maxContigs))) used += cost[j++];
+			const u32 j = stageCut(i, n_contigs, cost, budget, maxContigs);
 			dvSubBatch(c, i, j, thresh, contig_len, contig_aln_off, trg_start, col_off, trg_cols, qry_cols, rank, byteOf, nB, want_profile != 0, *own);
 			i = j;
 		}
 		c->timer.collect();
-		for (auto& v : own->list)
-			if (v.empty()) v.reserve(1);
-		for (auto* v : {&own->cov, &own->matCt, &own->subCt, &own->delCt, &own->insCt})
-			if (v->empty()) v->reserve(1);
-		for (auto* v : {&own->nucl, &own->subBase, &own->insBase, &own->flags})
-			if (v->empty()) v->reserve(1);
-	}
-	catch (const FgError& e) { c->lastError = e.msg; rc = e.code; }
-	catch (const std::bad_alloc&) { c->lastError = "host allocation failed"; rc = FG_ERR_NOMEM; }
-	catch (const std::exception& e) { c->lastError = e.what(); rc = FG_ERR_HIP; }
-	if (rc != FG_OK)
-	{
-		// launches of a call that failed half way drain before the context's scratch is used again
-		if (c->stream) (void)hipStreamSynchronize(c->stream);
-		c->timer.reset();
-		delete own;
-		return rc;
-	}
-	out->n_contigs = n_contigs;
-	out->total_off = own->listOff[0].data(); out->total_pos = own->list[0].data();
-	out->sub_off = own->listOff[1].data(); out->sub_pos = own->list[1].data();
-	out->del_off = own->listOff[2].data(); out->del_pos = own->list[2].data();
-	out->ins_off = own->listOff[3].data(); out->ins_pos = own->list[3].data();
-	if (want_profile)
-	{
-		out->prof_off = own->profOff.data();
-		out->cov = own->cov.data();
-		out->nucl = own->nucl.data();
-		out->mat_ct = own->matCt.data();
-		out->sub_base = own->subBase.data();
-		out->sub_ct = own->subCt.data();
-		out->del_ct = own->delCt.data();
-		out->ins_base = own->insBase.data();
-		out->ins_ct = own->insCt.data();
-		out->flags = own->flags.data();
-	}
-	out->owner_ = own;
-	return FG_OK;
+		for (auto& v : own->list) stageKeep(v);
+		stageKeep(own->cov, own->matCt, own->subCt, own->delCt, own->insCt, own->nucl, own->subBase, own->insBase, own->flags);
+
+		out->n_contigs = n_contigs;
+		out->total_off = own->listOff[0].data(); out->total_pos = own->list[0].data();
+		out->sub_off = own->listOff[1].data(); out->sub_pos = own->list[1].data();
+		out->del_off = own->listOff[2].data(); out->del_pos = own->list[2].data();
+		out->ins_off = own->listOff[3].data(); out->ins_pos = own->list[3].data();
+		if (want_profile)
+		{
+			out->prof_off = own->profOff.data();
+			out->cov = own->cov.data();
+			out->nucl = own->nucl.data();
+			out->mat_ct = own->matCt.data();
+			out->sub_base = own->subBase.data();
+			out->sub_ct = own->subCt.data();
+			out->del_ct = own->delCt.data();
+			out->ins_base = own->insBase.data();
+			out->ins_ct = own->insCt.data();
+			out->flags = own->flags.data();
+		}
+		out->owner_ = own;
+	});
 }
 
-void fg_release_divergence(struct fg_divergence_batch* b)
-{
-	if (!b) return;
-	delete (DivergenceOwner*)b->owner_;
-	memset(b, 0, sizeof(*b));
-}
+void fg_release_divergence(struct fg_divergence_batch* b) { stageRelease<DivergenceOwner>(b); }
 
 } // extern "C"

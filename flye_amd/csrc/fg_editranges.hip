@@ -7,6 +7,7 @@
 // into the primaries and the per-call query array the edit kernels read, and k_edit_range_collect packs what they
 // left into three dense int32 arrays (12 B per pair come back).  No PrimRec is built on or copied to the host.
 #include "fg_ctx.h"
+#include "fg_stage.h"
 
 namespace {
 
@@ -64,8 +65,7 @@ void fgEditRanges(fg_ctx* c, const std::vector<FgRangeSide>& sides, bool useHpc,
 	const u64 nPairs = sides.size() / 2;
 	if (!nPairs) return;
 	hipStream_t s = c->stream;
-	u64 batch = 1ULL << 20;
-	if (const char* e = getenv("FG_EDIT_BATCH_PAIRS")) batch = strtoull(e, nullptr, 10);
+	u64 batch = stageEnvU64("FG_EDIT_BATCH_PAIRS", 1ULL << 20);
 	batch = std::min<u64>(std::max<u64>(batch, 1), 1ULL << 26);		// fgEditDistances' lists index a sub-batch with 32 bits
 	const u64 cap = std::min(batch, nPairs);
 	c->dRangeSides.reserve(2 * cap * sizeof(FgRangeSide));

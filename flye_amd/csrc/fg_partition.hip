@@ -26,6 +26,7 @@
 // Integer atomics only: the result does not depend on the schedule.  The host does work proportional to jobs, edges,
 // alignments and (for the byte check) columns.
 #include "fg_ctx.h"
+#include "fg_stage.h"
 #include "fg_devprim.h"
 #include "fg_gapshift.h"
 
@@ -314,28 +315,10 @@ k_cl_vote(u32 nReads, const u64* __restrict__ readAt, u32 nJ, const u32* __restr
 }
 
 // ---- the host ---------------------------------------------------------------------------------------------------
-struct PtBufs {
-	fg_ctx* c;
-	int next = 0;
-	template <class T> T* get(size_t count)
-	{
-		if (next >= (int)(sizeof(c->dPt) / sizeof(c->dPt[0]))) throw FgError{FG_ERR_HIP, "internal: fg_partition buffer pool too small"};
-		DevBuf<char>& b = c->dPt[next++];
-		b.reserve(count * sizeof(T) + 16);
-		return (T*)b.p;
-	}
-};
-
 template <class T>
 void ptUp(hipStream_t s, T* dst, const std::vector<T>& src)
 {
 	if (!src.empty()) HIP_CHECK(hipMemcpyAsync(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, s));
-}
-
-u64 ptEnvU64(const char* name, u64 dflt)
-{
-	const char* e = getenv(name);
-	return e ? strtoull(e, nullptr, 10) : dflt;
 }
 
 struct PtCut { u64 budget, maxJobs; u32 tileShift; };
@@ -343,9 +326,9 @@ struct PtCut { u64 budget, maxJobs; u32 tileShift; };
 PtCut ptCut(const std::string& name)
 {
 	PtCut cut;
-	cut.budget = ptEnvU64("FG_PARTITION_BATCH_COLS", 1ULL << 27);
-	cut.maxJobs = getenv("FG_PARTITION_BATCH_JOBS") ? std::max<u64>(1, ptEnvU64("FG_PARTITION_BATCH_JOBS", 1)) : ~0ULL;
-	const u64 tile = ptEnvU64("FG_PARTITION_TILE", 1024);
+	cut.budget = stageEnvU64("FG_PARTITION_BATCH_COLS", 1ULL << 27);
+	cut.maxJobs = stageEnvCap("FG_PARTITION_BATCH_JOBS");
+	const u64 tile = stageEnvU64("FG_PARTITION_TILE", 1024);
 	if (tile < 64 || tile > 4096 || (tile & (tile - 1)))
 		throw FgError{FG_ERR_ARG, name + ": FG_PARTITION_TILE is " + std::to_string(tile) + ", not a power of two in 64 .. 4096"};
 	cut.tileShift = 0;
@@ -358,12 +341,7 @@ void ptCheckColumns(const std::string& name, u64 a, const int32_t* trgStart, con
 					const uint8_t* trgCols, const uint8_t* qryCols)
 {
 	if (trgStart[a] < 0) throw FgError{FG_ERR_ARG, name + ": trg_start < 0 at alignment " + std::to_string(a)};
-	u64 nonGap = 0;
-	for (u64 k = colOff[a]; k < colOff[a + 1]; ++k)
-	{
-		if ((trgCols[k] | qryCols[k]) >= 128) throw FgError{FG_ERR_ARG, name + ": a byte >= 128 in alignment " + std::to_string(a)};
-		nonGap += trgCols[k] != '-';
-	}
+	const u64 nonGap = stageColumnWalk(name, a, colOff, trgCols, qryCols);
 	if ((long long)nonGap != (long long)trgEnd[a] - (long long)trgStart[a])
 		throw FgError{FG_ERR_ARG, name + ": alignment " + std::to_string(a) + " has " + std::to_string(nonGap) +
 									  " non-gap target columns, trg_end - trg_start is " +
@@ -442,7 +420,7 @@ void cfSubBatch(fg_ctx* c, u32 j0, u32 j1, const ConfirmIn& in, const std::vecto
 		throw FgError{FG_ERR_NOMEM, "fg_confirm_positions: a sub-batch of 2^31 positions, columns or list entries; lower FG_PARTITION_BATCH_COLS"};
 	segOff[(size_t)4 * nJ] = (u32)nEntries;
 
-	PtBufs B{c};
+	DevPool B{c->dPt, "fg_partition"};
 	CfJob* dJobs = B.get<CfJob>(nJ);
 	u64* dJobAt = B.get<u64>((size_t)nJ + 1);
 	u64* dSlotAt = B.get<u64>((size_t)nE + 1);
@@ -630,7 +608,7 @@ void clSubBatch(fg_ctx* c, u32 j0, u32 j1, const ClassifyIn& in, const std::vect
 	while ((1ULL << eBits) < nE) ++eBits;
 	while ((1ULL << rBits) < nReads) ++rBits;
 
-	PtBufs B{c};
+	DevPool B{c->dPt, "fg_partition"};
 	u64* dReadAt = B.get<u64>((size_t)nJ + 1);
 	u64* dEdgePosAt = B.get<u64>((size_t)nE + 1);
 	u32* dJobEdge0 = B.get<u32>(nJ);
@@ -721,23 +699,13 @@ void clSubBatch(fg_ctx* c, u32 j0, u32 j1, const ClassifyIn& in, const std::vect
 	HIP_CHECK(hipStreamSynchronize(s));
 }
 
-void ptOffsets(const std::string& name, const char* what, const uint64_t* off, u64 lo, u64 hi)
+// col_off over the alignments lo .. hi.  Both calls report every decrease before any width: not stageColOff's order.
+void ptColOff(const std::string& name, const uint64_t* colOff, u64 lo, u64 hi, const uint8_t* trgCols, const uint8_t* qryCols)
 {
-	for (u64 i = lo; i < hi; ++i)
-		if (off[i + 1] < off[i]) throw FgError{FG_ERR_ARG, name + ": " + what + " decreases at " + std::to_string(i)};
+	stageOffsets(name, "col_off", "", colOff, lo, hi);
+	for (u64 a = lo; a < hi; ++a) stageColWidth(name, colOff, a);
+	stageColsGiven(name, colOff, lo, hi, trgCols, qryCols);
 }
-
-// whole jobs per sub-batch: [i, next)
-u32 ptNext(u32 i, u32 n, const std::vector<u64>& cost, const PtCut& cut)
-{
-	u32 j = i;
-	u64 used = 0;
-	while (j < n && (j == i || (used + cost[j] <= cut.budget && j - i < cut.maxJobs))) used += cost[j++];
-	return j;
-}
-
-template <class V>
-void ptKeep(V& v) { if (v.empty()) v.reserve(1); }
 
 } // namespace
 
@@ -749,13 +717,9 @@ int fg_confirm_positions(fg_ctx* c, uint32_t n_jobs, const uint8_t* side, const 
 						 const int32_t* sub_pos, const uint64_t* del_off, const int32_t* del_pos, const uint64_t* ins_off,
 						 const int32_t* ins_pos, struct fg_confirm_batch* out)
 {
-	if (!c) return FG_ERR_ARG;
-	if (out) memset(out, 0, sizeof(*out));
-	ConfirmOwner* own = nullptr;
-	int rc = FG_OK;
-	u64 nEdges = 0;
-	try
+	return stageCall<ConfirmOwner>(c, out, [&](ConfirmOwner*& own)
 	{
+		u64 nEdges = 0;
 		const std::string name = "fg_confirm_positions";
 		if (!out) throw FgError{FG_ERR_ARG, name + ": null result"};
 		const PtCut cut = ptCut(name);
@@ -767,19 +731,16 @@ int fg_confirm_positions(fg_ctx* c, uint32_t n_jobs, const uint8_t* side, const 
 		{
 			if (!side || !job_edge_off || !trg_start || !trg_end || !qry_start || !col_off)
 				throw FgError{FG_ERR_ARG, name + ": null side, job_edge_off, trg_start, trg_end, qry_start or col_off"};
-			ptOffsets(name, "job_edge_off", job_edge_off, 0, n_jobs);
+			stageOffsets(name, "job_edge_off", "", job_edge_off, 0, n_jobs);
 			for (int k = 0; k < 4; ++k)
 			{
 				if (!in.listOff[k]) throw FgError{FG_ERR_ARG, name + ": null offsets of a tentative list"};
-				ptOffsets(name, "a tentative list's offset array", in.listOff[k], 0, n_jobs);
+				stageOffsets(name, "a tentative list's offset array", "", in.listOff[k], 0, n_jobs);
 				if (in.listOff[k][n_jobs] > in.listOff[k][0] && !in.listPos[k]) throw FgError{FG_ERR_ARG, name + ": null positions of a tentative list"};
 			}
 			const u64 e0 = job_edge_off[0], e1 = job_edge_off[n_jobs];
 			nEdges = e1 - e0;
-			ptOffsets(name, "col_off", col_off, e0, e1);
-			for (u64 e = e0; e < e1; ++e)
-				if (col_off[e + 1] - col_off[e] >= (1ULL << 31)) throw FgError{FG_ERR_ARG, name + ": an alignment of 2^31 columns"};
-			if (e1 > e0 && col_off[e1] > col_off[e0] && (!trg_cols || !qry_cols)) throw FgError{FG_ERR_ARG, name + ": null trg_cols or qry_cols"};
+			ptColOff(name, col_off, e0, e1, trg_cols, qry_cols);
 			for (u32 j = 0; j < n_jobs; ++j)
 			{
 				if (side[j] > 1) throw FgError{FG_ERR_ARG, name + ": side > 1 at job " + std::to_string(j)};
@@ -794,9 +755,7 @@ int fg_confirm_positions(fg_ctx* c, uint32_t n_jobs, const uint8_t* side, const 
 					jb.minEnd = std::min(jb.minEnd, trg_end[e]); jb.maxEnd = std::max(jb.maxEnd, trg_end[e]);
 				}
 				cost[j] = col_off[job_edge_off[j + 1]] - col_off[job_edge_off[j]] + (u64)((long long)jb.maxEnd - jb.minStart);
-				if (cost[j] > cut.budget)
-					throw FgError{FG_ERR_NOMEM, name + ": job " + std::to_string(j) + " alone has " + std::to_string(cost[j]) +
-													" columns and table cells, FG_PARTITION_BATCH_COLS is " + std::to_string(cut.budget)};
+				stageFits(name, "job", j, cost[j], cut.budget, "columns and table cells", "FG_PARTITION_BATCH_COLS");
 			}
 		}
 		own = new ConfirmOwner;
@@ -806,57 +765,36 @@ int fg_confirm_positions(fg_ctx* c, uint32_t n_jobs, const uint8_t* side, const 
 		c->timer.reset();
 		for (u32 i = 0; i < n_jobs;)
 		{
-			const u32 j = ptNext(i, n_jobs, cost, cut);
+			const u32 j = stageCut(i, n_jobs, cost, cut.budget, cut.maxJobs);
 			cfSubBatch(c, i, j, in, jobs, cut.tileShift, *own);
 			i = j;
 		}
 		c->timer.collect();
-		for (auto& v : own->list) ptKeep(v);
-		ptKeep(own->cons);
-	}
-	catch (const FgError& e) { c->lastError = e.msg; rc = e.code; }
-	catch (const std::bad_alloc&) { c->lastError = "host allocation failed"; rc = FG_ERR_NOMEM; }
-	catch (const std::exception& e) { c->lastError = e.what(); rc = FG_ERR_HIP; }
-	if (rc != FG_OK)
-	{
-		// launches of a call that failed half way drain before the context's scratch is used again
-		if (c->stream) (void)hipStreamSynchronize(c->stream);
-		c->timer.reset();
-		delete own;
-		return rc;
-	}
-	out->n_jobs = n_jobs;
-	out->n_edges = nEdges;
-	uint64_t** offs[8] = {&out->conf_total_off, &out->conf_sub_off, &out->conf_del_off, &out->conf_ins_off,
-						  &out->rej_total_off, &out->rej_sub_off, &out->rej_del_off, &out->rej_ins_off};
-	int32_t** poss[8] = {&out->conf_total_pos, &out->conf_sub_pos, &out->conf_del_pos, &out->conf_ins_pos,
-						 &out->rej_total_pos, &out->rej_sub_pos, &out->rej_del_pos, &out->rej_ins_pos};
-	for (int k = 0; k < 8; ++k) { *offs[k] = own->listOff[k].data(); *poss[k] = own->list[k].data(); }
-	out->cons_off = own->consOff.data();
-	out->cons_pos = own->cons.data();
-	out->owner_ = own;
-	return FG_OK;
+		for (auto& v : own->list) stageKeep(v);
+		stageKeep(own->cons);
+		out->n_jobs = n_jobs;
+		out->n_edges = nEdges;
+		uint64_t** offs[8] = {&out->conf_total_off, &out->conf_sub_off, &out->conf_del_off, &out->conf_ins_off,
+							  &out->rej_total_off, &out->rej_sub_off, &out->rej_del_off, &out->rej_ins_off};
+		int32_t** poss[8] = {&out->conf_total_pos, &out->conf_sub_pos, &out->conf_del_pos, &out->conf_ins_pos,
+							 &out->rej_total_pos, &out->rej_sub_pos, &out->rej_del_pos, &out->rej_ins_pos};
+		for (int k = 0; k < 8; ++k) { *offs[k] = own->listOff[k].data(); *poss[k] = own->list[k].data(); }
+		out->cons_off = own->consOff.data();
+		out->cons_pos = own->cons.data();
+		out->owner_ = own;
+	});
 }
 
-void fg_release_confirm(struct fg_confirm_batch* b)
-{
-	if (!b) return;
-	delete (ConfirmOwner*)b->owner_;
-	memset(b, 0, sizeof(*b));
-}
+void fg_release_confirm(struct fg_confirm_batch* b) { stageRelease<ConfirmOwner>(b); }
 
 int fg_classify_reads(fg_ctx* c, int32_t buffer_count, uint32_t n_jobs, const uint64_t* job_edge_off, const uint32_t* job_n_reads,
 					  const uint64_t* edge_pos_off, const int32_t* edge_pos, const uint64_t* edge_aln_off, const uint32_t* read,
 					  const int32_t* trg_start, const int32_t* trg_end, const uint64_t* col_off, const uint8_t* trg_cols,
 					  const uint8_t* qry_cols, uint8_t want_scores, struct fg_classify_batch* out)
 {
-	if (!c) return FG_ERR_ARG;
-	if (out) memset(out, 0, sizeof(*out));
-	ClassifyOwner* own = nullptr;
-	int rc = FG_OK;
-	u64 nAlns = 0;
-	try
+	return stageCall<ClassifyOwner>(c, out, [&](ClassifyOwner*& own)
 	{
+		u64 nAlns = 0;
 		const std::string name = "fg_classify_reads";
 		if (!out) throw FgError{FG_ERR_ARG, name + ": null result"};
 		if (buffer_count < 0) throw FgError{FG_ERR_ARG, name + ": buffer_count < 0"};
@@ -869,18 +807,15 @@ int fg_classify_reads(fg_ctx* c, int32_t buffer_count, uint32_t n_jobs, const ui
 		{
 			if (!job_edge_off || !job_n_reads || !edge_pos_off || !edge_aln_off)
 				throw FgError{FG_ERR_ARG, name + ": null job_edge_off, job_n_reads, edge_pos_off or edge_aln_off"};
-			ptOffsets(name, "job_edge_off", job_edge_off, 0, n_jobs);
+			stageOffsets(name, "job_edge_off", "", job_edge_off, 0, n_jobs);
 			const u64 e0 = job_edge_off[0], e1 = job_edge_off[n_jobs];
-			ptOffsets(name, "edge_pos_off", edge_pos_off, e0, e1);
-			ptOffsets(name, "edge_aln_off", edge_aln_off, e0, e1);
+			stageOffsets(name, "edge_pos_off", "", edge_pos_off, e0, e1);
+			stageOffsets(name, "edge_aln_off", "", edge_aln_off, e0, e1);
 			if (edge_pos_off[e1] > edge_pos_off[e0] && !edge_pos) throw FgError{FG_ERR_ARG, name + ": null edge_pos"};
 			const u64 a0 = edge_aln_off[e0], a1 = edge_aln_off[e1];
 			nAlns = a1 - a0;
 			if (a1 > a0 && (!read || !trg_start || !trg_end || !col_off)) throw FgError{FG_ERR_ARG, name + ": null read, trg_start, trg_end or col_off"};
-			ptOffsets(name, "col_off", col_off, a0, a1);
-			for (u64 a = a0; a < a1; ++a)
-				if (col_off[a + 1] - col_off[a] >= (1ULL << 31)) throw FgError{FG_ERR_ARG, name + ": an alignment of 2^31 columns"};
-			if (a1 > a0 && col_off[a1] > col_off[a0] && (!trg_cols || !qry_cols)) throw FgError{FG_ERR_ARG, name + ": null trg_cols or qry_cols"};
+			ptColOff(name, col_off, a0, a1, trg_cols, qry_cols);
 			edges.resize(e1 - e0);
 			for (u32 j = 0; j < n_jobs; ++j)
 			{
@@ -905,9 +840,7 @@ int fg_classify_reads(fg_ctx* c, int32_t buffer_count, uint32_t n_jobs, const ui
 				cost[j] = cells;
 				if (edge_aln_off[job_edge_off[j + 1]] > edge_aln_off[job_edge_off[j]])
 					cost[j] += col_off[edge_aln_off[job_edge_off[j + 1]]] - col_off[edge_aln_off[job_edge_off[j]]];
-				if (cost[j] > cut.budget)
-					throw FgError{FG_ERR_NOMEM, name + ": job " + std::to_string(j) + " alone has " + std::to_string(cost[j]) +
-													" columns and table cells, FG_PARTITION_BATCH_COLS is " + std::to_string(cut.budget)};
+				stageFits(name, "job", j, cost[j], cut.budget, "columns and table cells", "FG_PARTITION_BATCH_COLS");
 			}
 		}
 		own = new ClassifyOwner;
@@ -916,45 +849,28 @@ int fg_classify_reads(fg_ctx* c, int32_t buffer_count, uint32_t n_jobs, const ui
 		c->timer.reset();
 		for (u32 i = 0; i < n_jobs;)
 		{
-			const u32 j = ptNext(i, n_jobs, cost, cut);
+			const u32 j = stageCut(i, n_jobs, cost, cut.budget, cut.maxJobs);
 			clSubBatch(c, i, j, in, edges, cut.tileShift, want_scores != 0, *own);
 			i = j;
 		}
 		c->timer.collect();
-		ptKeep(own->status); ptKeep(own->topEdge); ptKeep(own->topScore); ptKeep(own->totalScore);
-		ptKeep(own->alnScore); ptKeep(own->counted);
-	}
-	catch (const FgError& e) { c->lastError = e.msg; rc = e.code; }
-	catch (const std::bad_alloc&) { c->lastError = "host allocation failed"; rc = FG_ERR_NOMEM; }
-	catch (const std::exception& e) { c->lastError = e.what(); rc = FG_ERR_HIP; }
-	if (rc != FG_OK)
-	{
-		if (c->stream) (void)hipStreamSynchronize(c->stream);
-		c->timer.reset();
-		delete own;
-		return rc;
-	}
-	out->n_jobs = n_jobs;
-	out->n_alignments = nAlns;
-	out->read_off = own->readOff.data();
-	out->status = own->status.data();
-	out->top_edge = own->topEdge.data();
-	out->top_score = own->topScore.data();
-	out->total_score = own->totalScore.data();
-	if (want_scores)
-	{
-		out->aln_score = own->alnScore.data();
-		out->aln_counted = own->counted.data();
-	}
-	out->owner_ = own;
-	return FG_OK;
+		stageKeep(own->status, own->topEdge, own->topScore, own->totalScore, own->alnScore, own->counted);
+		out->n_jobs = n_jobs;
+		out->n_alignments = nAlns;
+		out->read_off = own->readOff.data();
+		out->status = own->status.data();
+		out->top_edge = own->topEdge.data();
+		out->top_score = own->topScore.data();
+		out->total_score = own->totalScore.data();
+		if (want_scores)
+		{
+			out->aln_score = own->alnScore.data();
+			out->aln_counted = own->counted.data();
+		}
+		out->owner_ = own;
+	});
 }
 
-void fg_release_classify(struct fg_classify_batch* b)
-{
-	if (!b) return;
-	delete (ClassifyOwner*)b->owner_;
-	memset(b, 0, sizeof(*b));
-}
+void fg_release_classify(struct fg_classify_batch* b) { stageRelease<ClassifyOwner>(b); }
 
 } // extern "C"

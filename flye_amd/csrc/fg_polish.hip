@@ -22,6 +22,7 @@
 // Scratch per item: 8 bytes per cell of F and of R, (L + 1) * (Lb + 1) cells per branch each, plus 72 (L + 1) for the
 // edit sums.
 #include "fg_ctx.h"
+#include "fg_stage.h"
 #include "../../include/introsort_emul.h"
 
 namespace {
@@ -327,10 +328,8 @@ void fgPolishBubbles(fg_ctx* c, const int64_t* score36, const uint8_t* cand, con
 	steps.clear(); steps.resize(wantSteps ? nBubbles : 0);
 	if (!nBubbles) return;
 	hipStream_t s = c->stream;
-	u64 budget = 8ULL << 30;
-	if (const char* e = getenv("FG_POLISH_SCRATCH_BYTES")) budget = strtoull(e, nullptr, 10);
-	u64 maxItems = ~0ULL;			// a switch for tests: bubbles at work per chunk
-	if (const char* e = getenv("FG_POLISH_BATCH_BUBBLES")) maxItems = std::max<u64>(1, strtoull(e, nullptr, 10));
+	const u64 budget = stageEnvU64("FG_POLISH_SCRATCH_BYTES", 8ULL << 30);
+	const u64 maxItems = stageEnvCap("FG_POLISH_BATCH_BUBBLES");		// a switch for tests: bubbles at work per chunk
 	const u64 br0 = bubbleBranchOff[0], nBr = bubbleBranchOff[nBubbles] - br0;
 	const u64 byte0 = nBr ? branchOff[br0] : 0, nBytes = nBr ? branchOff[br0 + nBr] - byte0 : 0;
 	if (nBr >= (1ULL << 32)) throw FgError{FG_ERR_ARG, "fg_polish_bubbles: more than 2^32 - 1 branches in one call"};

@@ -20,6 +20,7 @@
 // every array).  A block is one wave; the lists a wave's lanes hand to one another go through that scratch with a
 // workgroup barrier between the store and the loads that follow.  Every loop is bounded by the query's record count.
 #include "fg_ctx.h"
+#include "fg_stage.h"
 #include "fg_devprim.h"
 
 namespace {
@@ -336,8 +337,7 @@ void fgChainAlignments(fg_ctx* c, const fg_chain_params& p, const std::vector<Fg
 	aln.clear(); score.clear();
 	if (!nq || tab.empty()) return;
 	hipStream_t s = c->stream;
-	u64 batch = 1ULL << 20;
-	if (const char* e = getenv("FG_READCHAIN_BATCH_RECS")) batch = strtoull(e, nullptr, 10);
+	u64 batch = stageEnvU64("FG_READCHAIN_BATCH_RECS", 1ULL << 20);
 	batch = std::min<u64>(std::max<u64>(batch, 1), 1ULL << 28);
 	c->timer.reset();
 	c->dRcNodes.reserve(2 * (size_t)nExt);

@@ -16,6 +16,7 @@
 // of the two converted integers (what the host's division gives); the float a record carries is made by the host
 // shim from the two integers.
 #include "fg_ctx.h"
+#include "fg_stage.h"
 #include "fg_devprim.h"
 
 namespace {
@@ -327,7 +328,7 @@ void fgTrimRanges(fg_ctx* c, const std::vector<FgRangeSide>& sides, bool useHpc,
 	recs.clear();
 	if (!nPairs) return;
 	c->timer.reset();
-	const u64 budget = getenv("FG_TRIM_SCRATCH_BYTES") ? strtoull(getenv("FG_TRIM_SCRATCH_BYTES"), nullptr, 10) : (1ULL << 30);
+	const u64 budget = stageEnvU64("FG_TRIM_SCRATCH_BYTES", 1ULL << 30);
 	const bool trace = getenv("FG_TRIM_TRACE") != nullptr;
 	const TrimSeqs S{c->dQWords.p, c->dQWordOff.p, c->dQLen.p, c->dWords.p, c->dWordOff.p, c->dLen.p};
 	std::vector<u32> keptAll(nPairs, 0);
