@@ -670,6 +670,34 @@ int fg_debug_probe_skip_check(fg_ctx* c, uint64_t* clear_bits, uint64_t* violati
 	});
 }
 
+int fg_debug_table(fg_ctx* c, uint32_t* wide, uint32_t* n_parts, uint64_t* n_slots, uint64_t* bound, uint64_t* slot_base,
+				   uint64_t* key_base, uint32_t* groups, uint64_t* slots)
+{
+	if (!c) return FG_ERR_ARG;
+	return guarded(c, [&]()
+	{
+		HIP_CHECK(hipSetDevice(c->device));
+		if (!c->indexBuilt) throw FgError{FG_ERR_STATE, "no index"};
+		const FgTable& T = c->table;
+		if (wide) *wide = c->tableWide ? 1u : 0u;
+		if (n_parts) *n_parts = T.nParts;
+		if (n_slots) *n_slots = c->tableSlots;
+		for (u32 p = 0; p < T.nParts; ++p)
+		{
+			if (bound) bound[p] = T.bound[p];
+			if (slot_base) slot_base[p] = T.slotBase[p];
+			if (key_base) key_base[p] = T.keyBase[p];
+			if (groups) groups[p] = T.groups[p];
+		}
+		if (bound) bound[T.nParts] = T.bound[T.nParts];
+		if (slots && c->tableSlots)
+		{
+			HIP_CHECK(hipMemcpyAsync(slots, c->dTable.p, c->tableSlots * (c->tableWide ? 16 : 8), hipMemcpyDeviceToHost, c->stream));
+			HIP_CHECK(hipStreamSynchronize(c->stream));
+		}
+	});
+}
+
 int fg_debug_chain_lazy(fg_ctx* c, uint64_t out[6])
 {
 	if (!c || !out) return FG_ERR_ARG;

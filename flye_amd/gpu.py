@@ -78,7 +78,7 @@ ABI_SYMBOLS = ["fg_abi_version", "fg_create", "fg_destroy", "fg_strerror", "fg_l
                "fg_group_build_index_minimizers", "fg_group_clear_index", "fg_group_overlaps", "fg_group_stats",
                "fg_group_build_info", "fg_debug_freq_accumulate", "fg_debug_group_bin_cuts", "fg_debug_scan",
                "fg_debug_radix_sort_pairs", "fg_debug_tie_free", "fg_debug_chain_lazy", "fg_debug_sort_screen",
-               "fg_debug_order_free", "fg_debug_sort_radix_segments"]
+               "fg_debug_order_free", "fg_debug_sort_radix_segments", "fg_debug_table"]
 
 # struct fg_range_pair: one pair of fg_align_ranges
 RANGE_PAIR_DTYPE = np.dtype([("cur_id", "<u4"), ("ext_id", "<u4"), ("cur_begin", "<i4"), ("cur_end", "<i4"),
@@ -378,6 +378,8 @@ def load_library():
         L.fg_debug_sort_radix_segments.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.fg_debug_probe_skip_check.argtypes =[C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.fg_debug_chain_lazy.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        L.fg_debug_table.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.fg_debug_edit_distances.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.fg_align_cigar_ksw.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.POINTER(CigarBatch)]
@@ -965,6 +967,22 @@ class Context:
         clear, bad = C.c_uint64(0), C.c_uint64(0)
         self._check(self.L.fg_debug_probe_skip_check(self.h, C.byref(clear), C.byref(bad)))
         return int(clear.value), int(bad.value)
+
+    def debug_table(self):
+        """The lookup table of the context's index (fg_debug_table): dict of ``wide``, ``n_parts``, ``n_slots``, the
+        per-part ``bound`` (n_parts + 1), ``slot_base``, ``key_base``, ``groups`` and ``slots``: the slot words, or for
+        the wide form an (n_slots, 2) array of (key, key index)."""
+        wide, parts, n = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)
+        self._check(self.L.fg_debug_table(self.h, C.byref(wide), C.byref(parts), C.byref(n), None, None, None, None, None))
+        p = int(parts.value)
+        bound, base, kbase = np.zeros(p + 1, np.uint64), np.zeros(p, np.uint64), np.zeros(p, np.uint64)
+        groups = np.zeros(p, np.uint32)
+        slots = np.zeros(max(1, int(n.value) * (2 if wide.value else 1)), np.uint64)
+        self._check(self.L.fg_debug_table(self.h, None, None, None, bound.ctypes.data, base.ctypes.data, kbase.ctypes.data,
+                                          groups.ctypes.data, slots.ctypes.data))
+        slots = slots[:int(n.value) * (2 if wide.value else 1)]
+        return dict(wide=bool(wide.value), n_parts=p, n_slots=int(n.value), bound=bound, slot_base=base, key_base=kbase,
+                    groups=groups, slots=slots.reshape(-1, 2) if wide.value else slots)
 
     def debug_chain_lazy(self):
         """How the groups of the last fg_overlaps call left the chaining stage's backtracking: dict of ``entered``,

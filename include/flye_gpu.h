@@ -509,6 +509,18 @@ int fg_debug_radix_sort_pairs(fg_ctx* ctx, uint64_t* keys, uint64_t* vals, uint6
  * k-mer is then looked up.  The environment switch FG_PROBE_SKIP=0 makes the overlap stage ignore the bits. */
 int fg_debug_probe_skip_check(fg_ctx* ctx, uint64_t* clear_bits, uint64_t* violations);
 
+/* Test hook (read only): the k-mer lookup table of the context's index as the kernels see it.  *wide = 1 for the
+ * {key, key index} pair form (k >= 18), 0 for the one-word form (key << 30 | key index inside the part, all ones in
+ * the index bits = a repetitive k-mer); *n_parts = key-range parts (at most FG_DEBUG_TABLE_MAX_PARTS); *n_slots =
+ * slots over all parts.  Part p holds the keys in [bound[p], bound[p + 1]) (bound: *n_parts + 1 values) in groups[p]
+ * 8-slot groups that start at slot slot_base[p]; the index a one-word slot stores counts from key key_base[p] of the
+ * sorted key array.  slots: a copy of the slot array, *n_slots words, or 2 * *n_slots for the pair form (key, then key
+ * index or all ones for a repetitive k-mer); an empty slot is all ones.  Every output pointer may be null: a call
+ * with null arrays asks for the sizes.  FG_ERR_STATE without an index. */
+#define FG_DEBUG_TABLE_MAX_PARTS 16
+int fg_debug_table(fg_ctx* ctx, uint32_t* wide, uint32_t* n_parts, uint64_t* n_slots, uint64_t* bound,
+                   uint64_t* slot_base, uint64_t* key_base, uint32_t* groups, uint64_t* slots);
+
 /* Test hook for the lazy primary of the chaining stage (only_max_ext): how the groups of the last fg_overlaps call on
  * this context left the backtracking stage.  out[0]: groups that reached it (through the prefilter and the DP);
  * out[1]: groups whose primary was taken straight from the DP tables -- the live element of the strictly largest

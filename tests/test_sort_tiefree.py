@@ -22,6 +22,8 @@ import sys
 import numpy as np
 import pytest
 
+from helpers import cpu_seed_hits as _cpu_seed_hits
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SORT_CAP = 448          # fg_overlap.hip: pieces up to this size are sorted in LDS
 TILE = 2048             # k_sort_radix: hits per tile (256 threads x 8)
@@ -137,41 +139,6 @@ def _tie_free_from_hits(counts, hits):
         pair = (h["ext_id"].astype(np.uint64) << np.uint64(32)) | h["cur_pos"].astype(np.uint64)
         out[i] = 1 if len(np.unique(pair)) == len(pair) else 0
     return out
-
-
-def _bases(rs, r):
-    L = int(rs.length[r])
-    w = rs.words[int(rs.word_off[r]):int(rs.word_off[r + 1])]
-    sh = np.arange(32, dtype=np.uint64) * np.uint64(2)
-    return ((w[:, None] >> sh[None, :]) & np.uint64(3)).reshape(-1)[:L].astype(np.uint8)
-
-
-def _cpu_seed_hits(rs, ex, k, q):
-    """(hits per query, hits in emission order) of overlap.cpp:176-196 on an exported index, in numpy"""
-    import chain_craft as cc
-    from flye_amd import gpu
-    keys, off = ex.keys, ex.key_off.astype(np.int64)
-    length = rs.length.astype(np.int64)
-    counts, chunks = [], []
-    for rec in q:
-        rec = int(rec)
-        s = _bases(rs, rec >> 1)
-        fw, rv = cc.kmer_codes(cc.revcomp(s) if rec & 1 else s, k)
-        can, flip = np.minimum(fw, rv), rv < fw
-        idx = np.minimum(np.searchsorted(keys, can), len(keys) - 1)
-        p = np.nonzero(keys[idx] == can)[0]
-        ln = off[idx[p] + 1] - off[idx[p]]
-        cur, fl = np.repeat(p, ln), np.repeat(flip[p], ln)
-        e = ex.entries[np.repeat(off[idx[p]], ln) + (np.arange(int(ln.sum())) - np.repeat(np.cumsum(ln) - ln, ln))]
-        erec, epos = (e >> np.uint64(32)).astype(np.int64), (e & np.uint64(0xFFFFFFFF)).astype(np.int64)
-        epos = np.where(fl, length[erec >> 1] - epos - k, epos)
-        erec = np.where(fl, erec ^ 1, erec)
-        keep = ~((erec == rec) & (epos == cur))            # no trivial matches (overlap.cpp:188-190)
-        h = np.zeros(int(keep.sum()), gpu.SEED_HIT_DTYPE)
-        h["cur_pos"], h["ext_pos"], h["ext_id"] = cur[keep], epos[keep], erec[keep]
-        counts.append(len(h))
-        chunks.append(h)
-    return np.asarray(counts, np.uint64), np.concatenate(chunks) if chunks else np.zeros(0, gpu.SEED_HIT_DTYPE)
 
 
 # ---- child processes ------------------------------------------------------------------------------------------------
