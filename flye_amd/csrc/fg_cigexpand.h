@@ -1,10 +1,11 @@
 // The expansion of SAM CIGAR runs into gapped columns (what fg_cigar.hip describes at its head), shared by
-// fg_expand_cigars (fg_cigar.hip), which copies the columns down, and by fg_contig_consensus_cigars (fg_contigcons.hip)
-// and fg_make_bubbles_cigars (fg_bubbles.hip), which expand straight into the buffers their own kernels read:
+// fg_expand_cigars (fg_cigar.hip), which copies the columns down, and by fg_contig_consensus_cigars (fg_contigcons.hip),
+// fg_make_bubbles_cigars (fg_bubbles.hip), fg_divergence_profile_cigars (fg_divergence.hip) and fg_classify_reads_cigars
+// (fg_partition.hip), which expand straight into the buffers their own kernels read:
 //   cigCheckRecords     the host walk over every run: argument errors, column totals, trg_start / trg_end, the query span.
 //   cigExpandOnDevice   the device part of one sub-batch of whole alignments: k_cig_advance, the four scans, k_cig_place
 //                       and k_cig_expand into destination pointers the caller gives.
-//   cigCutContigs       where a sub-batch of whole contigs ends for a caller that expands per sub-batch.
+//   cigCutContigs       where a sub-batch of whole contigs (or jobs) ends for a caller that expands per sub-batch.
 #pragma once
 #include "fg_ctx.h"
 #include "fg_stage.h"
@@ -277,10 +278,12 @@ struct CigStaged { std::vector<u32> runBegin, alnRead; std::vector<u64> alnTrg; 
 // columns of the sub-batch go to dTrgOut / dQryOut from byte 0 on, whole 8-column words: both hold at least columns +
 // CIG_LANE_COLS bytes (both NULL: the equal columns are counted and nothing is stored).  trgBase[a] is the alignment's
 // first contig byte in dContig.  Returns the equal columns per alignment, on the device; nothing is waited for, so
-// `staged` stays alive until the caller has synchronised the stream.
+// `staged` stays alive until the caller has synchronised the stream.  dReadsResident, where given, holds the SEQ bytes
+// from readOff[a0] on already: nothing of readSeq goes up.
 inline u32* cigExpandOnDevice(fg_ctx* c, DevPool& B, CigStaged& staged, u64 a0, u64 a1, const std::vector<CigTotals>& tot, const std::vector<u64>& trgBase,
 							  const unsigned char* dContig, const uint64_t* runOff, const uint8_t* runOp, const uint32_t* runLen,
-							  const uint64_t* readOff, const uint8_t* readSeq, u32 tile, unsigned char* dTrgOut, unsigned char* dQryOut)
+							  const uint64_t* readOff, const uint8_t* readSeq, u32 tile, unsigned char* dTrgOut, unsigned char* dQryOut,
+							  const unsigned char* dReadsResident = nullptr)
 {
 	hipStream_t s = c->stream;
 	const u32 nAln = (u32)(a1 - a0);
@@ -309,7 +312,7 @@ inline u32* cigExpandOnDevice(fg_ctx* c, DevPool& B, CigStaged& staged, u64 a0, 
 	u32* dAlnRead = B.get<u32>(nAln);
 	u64* dAlnTrg = B.get<u64>(nAln);
 	CigRun* dRec = B.get<CigRun>(nRec);
-	unsigned char* dReads = B.get<unsigned char>(nReadBytes);
+	const unsigned char* dReads = dReadsResident ? (B.get<unsigned char>(0), dReadsResident) : B.get<unsigned char>(nReadBytes);
 	u32* dMatches = B.get<u32>(nAln);
 	u32 *dCol = dAdv, *dRead = dAdv + (nRuns + 1), *dTrg = dAdv + 2 * ((size_t)nRuns + 1), *dSlot = dAdv + 3 * ((size_t)nRuns + 1);
 
@@ -318,7 +321,7 @@ inline u32* cigExpandOnDevice(fg_ctx* c, DevPool& B, CigStaged& staged, u64 a0, 
 	HIP_CHECK(hipMemcpyAsync(dRunBegin, runBegin.data(), ((size_t)nAln + 1) * 4, hipMemcpyHostToDevice, s));
 	HIP_CHECK(hipMemcpyAsync(dAlnRead, alnRead.data(), (size_t)nAln * 4, hipMemcpyHostToDevice, s));
 	HIP_CHECK(hipMemcpyAsync(dAlnTrg, alnTrg.data(), (size_t)nAln * 8, hipMemcpyHostToDevice, s));
-	if (nReadBytes) HIP_CHECK(hipMemcpyAsync(dReads, readSeq + rd0, nReadBytes, hipMemcpyHostToDevice, s));
+	if (nReadBytes && !dReadsResident) HIP_CHECK(hipMemcpyAsync((void*)dReads, readSeq + rd0, nReadBytes, hipMemcpyHostToDevice, s));
 	HIP_CHECK(hipMemsetAsync(dMatches, 0, (size_t)nAln * 4, s));
 	{
 		ScopedK t(c->timer, "k_cig_advance");
@@ -349,6 +352,8 @@ struct CigSource {
 	const uint64_t* runOff; const uint8_t* runOp; const uint32_t* runLen;
 	const uint64_t* readOff; const uint8_t* readSeq;
 	u32 tile;
+	const unsigned char* dSeq = nullptr;	// the call's SEQ bytes from read_seq[seq0] on, where they are on the device already
+	u64 seq0 = 0;
 };
 
 // the contig bytes of a fused call go up once, into the first buffer of the expansion's pool
@@ -366,15 +371,17 @@ inline DevPool cigExpandSource(fg_ctx* c, const CigSource& src, CigStaged& stage
 {
 	DevPool B = cigPool(c, 1);
 	(void)cigExpandOnDevice(c, B, staged, a0, a1, src.plan->tot, src.plan->trgBase, src.dContig, src.runOff, src.runOp, src.runLen, src.readOff,
-							src.readSeq, src.tile, dTrg, dQry);
+							src.readSeq, src.tile, dTrg, dQry, src.dSeq ? src.dSeq + (src.readOff[a0] - src.seq0) : nullptr);
 	return B;
 }
 
 // The end of the sub-batch of whole contigs that begins at contig i, for a call that expands each sub-batch itself: the
 // consumer's budget (cost per contig, at most maxContigs contigs) and the expansion's numbering: the runs and read bytes
 // of a sub-batch in 32 bits, an alignment's number in 30.  A contig that alone exceeds the numbering cannot be cut.
+// fg_classify_reads_cigars cuts between jobs: `item` is "job" and contigAlnOff[j] the first alignment of job j's edges.
 inline u32 cigCutContigs(const std::string& name, const char* budgetSwitch, u32 i, u32 n_contigs, const std::vector<u64>& cost, u64 budget,
-						 u64 maxContigs, const uint64_t* contigAlnOff, const uint64_t* runOff, const uint64_t* readOff)
+						 u64 maxContigs, const uint64_t* contigAlnOff, const uint64_t* runOff, const uint64_t* readOff,
+						 const char* item = "contig")
 {
 	const u64 aI = contigAlnOff[i];
 	const auto fits = [&](u32 j)		// the contigs i .. j together
@@ -383,8 +390,8 @@ inline u32 cigCutContigs(const std::string& name, const char* budgetSwitch, u32 
 		return aJ == aI || (aJ - aI <= CIG_ALN_MASK && runOff[aJ] - runOff[aI] <= CIG_I32 && readOff[aJ] - readOff[aI] <= CIG_I32);
 	};
 	if (!fits(i) || cost[i] > CIG_I32)
-		throw FgError{FG_ERR_NOMEM, name + ": contig " + std::to_string(i) + " alone has 2^30 alignments or 2^31 columns, runs or SEQ bytes, " +
-										"more than the expansion numbers in one sub-batch; " + budgetSwitch + " cuts between contigs only"};
+		throw FgError{FG_ERR_NOMEM, name + ": " + item + " " + std::to_string(i) + " alone has 2^30 alignments or 2^31 columns, runs or SEQ bytes, " +
+										"more than the expansion numbers in one sub-batch; " + budgetSwitch + " cuts between " + item + "s only"};
 	const u64 most = std::min<u64>(budget, CIG_I32);		// the columns of a sub-batch are numbered in 32 bits too
 	u32 j = i;
 	u64 used = 0;

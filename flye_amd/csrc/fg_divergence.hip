@@ -18,10 +18,17 @@
 //                   lists' starts per contig.
 // Integer atomics only: the result does not depend on the schedule.  The host does work proportional to contigs,
 // alignments and (for the byte check) columns.
+//
+// fg_divergence_profile_cigars takes SAM records for the columns: a sub-batch expands its own alignments (fg_cigexpand.h)
+// into the buffers k_bub_shift reads.  The distinct query bytes of the call size the count tables and so decide the cut
+// before any column exists:
+//   k_seq_present   one wave per maximal piece of SEQ that M and I runs consume: the 128-bit set of its bytes, upper-cased
+//                   as k_cig_expand stores them.  The host adds '-' where a D run has a length.
 #include "fg_ctx.h"
 #include "fg_stage.h"
 #include "fg_devprim.h"
 #include "fg_gapshift.h"
+#include "fg_cigexpand.h"
 #include <cmath>
 
 namespace {
@@ -198,6 +205,48 @@ k_dv_pick(u32 n, const u64* __restrict__ at, const u32* __restrict__ off0, const
 	out[i] = off0[p]; out[n + i] = off1[p]; out[2 * n + i] = off2[p]; out[3 * n + i] = off3[p];
 }
 
+// present[0 .. 4) |= the set of the bytes (below 128) of the pieces seq[start[i] .. start[i] + len[i]), each mapped as
+// k_cig_expand maps a SEQ byte before it stores it: bit b of the 128 stands for byte b.  One wave per piece, in the manner
+// of k_col_present (fg_contigcons.hip): whole 8-byte words where the address allows, the piece's first bytes up to the
+// next word boundary and its last bytes one per lane; four mask registers, folded over the wave by a butterfly; lane 0
+// issues one atomic per word that has a bit.  No LDS.
+__global__ void __launch_bounds__(BUB_BLOCK)
+k_seq_present(const u32* __restrict__ start, const u32* __restrict__ len, u32 nSeg, const unsigned char* __restrict__ seq, u32* present)
+{
+	const int lane = threadIdx.x & 63;
+	const u32 g = blockIdx.x * BUB_WAVES + (threadIdx.x >> 6);
+	if (g >= nSeg) return;
+	const unsigned char* q = seq + start[g];
+	const u64 n = len[g];
+	u32 m[4] = {0u, 0u, 0u, 0u};
+	const auto mark = [&m](u32 raw)
+	{
+		const u32 b = cig_upper((unsigned char)raw);
+		const u32 bit = 1u << (b & 31u), w = (b >> 5) & 3u;
+		m[0] |= w == 0 ? bit : 0u; m[1] |= w == 1 ? bit : 0u; m[2] |= w == 2 ? bit : 0u; m[3] |= w == 3 ? bit : 0u;
+	};
+	const u64 toBoundary = (8 - ((uintptr_t)q & 7)) & 7;
+	const u64 head = toBoundary < n ? toBoundary : n;
+	const u64 nWords = (n - head) / 8, tail0 = head + 8 * nWords;
+	if ((u64)lane < head) mark(q[lane]);
+	const u64* qw = (const u64*)(q + head);
+	for (u64 w = lane; w < nWords; w += 64)
+	{
+		const u64 v = qw[w];
+#pragma unroll
+		for (int i = 0; i < 8; ++i) mark((u32)(v >> (8 * i)) & 0xffu);
+	}
+	if (tail0 + (u64)lane < n) mark(q[tail0 + lane]);
+#pragma unroll
+	for (int k = 0; k < 4; ++k)
+	{
+		u32 v = m[k];
+#pragma unroll
+		for (int sh = 32; sh > 0; sh >>= 1) v |= __shfl_xor(v, sh);
+		if (lane == 0 && v) atomicOr(&present[k], v);
+	}
+}
+
 struct DivergenceOwner {
 	std::vector<uint64_t> listOff[4], profOff;		// total, sub, del, ins
 	std::vector<int32_t> list[4];
@@ -219,7 +268,8 @@ u32 dvMinCount(double thresh, u32 cov)
 
 void dvSubBatch(fg_ctx* c, u32 c0, u32 c1, const double* thresh, const int32_t* contigLen, const uint64_t* contigAlnOff,
 				const int32_t* trgStart, const uint64_t* colOff, const uint8_t* trgCols, const uint8_t* qryCols,
-				const unsigned char* rank, const unsigned char* byteOf, u32 nB, bool wantProfile, DivergenceOwner& own)
+				const unsigned char* rank, const unsigned char* byteOf, u32 nB, bool wantProfile, DivergenceOwner& own,
+				const CigSource* cig = nullptr /* the columns are expanded here, not read from the host */)
 {
 	hipStream_t s = c->stream;
 	const u32 nC = c1 - c0;
@@ -267,8 +317,9 @@ void dvSubBatch(fg_ctx* c, u32 c0, u32 c1, const double* thresh, const int32_t* 
 	u64* dCtgAt = B.get<u64>((size_t)nC + 1);
 	u32* dTileOff = B.get<u32>((size_t)nAln + 1);
 	u32* dTileNg = B.get<u32>(nTiles + 1);
-	unsigned char* dTrg = B.get<unsigned char>(nCols);
-	unsigned char* dQry = B.get<unsigned char>(nCols);
+	// k_cig_expand stores whole words past the last column
+	unsigned char* dTrg = B.get<unsigned char>(nCols + (cig ? CIG_LANE_COLS : 0));
+	unsigned char* dQry = B.get<unsigned char>(nCols + (cig ? CIG_LANE_COLS : 0));
 	unsigned char* dTrgS = B.get<unsigned char>(nCols);
 	unsigned char* dQryS = B.get<unsigned char>(nCols);
 	unsigned char* dTab = B.get<unsigned char>(256);
@@ -292,7 +343,9 @@ void dvSubBatch(fg_ctx* c, u32 c0, u32 c1, const double* thresh, const int32_t* 
 	HIP_CHECK(hipMemcpyAsync(dCtgAt, ctgAt.data(), ((size_t)nC + 1) * 8, hipMemcpyHostToDevice, s));
 	HIP_CHECK(hipMemcpyAsync(dTileOff, tileOff.data(), ((size_t)nAln + 1) * 4, hipMemcpyHostToDevice, s));
 	HIP_CHECK(hipMemcpyAsync(dMinCt, minCt.data(), (size_t)3 * nCov * 4, hipMemcpyHostToDevice, s));
-	if (nCols)
+	CigStaged staged;		// read by the expansion's uploads: alive until the stream has been waited for
+	if (cig && nAln) (void)cigExpandSource(c, *cig, staged, a0, a1, dTrg, dQry);
+	else if (nCols)
 	{
 		HIP_CHECK(hipMemcpyAsync(dTrg, trgCols + col0, nCols, hipMemcpyHostToDevice, s));
 		HIP_CHECK(hipMemcpyAsync(dQry, qryCols + col0, nCols, hipMemcpyHostToDevice, s));
@@ -380,6 +433,112 @@ void dvSubBatch(fg_ctx* c, u32 c0, u32 c1, const double* thresh, const int32_t* 
 	HIP_CHECK(hipStreamSynchronize(s));
 }
 
+// the query bytes of a call, ranked in byte order: the width of the count tables
+u32 dvRankBytes(const bool* present, unsigned char* rank, unsigned char* byteOf)
+{
+	memset(rank, DV_NONE, 128);
+	memset(byteOf, 0, 128);
+	u32 nB = 0;
+	for (int b = 0; b < 128; ++b)
+		if (present[b]) { rank[b] = (unsigned char)nB; byteOf[nB++] = (unsigned char)b; }
+	if (nB == 0) { rank['-'] = 0; byteOf[0] = '-'; nB = 1; }
+	return nB;
+}
+
+// The set of query bytes the columns of the alignments a0 .. a1 would show, from the records (checked by cigCheckRecords):
+// the SEQ bytes that M and I runs consume, as k_cig_expand stores them, and '-' where a D run has a length.  Zero-length
+// runs, clipped bytes and the bytes of SEQ behind the consumed part give nothing.  The SEQ bytes go up in pieces of whole
+// alignments of at most `chunk` bytes (one alignment at least) into a buffer of the expansion's pool; where ONE piece
+// holds the call it stays there and the pointer is returned for the expansion to read, otherwise NULL.
+const unsigned char* dvPresentOfRecords(fg_ctx* c, u64 a0, u64 a1, const uint64_t* runOff, const uint8_t* runOp, const uint32_t* runLen,
+										const uint64_t* readOff, const uint8_t* readSeq, u64 chunk, bool* present)
+{
+	hipStream_t s = c->stream;
+	u32 mask[4] = {};
+	bool resident = false;
+	const unsigned char* dSeq = nullptr;
+	std::vector<u32> segStart, segLen;
+	for (u64 b0 = a0; b0 < a1;)
+	{
+		u64 b1 = b0 + 1;
+		while (b1 < a1 && readOff[b1 + 1] - readOff[b0] <= chunk) ++b1;
+		const u64 rd0 = readOff[b0], nBytes = readOff[b1] - rd0;
+		segStart.clear(); segLen.clear();
+		for (u64 a = b0; a < b1; ++a)
+		{
+			u64 qpos = readOff[a] - rd0, open = ~0ULL;		// open: where the piece under way ends
+			for (u64 r = runOff[a]; r < runOff[a + 1]; ++r)
+			{
+				const u64 l = runLen[r];
+				const unsigned char o = runOp[r];
+				if (l == 0) continue;
+				if (o == 'D') present['-'] = true;
+				else if (o == 'S') qpos += l;
+				else if (o == 'M' || o == 'I')
+				{
+					if (open == qpos) segLen.back() += (u32)l;
+					else { segStart.push_back((u32)qpos); segLen.push_back((u32)l); }
+					qpos += l; open = qpos;
+				}
+			}
+		}
+		if (nBytes >= (1ULL << 32))
+			throw FgError{FG_ERR_NOMEM, "fg_divergence_profile_cigars: an alignment with 2^32 SEQ bytes"};
+		const u32 nSeg = (u32)segStart.size();
+		if (nSeg)
+		{
+			DevPool B = cigPool(c, 12);			// behind the buffers of cigExpandOnDevice and its callers
+			unsigned char* dBytes = B.get<unsigned char>(nBytes);
+			u32* dStart = B.get<u32>(nSeg);
+			u32* dLen = B.get<u32>(nSeg);
+			u32* dPresent = B.get<u32>(4);
+			HIP_CHECK(hipMemcpyAsync(dBytes, readSeq + rd0, nBytes, hipMemcpyHostToDevice, s));
+			HIP_CHECK(hipMemcpyAsync(dStart, segStart.data(), (size_t)nSeg * 4, hipMemcpyHostToDevice, s));
+			HIP_CHECK(hipMemcpyAsync(dLen, segLen.data(), (size_t)nSeg * 4, hipMemcpyHostToDevice, s));
+			HIP_CHECK(hipMemsetAsync(dPresent, 0, 16, s));
+			{
+				ScopedK t(c->timer, "k_seq_present");
+				hipLaunchKernelGGL(k_seq_present, bubWaveGrid(nSeg), BUB_BLOCK, 0, s, dStart, dLen, nSeg, dBytes, dPresent);
+			}
+			HIP_CHECK(hipGetLastError());
+			u32 m[4] = {};
+			HIP_CHECK(hipMemcpyAsync(m, dPresent, 16, hipMemcpyDeviceToHost, s));
+			HIP_CHECK(hipStreamSynchronize(s));		// also keeps segStart / segLen alive until their copies have run
+			for (int k = 0; k < 4; ++k) mask[k] |= m[k];
+			resident = b0 == a0 && b1 == a1;
+			dSeq = dBytes;
+		}
+		b0 = b1;
+	}
+	for (int b = 0; b < 128; ++b)
+		if ((mask[b >> 5] >> (b & 31)) & 1u) present[b] = true;
+	return resident ? dSeq : nullptr;
+}
+
+// the finished owner into the caller's struct
+void dvHandOver(struct fg_divergence_batch* out, DivergenceOwner* own, uint32_t n_contigs, bool wantProfile)
+{
+	out->n_contigs = n_contigs;
+	out->total_off = own->listOff[0].data(); out->total_pos = own->list[0].data();
+	out->sub_off = own->listOff[1].data(); out->sub_pos = own->list[1].data();
+	out->del_off = own->listOff[2].data(); out->del_pos = own->list[2].data();
+	out->ins_off = own->listOff[3].data(); out->ins_pos = own->list[3].data();
+	if (wantProfile)
+	{
+		out->prof_off = own->profOff.data();
+		out->cov = own->cov.data();
+		out->nucl = own->nucl.data();
+		out->mat_ct = own->matCt.data();
+		out->sub_base = own->subBase.data();
+		out->sub_ct = own->subCt.data();
+		out->del_ct = own->delCt.data();
+		out->ins_base = own->insBase.data();
+		out->ins_ct = own->insCt.data();
+		out->flags = own->flags.data();
+	}
+	out->owner_ = own;
+}
+
 } // namespace
 
 extern "C" {
@@ -409,12 +568,8 @@ int fg_divergence_profile(fg_ctx* c, double sub_thresh, double del_thresh, doubl
 				stageBasesOnContig(name, a, nonGap, contig_len[i]);
 			}
 		// the query bytes of the call, ranked in byte order: the width of the count tables
-		unsigned char rank[128], byteOf[128] = {};
-		memset(rank, DV_NONE, sizeof(rank));
-		u32 nB = 0;
-		for (int b = 0; b < 128; ++b)
-			if (present[b]) { rank[b] = (unsigned char)nB; byteOf[nB++] = (unsigned char)b; }
-		if (nB == 0) { rank['-'] = 0; byteOf[0] = '-'; nB = 1; }
+		unsigned char rank[128], byteOf[128];
+		const u32 nB = dvRankBytes(present, rank, byteOf);
 		// a contig counts its columns and a table row per position
 		std::vector<u64> cost(n_contigs, 0);
 		for (u32 i = 0; i < n_contigs; ++i)
@@ -439,26 +594,77 @@ int fg_divergence_profile(fg_ctx* c, double sub_thresh, double del_thresh, doubl
 		c->timer.collect();
 		for (auto& v : own->list) stageKeep(v);
 		stageKeep(own->cov, own->matCt, own->subCt, own->delCt, own->insCt, own->nucl, own->subBase, own->insBase, own->flags);
+		dvHandOver(out, own, n_contigs, want_profile != 0);
+	});
+}
 
-		out->n_contigs = n_contigs;
-		out->total_off = own->listOff[0].data(); out->total_pos = own->list[0].data();
-		out->sub_off = own->listOff[1].data(); out->sub_pos = own->list[1].data();
-		out->del_off = own->listOff[2].data(); out->del_pos = own->list[2].data();
-		out->ins_off = own->listOff[3].data(); out->ins_pos = own->list[3].data();
-		if (want_profile)
+int fg_divergence_profile_cigars(fg_ctx* c, double sub_thresh, double del_thresh, double ins_thresh, uint32_t n_contigs,
+								 const uint64_t* contig_off, const uint8_t* contig_seq, const uint64_t* contig_aln_off,
+								 const int32_t* ctg_pos, const uint64_t* run_off, const uint8_t* run_op, const uint32_t* run_len,
+								 const uint64_t* read_off, const uint8_t* read_seq, uint8_t want_profile, struct fg_divergence_batch* out)
+{
+	return stageCall<DivergenceOwner>(c, out, [&](DivergenceOwner*& own)
+	{
+		const std::string name = "fg_divergence_profile_cigars";
+		if (!out) throw FgError{FG_ERR_ARG, name + ": null result"};
+		if (n_contigs && !contig_aln_off) throw FgError{FG_ERR_ARG, name + ": null contig_aln_off"};
+		stageOffsets(name, "contig_aln_off", "contig ", contig_aln_off, 0, n_contigs);
+		const u64 a0 = n_contigs ? contig_aln_off[0] : 0, a1 = n_contigs ? contig_aln_off[n_contigs] : 0;
+		std::vector<uint32_t> alnContig((size_t)a1, 0);
+		for (u32 i = 0; i < n_contigs; ++i)
+			for (u64 a = contig_aln_off[i]; a < contig_aln_off[i + 1]; ++a) alnContig[a] = i;
+		// every check of fg_expand_cigars, then those fg_divergence_profile makes on what the expansion would hand it
+		CigPlan plan;
+		cigCheckRecords(name, n_contigs, contig_off, contig_seq, a0, a1, alnContig.data(), !ctg_pos || !run_off || !read_off,
+						"null ctg_pos, run_off or read_off", ctg_pos, run_off, run_op, run_len, read_off, read_seq, plan);
+		const double thresh[3] = {sub_thresh, del_thresh, ins_thresh};
+		for (double t : thresh)
+			if (!(t >= 0.0)) throw FgError{FG_ERR_ARG, name + ": a threshold that is NaN or negative"};
+		// No walk over columns on the host.  What fg_divergence_profile reads from them holds by construction after
+		// cigCheckRecords: every contig and SEQ byte is below 128, so every column is; the non-gap target columns of an
+		// alignment are the contig bytes its runs consume, which end on the contig.  trg_start does not: an alignment of
+		// insertions alone may stand behind the last base.
+		std::vector<int32_t> contigLen(n_contigs, 0);
+		for (u32 i = 0; i < n_contigs; ++i)
 		{
-			out->prof_off = own->profOff.data();
-			out->cov = own->cov.data();
-			out->nucl = own->nucl.data();
-			out->mat_ct = own->matCt.data();
-			out->sub_base = own->subBase.data();
-			out->sub_ct = own->subCt.data();
-			out->del_ct = own->delCt.data();
-			out->ins_base = own->insBase.data();
-			out->ins_ct = own->insCt.data();
-			out->flags = own->flags.data();
+			if (contig_off[i + 1] - contig_off[i] > CIG_I32) throw FgError{FG_ERR_ARG, name + ": contig " + std::to_string(i) + " has 2^31 bytes"};
+			contigLen[i] = (int32_t)(contig_off[i + 1] - contig_off[i]);
+			for (u64 a = contig_aln_off[i]; a < contig_aln_off[i + 1]; ++a) stageStartOnContig(name, a, plan.trgStart[a], contigLen[i]);
 		}
-		out->owner_ = own;
+		const u64 budget = stageEnvU64("FG_DIVERGENCE_BATCH_COLS", 1ULL << 27);
+		const u64 maxContigs = stageEnvCap("FG_DIVERGENCE_BATCH_CONTIGS");
+		HIP_CHECK(hipSetDevice(c->device));
+		c->timer.reset();
+		// the query bytes of the call decide every contig's cost, so they are found from the records, before the cut
+		bool present[128] = {};
+		const unsigned char* dSeq = a1 > a0 ? dvPresentOfRecords(c, a0, a1, run_off, run_op, run_len, read_off, read_seq,
+																 std::max<u64>(1, std::min<u64>(budget, CIG_I32)), present) : nullptr;
+		unsigned char rank[128], byteOf[128];
+		const u32 nB = dvRankBytes(present, rank, byteOf);
+		// a contig counts its columns and a table row per position
+		std::vector<u64> cost(n_contigs, 0);
+		for (u32 i = 0; i < n_contigs; ++i)
+			cost[i] = (u64)contigLen[i] * nB + (plan.colOff[contig_aln_off[i + 1]] - plan.colOff[contig_aln_off[i]]);
+		stageAllFit(name, "contig", cost, budget, "columns and table cells", "FG_DIVERGENCE_BATCH_COLS");
+		own = new DivergenceOwner;
+		for (auto& v : own->listOff) v.assign(1, 0);
+		if (want_profile) own->profOff.assign(1, 0);
+		// the contig bytes go up once per call; a sub-batch expands its own alignments.  The SEQ bytes k_seq_present has read
+		// serve the expansion where one sub-batch holds every alignment of the call.
+		CigSource src{&plan, a1 > a0 ? cigUploadContigs(c, plan, contig_seq) : nullptr, run_off, run_op, run_len, read_off, read_seq, cigTile()};
+		for (u32 i = 0; i < n_contigs;)
+		{
+			const u32 j = cigCutContigs(name, "FG_DIVERGENCE_BATCH_COLS", i, n_contigs, cost, budget, maxContigs, contig_aln_off, run_off, read_off);
+			if (dSeq && contig_aln_off[i] == a0 && contig_aln_off[j] == a1) { src.dSeq = dSeq; src.seq0 = read_off[a0]; }
+			else src.dSeq = nullptr;
+			dvSubBatch(c, i, j, thresh, contigLen.data(), contig_aln_off, plan.trgStart.data(), plan.colOff.data(), nullptr, nullptr, rank, byteOf,
+					   nB, want_profile != 0, *own, &src);
+			i = j;
+		}
+		c->timer.collect();
+		for (auto& v : own->list) stageKeep(v);
+		stageKeep(own->cov, own->matCt, own->subCt, own->delCt, own->insCt, own->nucl, own->subBase, own->insBase, own->flags);
+		dvHandOver(out, own, n_contigs, want_profile != 0);
 	});
 }
 

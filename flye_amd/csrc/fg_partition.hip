@@ -25,10 +25,15 @@
 //                   its last alignment, a larger one 0 (the reference's reset rule); then the vote of :1578-1596.
 // Integer atomics only: the result does not depend on the schedule.  The host does work proportional to jobs, edges,
 // alignments and (for the byte check) columns.
+//
+// fg_classify_reads_cigars takes SAM records for the columns, the alignments of edge e lying on contig e (the edge's own
+// consensus): a sub-batch of whole jobs expands its own alignments (fg_cigexpand.h) into the buffers k_pt_tiles and
+// k_cl_score read.
 #include "fg_ctx.h"
 #include "fg_stage.h"
 #include "fg_devprim.h"
 #include "fg_gapshift.h"
+#include "fg_cigexpand.h"
 
 namespace {
 
@@ -555,7 +560,7 @@ struct ClassifyIn {
 };
 
 void clSubBatch(fg_ctx* c, u32 j0, u32 j1, const ClassifyIn& in, const std::vector<ClEdge>& allEdges, u32 tileShift, bool wantScores,
-				ClassifyOwner& own)
+				ClassifyOwner& own, const CigSource* cig = nullptr /* the columns are expanded here, not read from the host */)
 {
 	hipStream_t s = c->stream;
 	const u32 nJ = j1 - j0;
@@ -618,8 +623,9 @@ void clSubBatch(fg_ctx* c, u32 j0, u32 j1, const ClassifyIn& in, const std::vect
 	i32* dEntries = B.get<i32>(nEntries);
 	u32* dCnt = B.get<u32>(nCells);
 	u32* dTileNg = B.get<u32>(nTiles + 1);
-	unsigned char* dTrg = B.get<unsigned char>(nCols);
-	unsigned char* dQry = B.get<unsigned char>(nCols);
+	// k_cig_expand stores whole words past the last column
+	unsigned char* dTrg = B.get<unsigned char>(nCols + (cig ? CIG_LANE_COLS : 0));
+	unsigned char* dQry = B.get<unsigned char>(nCols + (cig ? CIG_LANE_COLS : 0));
 	u32* dScore = B.get<u32>(nAln);
 	unsigned char* dCounted = B.get<unsigned char>(nAln);
 	u64* dKeys[2] = {B.get<u64>(nAln), B.get<u64>(nAln)};
@@ -632,7 +638,9 @@ void clSubBatch(fg_ctx* c, u32 j0, u32 j1, const ClassifyIn& in, const std::vect
 	ptUp(s, dReadAt, readAt); ptUp(s, dEdgePosAt, edgePosAt); ptUp(s, dJobEdge0, jobEdge0); ptUp(s, dEdges, edges); ptUp(s, dAln, alns);
 	ptUp(s, dTileOff, tileOff);
 	if (nEntries) HIP_CHECK(hipMemcpyAsync(dEntries, in.edgePos + p0, nEntries * 4, hipMemcpyHostToDevice, s));
-	if (nCols)
+	CigStaged staged;		// read by the expansion's uploads: alive until the stream has been waited for
+	if (cig && nAln) (void)cigExpandSource(c, *cig, staged, a0, a1, dTrg, dQry);
+	else if (nCols)
 	{
 		HIP_CHECK(hipMemcpyAsync(dTrg, in.trgCols + col0, nCols, hipMemcpyHostToDevice, s));
 		HIP_CHECK(hipMemcpyAsync(dQry, in.qryCols + col0, nCols, hipMemcpyHostToDevice, s));
@@ -705,6 +713,24 @@ void ptColOff(const std::string& name, const uint64_t* colOff, u64 lo, u64 hi, c
 	stageOffsets(name, "col_off", "", colOff, lo, hi);
 	for (u64 a = lo; a < hi; ++a) stageColWidth(name, colOff, a);
 	stageColsGiven(name, colOff, lo, hi, trgCols, qryCols);
+}
+
+// the finished owner into the caller's struct
+void clHandOver(struct fg_classify_batch* out, ClassifyOwner* own, uint32_t n_jobs, u64 nAlns, bool wantScores)
+{
+	out->n_jobs = n_jobs;
+	out->n_alignments = nAlns;
+	out->read_off = own->readOff.data();
+	out->status = own->status.data();
+	out->top_edge = own->topEdge.data();
+	out->top_score = own->topScore.data();
+	out->total_score = own->totalScore.data();
+	if (wantScores)
+	{
+		out->aln_score = own->alnScore.data();
+		out->aln_counted = own->counted.data();
+	}
+	out->owner_ = own;
 }
 
 } // namespace
@@ -855,19 +881,98 @@ int fg_classify_reads(fg_ctx* c, int32_t buffer_count, uint32_t n_jobs, const ui
 		}
 		c->timer.collect();
 		stageKeep(own->status, own->topEdge, own->topScore, own->totalScore, own->alnScore, own->counted);
-		out->n_jobs = n_jobs;
-		out->n_alignments = nAlns;
-		out->read_off = own->readOff.data();
-		out->status = own->status.data();
-		out->top_edge = own->topEdge.data();
-		out->top_score = own->topScore.data();
-		out->total_score = own->totalScore.data();
-		if (want_scores)
+		clHandOver(out, own, n_jobs, nAlns, want_scores != 0);
+	});
+}
+
+int fg_classify_reads_cigars(fg_ctx* c, int32_t buffer_count, uint32_t n_jobs, const uint64_t* job_edge_off, const uint32_t* job_n_reads,
+							 const uint64_t* edge_pos_off, const int32_t* edge_pos, const uint64_t* edge_off, const uint8_t* edge_seq,
+							 const uint64_t* edge_aln_off, const uint32_t* read, const int32_t* ctg_pos, const uint64_t* run_off,
+							 const uint8_t* run_op, const uint32_t* run_len, const uint64_t* read_off, const uint8_t* read_seq,
+							 uint8_t want_scores, struct fg_classify_batch* out)
+{
+	return stageCall<ClassifyOwner>(c, out, [&](ClassifyOwner*& own)
+	{
+		u64 nAlns = 0;
+		const std::string name = "fg_classify_reads_cigars";
+		if (!out) throw FgError{FG_ERR_ARG, name + ": null result"};
+		const PtCut cut = ptCut(name);
+		CigPlan plan;
+		std::vector<ClEdge> edges;
+		std::vector<u64> cost(n_jobs, 0), jobAlnOff((size_t)n_jobs + 1, 0);
+		if (n_jobs)
 		{
-			out->aln_score = own->alnScore.data();
-			out->aln_counted = own->counted.data();
+			if (!job_edge_off || !job_n_reads || !edge_pos_off || !edge_aln_off)
+				throw FgError{FG_ERR_ARG, name + ": null job_edge_off, job_n_reads, edge_pos_off or edge_aln_off"};
+			stageOffsets(name, "job_edge_off", "", job_edge_off, 0, n_jobs);
+			const u64 e0 = job_edge_off[0], e1 = job_edge_off[n_jobs];
+			stageOffsets(name, "edge_pos_off", "", edge_pos_off, e0, e1);
+			stageOffsets(name, "edge_aln_off", "", edge_aln_off, e0, e1);
+			if (e1 - e0 > 0xffffffffULL) throw FgError{FG_ERR_ARG, name + ": 2^32 edges"};
+			if (e1 > e0 && !edge_off) throw FgError{FG_ERR_ARG, name + ": null edge_off"};
+			const u64 a0 = edge_aln_off[e0], a1 = edge_aln_off[e1];
+			nAlns = a1 - a0;
+			// the edges of the call are the contigs of the expansion, numbered from the first one
+			std::vector<uint32_t> alnContig((size_t)a1, 0);
+			for (u64 e = e0; e < e1; ++e)
+				for (u64 a = edge_aln_off[e]; a < edge_aln_off[e + 1]; ++a) alnContig[a] = (uint32_t)(e - e0);
+			// every check of fg_expand_cigars, then those fg_classify_reads makes on what the expansion would hand it
+			cigCheckRecords(name, (u32)(e1 - e0), edge_off ? edge_off + e0 : nullptr, edge_seq, a0, a1, alnContig.data(),
+							!read || !ctg_pos || !run_off || !read_off, "null read, ctg_pos, run_off or read_off", ctg_pos, run_off, run_op,
+							run_len, read_off, read_seq, plan);
 		}
-		out->owner_ = own;
+		if (buffer_count < 0) throw FgError{FG_ERR_ARG, name + ": buffer_count < 0"};
+		if (n_jobs)
+		{
+			const u64 e0 = job_edge_off[0], e1 = job_edge_off[n_jobs];
+			if (edge_pos_off[e1] > edge_pos_off[e0] && !edge_pos) throw FgError{FG_ERR_ARG, name + ": null edge_pos"};
+			edges.resize(e1 - e0);
+			for (u32 j = 0; j < n_jobs; ++j)
+			{
+				if (job_edge_off[j + 1] == job_edge_off[j]) throw FgError{FG_ERR_ARG, name + ": job " + std::to_string(j) + " has no edges"};
+				if (edge_pos_off[job_edge_off[j + 1]] - edge_pos_off[job_edge_off[j]] >= (1ULL << 31))
+					throw FgError{FG_ERR_ARG, name + ": the edge lists of job " + std::to_string(j) + " hold 2^31 entries: the scores do not fit int32"};
+				u64 cells = 0;
+				for (u64 e = job_edge_off[j]; e < job_edge_off[j + 1]; ++e)
+				{
+					ClEdge& ed = edges[e - e0];
+					ed = ClEdge{0, INT32_MAX, INT32_MIN, 0};
+					for (u64 a = edge_aln_off[e]; a < edge_aln_off[e + 1]; ++a)
+					{
+						if (read[a] >= job_n_reads[j])
+							throw FgError{FG_ERR_ARG, name + ": read " + std::to_string(read[a]) + " of alignment " + std::to_string(a) + " is not below n_reads"};
+						// No walk over columns on the host.  What ptCheckColumns reads from them holds by construction after
+						// cigCheckRecords: every contig and SEQ byte is below 128, so every column is; trg_start = ctg_pos - 1 >= 0;
+						// the non-gap target columns are the contig bytes the runs consume, which is trg_end - trg_start.
+						ed.minPos = std::min(ed.minPos, plan.trgStart[a]); ed.maxEnd = std::max(ed.maxEnd, plan.trgEnd[a]);
+					}
+					if (edge_aln_off[e + 1] == edge_aln_off[e]) ed.minPos = ed.maxEnd = 0;
+					cells += (u64)((long long)ed.maxEnd - ed.minPos);
+				}
+				jobAlnOff[j] = edge_aln_off[job_edge_off[j]];
+				jobAlnOff[j + 1] = edge_aln_off[job_edge_off[j + 1]];
+				cost[j] = cells + (plan.colOff[jobAlnOff[j + 1]] - plan.colOff[jobAlnOff[j]]);
+				stageFits(name, "job", j, cost[j], cut.budget, "columns and table cells", "FG_PARTITION_BATCH_COLS");
+			}
+		}
+		ClassifyIn in{buffer_count, job_edge_off, job_n_reads, edge_pos_off, edge_pos, edge_aln_off, read, plan.trgStart.data(),
+					  plan.trgEnd.data(), plan.colOff.data(), nullptr, nullptr};
+		own = new ClassifyOwner;
+		own->readOff.assign(1, 0);
+		HIP_CHECK(hipSetDevice(c->device));
+		c->timer.reset();
+		// the edge consensuses go up once per call; a sub-batch expands its own alignments
+		const CigSource src{&plan, nAlns ? cigUploadContigs(c, plan, edge_seq) : nullptr, run_off, run_op, run_len, read_off, read_seq, cigTile()};
+		for (u32 i = 0; i < n_jobs;)
+		{
+			// the "contigs i .. j" of the cut are the edges of the jobs i .. j
+			const u32 j = cigCutContigs(name, "FG_PARTITION_BATCH_COLS", i, n_jobs, cost, cut.budget, cut.maxJobs, jobAlnOff.data(), run_off, read_off, "job");
+			clSubBatch(c, i, j, in, edges, cut.tileShift, want_scores != 0, *own, &src);
+			i = j;
+		}
+		c->timer.collect();
+		stageKeep(own->status, own->topEdge, own->topScore, own->totalScore, own->alnScore, own->counted);
+		clHandOver(out, own, n_jobs, nAlns, want_scores != 0);
 	});
 }
 

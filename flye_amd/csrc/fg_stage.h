@@ -1,5 +1,6 @@
 // What the stage calls of the C ABI share on the host (fg_uniform_alignments, fg_contig_consensus[_cigars],
-// fg_make_bubbles[_cigars], fg_expand_cigars, fg_divergence_profile, fg_confirm_positions, fg_classify_reads):
+// fg_make_bubbles[_cigars], fg_expand_cigars, fg_divergence_profile[_cigars], fg_confirm_positions,
+// fg_classify_reads[_cigars]):
 //   host part (no HIP: fg_error.h and include/flye_gpu.h alone; tests/stage_host_check.cpp builds it with g++)
 //     stageEnvU64 / stageEnvCap             the u64 switches of the environment
 //     stageOffsets .. stageColumnWalk       the argument checks; each takes the call's name, so a message reads the same

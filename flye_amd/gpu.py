@@ -24,10 +24,11 @@ like calls into the reference:
   ``polish_sam`` (fg_contig_consensus_cigars / fg_make_bubbles_cigars: the columns are made and stay on the device)
 * ``DivergenceFinder(ctx).find_divergence(alignment_path, contigs_path, contigs_info, frequency_path, positions_path,
   div_sum_path, sub_thresh, del_thresh, ins_thresh)`` / ``profile``  (flye/trestle/divergence.py:55-232, on
-  fg_divergence_profile)
+  fg_divergence_profile); ``find_divergence_sam`` / ``profile_sam`` on fg_divergence_profile_cigars
 * ``ReadPartitioner(ctx).partition_reads(edges, it, side, position_path, cons_align_path, template, read_align_path,
   consensuses, confirmed_pos_path, part_file, headers_to_id)`` / ``confirm`` / ``classify``
-  (flye/trestle/trestle.py:1075-1628, on fg_confirm_positions and fg_classify_reads)
+  (flye/trestle/trestle.py:1075-1628, on fg_confirm_positions and fg_classify_reads); ``partition_reads_sam`` /
+  ``classify_sam`` on fg_classify_reads_cigars
 
 There is no CPU fallback: if the HIP library or a device is missing every entry
 point raises ``FlyeGpuError``.
@@ -71,6 +72,7 @@ ABI_SYMBOLS = ["fg_abi_version", "fg_create", "fg_destroy", "fg_strerror", "fg_l
                "fg_expand_cigars", "fg_release_expand", "fg_cigar_parse", "fg_contig_consensus_cigars", "fg_make_bubbles_cigars",
                "fg_divergence_profile", "fg_release_divergence",
                "fg_confirm_positions", "fg_release_confirm", "fg_classify_reads", "fg_release_classify",
+               "fg_divergence_profile_cigars", "fg_classify_reads_cigars",
                "fg_index_keep_targets", "fg_index_shard", "fg_probe_hits", "fg_overlaps_from_hits",
                "fg_index_piece_split", "fg_index_scatter_begin", "fg_index_scatter_end", "fg_debug_probe_skip_check",
                "fg_group_create", "fg_group_destroy", "fg_group_size", "fg_group_member", "fg_group_last_error",
@@ -442,6 +444,9 @@ def load_library():
         L.fg_classify_reads.argtypes = [C.c_void_p, C.c_int32, C.c_uint32] + [C.c_void_p] * 11 + [C.c_uint8, C.POINTER(ClassifyBatch)]
         L.fg_release_classify.argtypes = [C.POINTER(ClassifyBatch)]
         L.fg_release_classify.restype = None
+        L.fg_divergence_profile_cigars.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_uint32] + [C.c_void_p] * 9 + \
+            [C.c_uint8, C.POINTER(DivergenceBatch)]
+        L.fg_classify_reads_cigars.argtypes = [C.c_void_p, C.c_int32, C.c_uint32] + [C.c_void_p] * 14 + [C.c_uint8, C.POINTER(ClassifyBatch)]
         L.fg_debug_group_bin_cuts.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         L.fg_debug_freq_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
         L.fg_debug_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int]
@@ -1357,7 +1362,9 @@ class Context:
                                                  cao.ctypes.data, ptr(ts), ptr(co), ptr(tc), ptr(qc), int(bool(want_profile)),
                                                  C.byref(b)))
         self.last_divergence_seconds = time.perf_counter() - t0
+        return self._divergence_result(b, n, want_profile)
 
+    def _divergence_result(self, b, n, want_profile):
         def take(p, k, dtype):
             return np.ctypeslib.as_array(p, (k,)).copy() if k else np.zeros(0, dtype)
 
@@ -1427,6 +1434,9 @@ class Context:
                                              eao.ctypes.data, ptr(rd), ptr(ts), ptr(te), co.ctypes.data, ptr(tc), ptr(qc),
                                              int(bool(want_scores)), C.byref(b)))
         self.last_classify_seconds = time.perf_counter() - t0
+        return self._classify_result(b, n, want_scores)
+
+    def _classify_result(self, b, n, want_scores):
         take = lambda p, k, dtype: np.ctypeslib.as_array(p, (k,)).copy() if k else np.zeros(0, dtype)
         out = dict(read_off=take(b.read_off, n + 1, np.uint64), aln_score=None, aln_counted=None)
         nr = int(out["read_off"][n])
@@ -1530,6 +1540,44 @@ class Context:
                                                   *[ptr(a) for a in arrs[3:]], ptr(er), int(bool(want_profile)), C.byref(b)))
         self.last_bubbles_seconds = time.perf_counter() - t0
         return self._bubble_result(b, n, want_profile)
+
+    def divergence_profile_cigars(self, sub_thresh, del_thresh, ins_thresh, contig_off, contig_seq, contig_aln_off, ctg_pos, run_off,
+                                  run_op, run_len, read_off, read_seq, want_profile=False):
+        """fg_divergence_profile_cigars: expand_cigars and divergence_profile as one call, the columns never leaving the
+        device.  The contigs and records as for contig_consensus_cigars.  Returns a DivergenceResult equal to the two
+        calls'."""
+        n, na, arrs = self._record_arrays("divergence_profile_cigars", contig_off, contig_seq, contig_aln_off, ctg_pos, run_off,
+                                          run_op, run_len, read_off, read_seq)
+        ptr = lambda a: a.ctypes.data if a is not None and len(a) else None
+        b = DivergenceBatch()
+        t0 = time.perf_counter()
+        self._check(self.L.fg_divergence_profile_cigars(self.h, float(sub_thresh), float(del_thresh), float(ins_thresh), n,
+                                                        *[ptr(a) for a in arrs], int(bool(want_profile)), C.byref(b)))
+        self.last_divergence_seconds = time.perf_counter() - t0
+        return self._divergence_result(b, n, want_profile)
+
+    def classify_reads_cigars(self, buffer_count, job_edge_off, job_n_reads, edge_pos_off, edge_pos, edge_off, edge_seq, edge_aln_off,
+                              read, ctg_pos, run_off, run_op, run_len, read_off, read_seq, want_scores=False):
+        """fg_classify_reads_cigars: expand_cigars and classify_reads as one call, the columns never leaving the device.
+        Jobs, edges, lists and read numbers as for classify_reads; edge e's consensus is edge_seq[edge_off[e]:edge_off[e + 1]]
+        and its alignments (edge_aln_off[e] .. edge_aln_off[e + 1]) are records on it, given as for expand_cigars.  Returns
+        a ClassifyResult equal to the two calls'."""
+        jnr = np.ascontiguousarray(job_n_reads, np.uint32)
+        n = len(jnr)
+        jeo, epo = np.ascontiguousarray(job_edge_off, np.uint64), np.ascontiguousarray(edge_pos_off, np.uint64)
+        ep, rd = np.ascontiguousarray(edge_pos, np.int32), np.ascontiguousarray(read, np.uint32)
+        _, na, (eo, es, eao, cp, ro, rop, rl, rdo, rs) = self._record_arrays(
+            "classify_reads_cigars", edge_off, edge_seq, edge_aln_off, ctg_pos, run_off, run_op, run_len, read_off, read_seq)
+        if len(jeo) != n + 1 or len(rd) != na or len(epo) != len(eao) or int(jeo.max()) + 1 > len(epo) or int(epo.max()) > len(ep):
+            raise ValueError("classify_reads_cigars: offsets outside their arrays")
+        ptr = lambda a: a.ctypes.data if a is not None and len(a) else None
+        b = ClassifyBatch()
+        t0 = time.perf_counter()
+        self._check(self.L.fg_classify_reads_cigars(self.h, int(buffer_count), n, jeo.ctypes.data, ptr(jnr), epo.ctypes.data, ptr(ep),
+                                                    eo.ctypes.data, ptr(es), eao.ctypes.data, ptr(rd), ptr(cp), ro.ctypes.data, ptr(rop),
+                                                    ptr(rl), rdo.ctypes.data, ptr(rs), int(bool(want_scores)), C.byref(b)))
+        self.last_classify_seconds = time.perf_counter() - t0
+        return self._classify_result(b, n, want_scores)
 
     def edge_coverage(self, window, recs, aln, aln_off, first_ext_id, edge_of, edge_len, want_vectors=True):
         """fg_edge_coverage: the window coverage of MultiplicityInferer::estimateCoverage (multiplicity_inferer.cpp:
@@ -2692,6 +2740,35 @@ class DivergenceFinder:
                     f.write(text)
         return sum(self.aln_errors) / (len(self.aln_errors) + 1)
 
+    def profile_sam(self, sam, contigs, sub_thresh, del_thresh, ins_thresh, want_profile=True):
+        """profile(sam.by_contig(), contigs, ...) for a SamAlignments made with want_cols=False: one
+        fg_divergence_profile_cigars, which expands the CIGARs on the device straight into the divergence kernels'
+        buffers.  contigs are records with id; their bytes are the reader's.  No gapped string exists on the host."""
+        alns, rec = sam.flatten(contigs)
+        self.aln_errors = [a.err_rate for a in alns]
+        self.result = self.ctx.divergence_profile_cigars(sub_thresh, del_thresh, ins_thresh, want_profile=want_profile, **rec)
+        return self.result
+
+    def find_divergence_sam(self, alignment_path, contigs_path, contigs_info, frequency_path, positions_path, div_sum_path,
+                            sub_thresh, del_thresh, ins_thresh):
+        """find_divergence on profile_sam: the same three files and the same return value.  A contig's positions are
+        those of the bytes read from contigs_path, which is where the reference's contigs_info has its lengths from."""
+        if not os.path.isfile(alignment_path) or not os.path.isfile(contigs_path):
+            raise ValueError("_get_median() arg is an empty sequence")
+        sam = SamAlignments(self.ctx, alignment_path, self.read_fasta(contigs_path), self.max_read_coverage, want_cols=False)
+        Contig = collections.namedtuple("Contig", ["id", "length"])
+        contigs = [Contig(cid, contigs_info[cid].length) for cid, _ in sam.chunks()]
+        res = self.profile_sam(sam, contigs, sub_thresh, del_thresh, ins_thresh)
+        if contigs:                                     # every contig overwrites the files: the last one stays
+            i = len(contigs) - 1
+            pos = res.positions(i)
+            texts = ((frequency_path, self.frequency_text(res, i)), (positions_path, self.positions_text(pos, sub_thresh, del_thresh, ins_thresh)),
+                     (div_sum_path, self.summary_text(pos, contigs[i].length)))
+            for path, text in texts:
+                with open(path, "w") as f:
+                    f.write(text)
+        return sum(self.aln_errors) / (len(self.aln_errors) + 1)
+
 
 class ReadPartitioner:
     """Mirror of the reference's partition_reads (flye/trestle/trestle.py:1075-1142) on fg_confirm_positions and
@@ -2868,6 +2945,80 @@ class ReadPartitioner:
             out.append([(headers_to_id[h], self.STATUS[st], str(ids[edge]) if st == 2 else "NA", top, total, h)
                         for h, (st, edge, top, total) in zip(headers_to_id, res.reads(j))])
         return out
+
+    def classify_sam(self, jobs):
+        """classify for read alignments kept as SamRecords: jobs are [(read_aligns {edge_id: [records of the first chunk,
+        ...]}, consensus_pos, headers_to_id, edge_seqs {edge_id: the bytes of the consensus the first chunk lies on})], and
+        ONE fg_classify_reads_cigars expands the CIGARs on the device straight into the scoring kernels' buffers.  No
+        gapped string of a read alignment exists on the host."""
+        job_edges, numbers, seqs = [], [], []
+        for read_aligns, _, headers_to_id, edge_seqs in jobs:
+            number = {h: i for i, h in enumerate(headers_to_id)}
+            numbers.append(number)
+            job_edges.append([[r for r in read_aligns[e][0] if r.trg_id != "*" and r.qry_id in number] for e in read_aligns])
+            seqs += [edge_seqs[e] if isinstance(edge_seqs[e], bytes) else edge_seqs[e].encode("latin-1") for e in read_aligns]
+        edges = [lst for je in job_edges for lst in je]
+        pos = [list(cons_pos[e]) for read_aligns, cons_pos, _, _ in jobs for e in read_aligns]
+        recs = [r for lst in edges for r in lst]
+        reads = [number[r.qry_id] for je, number in zip(job_edges, numbers) for lst in je for r in lst]
+        res = self.ctx.classify_reads_cigars(
+            self.buffer_count, np.cumsum([0] + [len(je) for je in job_edges]), [len(n) for n in numbers],
+            np.cumsum([0] + [len(p) for p in pos]), [x for p in pos for x in p], np.cumsum([0] + [len(x) for x in seqs]), b"".join(seqs),
+            np.cumsum([0] + [len(lst) for lst in edges]), reads, [r.ctg_pos for r in recs], np.cumsum([0] + [len(r.ops) for r in recs]),
+            np.concatenate([r.ops for r in recs]) if recs else np.zeros(0, np.uint8),
+            np.concatenate([r.lens for r in recs]) if recs else np.zeros(0, np.uint32),
+            np.cumsum([0] + [len(r.seq) for r in recs]), b"".join(r.seq for r in recs))
+        out = []
+        for j, (read_aligns, _, headers_to_id, _) in enumerate(jobs):
+            ids = list(read_aligns)
+            out.append([(headers_to_id[h], self.STATUS[st], str(ids[edge]) if st == 2 else "NA", top, total, h)
+                        for h, (st, edge, top, total) in zip(headers_to_id, res.reads(j))])
+        return out
+
+    def _read_records(self, alignment, target_path):
+        """-> ([records per chunk], the consensus bytes the first chunk lies on)"""
+        sam = SamAlignments(self.ctx, alignment, DivergenceFinder.read_fasta(target_path), self.max_read_coverage, want_cols=False)
+        chunks = sam.chunks()
+        return [recs for _, recs in chunks], sam.contigs[chunks[0][0].encode("latin-1")] if chunks else b""
+
+    def partition_reads_sam(self, edges, it, side, position_path, cons_align_path, template, read_align_path, consensuses,
+                            confirmed_pos_path, part_file, headers_to_id):
+        """partition_reads with the read SAM files read without columns and scored by classify_sam; the consensus SAM
+        files are read as there and go through confirm.  The same two files."""
+        skip = False
+        pos = self.read_positions(position_path)
+        cons_aligns = {}
+        for edge_id in edges:
+            if not os.path.isfile(cons_align_path.format(it, side, edge_id)):
+                skip = True
+            else:
+                cons_aligns[edge_id] = self._read_alignment(cons_align_path.format(it, side, edge_id), template)
+            if skip or not cons_aligns or not cons_aligns[edge_id] or not cons_aligns[edge_id][0]:
+                skip = True
+        if skip:
+            if it <= 1:
+                confirmed, rejected = {k: [] for k in self.KEYS}, {k: [] for k in self.KEYS}
+                consensus_pos = pos
+            else:
+                confirmed, rejected, consensus_pos = self._read_confirmed_positions(confirmed_pos_path.format(it - 1, side))
+        else:
+            coll = {edge_id: self._collapse_cons_aln(aln) for edge_id, aln in cons_aligns.items()}
+            (confirmed, rejected, consensus_pos), = self.confirm([(pos, coll, side)])
+        self._write_confirmed_positions(confirmed, rejected, pos, confirmed_pos_path.format(it, side))
+        read_aligns, edge_seqs = {}, {}
+        for edge_id in edges:
+            if not os.path.isfile(read_align_path.format(it, side, edge_id)) or not os.path.isfile(consensuses[(it, side, edge_id)]):
+                skip = True
+            elif not skip:
+                read_aligns[edge_id], edge_seqs[edge_id] = self._read_records(read_align_path.format(it, side, edge_id),
+                                                                              consensuses[(it, side, edge_id)])
+            if skip or not read_aligns or not read_aligns[edge_id] or not read_aligns[edge_id][0]:
+                skip = True
+        if skip:
+            partitioning = self._read_partitioning_file(part_file.format(it - 1, side))
+        else:
+            partitioning, = self.classify_sam([(read_aligns, consensus_pos, headers_to_id, edge_seqs)])
+        self._write_partitioning_file(partitioning, part_file.format(it, side))
 
     def _read_alignment(self, alignment, target_path):
         sam = SamAlignments(self.ctx, alignment, DivergenceFinder.read_fasta(target_path), self.max_read_coverage)

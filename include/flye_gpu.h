@@ -1212,6 +1212,52 @@ int  fg_classify_reads(fg_ctx* ctx, int32_t buffer_count, uint32_t n_jobs, const
                        const uint8_t* qry_cols, uint8_t want_scores, struct fg_classify_batch* out);
 void fg_release_classify(struct fg_classify_batch* b);
 
+/* fg_expand_cigars(want_cols = 1) followed by fg_divergence_profile as ONE call, with the substitutions of
+ * fg_contig_consensus_cigars: contig bytes for contig_len, contig_aln_off for aln_contig, the records (SAM POS, CIGAR
+ * runs, SEQ, grouped by contig) for the columns; trg_start = ctg_pos - 1.  Every per-alignment array is indexed by the
+ * caller's alignment number and no offset array need start at zero.  Every field of *out equals what the two calls give
+ * for the same records; it is released with fg_release_divergence.
+ * Sub-batches of whole contigs under FG_DIVERGENCE_BATCH_COLS / FG_DIVERGENCE_BATCH_CONTIGS and the expansion's
+ * numbering (2^31 - 1 columns, runs and SEQ bytes, 2^30 - 1 alignments); each sub-batch expands its own alignments
+ * (FG_CIGAR_TILE applies, FG_CIGAR_BATCH_COLS and FG_CIGAR_BATCH_ALNS do not); the contig bytes go up once per call.
+ * The number of distinct query bytes of the call, which enters every contig's cost, is found from the records before
+ * the cut (k_seq_present over the SEQ bytes that M and I runs consume, upper-cased as the expansion stores them, and '-'
+ * where a D run has a length): it is the set the columns would show.  Where one sub-batch holds every alignment the SEQ
+ * bytes that kernel has read serve the expansion and cross the bus once; otherwise they go up a second time, per
+ * sub-batch.  The result depends on none of the switches.
+ * Errors: every code of fg_expand_cigars for the same records, then those of fg_divergence_profile that the expansion
+ * does not already exclude (FG_ERR_ARG: a threshold that is NaN or negative; a trg_start that is not inside its contig,
+ * which only an alignment of insertions alone behind the last base can be; a contig of 2^31 bytes).  FG_ERR_NOMEM: a
+ * contig that alone exceeds FG_DIVERGENCE_BATCH_COLS (the same text as fg_divergence_profile's but for the name) or the
+ * expansion's numbering.  After an error *out is all zero and the context stays usable.  n_contigs = 0 gives an empty
+ * batch. */
+int  fg_divergence_profile_cigars(fg_ctx* ctx, double sub_thresh, double del_thresh, double ins_thresh, uint32_t n_contigs,
+                                  const uint64_t* contig_off, const uint8_t* contig_seq, const uint64_t* contig_aln_off,
+                                  const int32_t* ctg_pos /* SAM POS, 1-based */, const uint64_t* run_off,
+                                  const uint8_t* run_op /* ASCII */, const uint32_t* run_len, const uint64_t* read_off,
+                                  const uint8_t* read_seq, uint8_t want_profile, struct fg_divergence_batch* out);
+
+/* fg_expand_cigars(want_cols = 1) followed by fg_classify_reads as ONE call.  The jobs, edges, lists and read numbers
+ * are those of fg_classify_reads.  The edge consensuses are the contigs of the expansion: edge e has the bytes
+ * edge_seq[edge_off[e] .. edge_off[e+1]] (edge_off is indexed by the edge number, from job_edge_off[0] on, like
+ * edge_pos_off and edge_aln_off) and its alignments edge_aln_off[e] .. edge_aln_off[e+1] lie on it: the reference aligns
+ * each edge's reads to that edge's own consensus.  ctg_pos, run_off, run_op, run_len, read_off and read_seq describe
+ * alignment a as for fg_expand_cigars; trg_start = ctg_pos - 1 and trg_end = trg_start + the consensus bytes the runs
+ * consume.  Every field of *out equals what the two calls give for the same records; it is released with
+ * fg_release_classify.
+ * Sub-batches of whole jobs under FG_PARTITION_BATCH_COLS / FG_PARTITION_BATCH_JOBS and the expansion's numbering, as
+ * above; FG_PARTITION_TILE and FG_CIGAR_TILE apply.  The edge consensuses go up once per call.
+ * Errors: every code of fg_expand_cigars for the records, those of fg_classify_reads for the rest (FG_ERR_ARG:
+ * buffer_count < 0, a job without edges, read[a] >= n_reads, edge lists of 2^31 entries); FG_ERR_NOMEM as
+ * fg_classify_reads (the same text but for the name) and for a job beyond the expansion's numbering.  After an error
+ * *out is all zero and the context stays usable.  n_jobs = 0 gives an empty batch. */
+int  fg_classify_reads_cigars(fg_ctx* ctx, int32_t buffer_count, uint32_t n_jobs, const uint64_t* job_edge_off,
+                              const uint32_t* job_n_reads, const uint64_t* edge_pos_off, const int32_t* edge_pos,
+                              const uint64_t* edge_off, const uint8_t* edge_seq, const uint64_t* edge_aln_off,
+                              const uint32_t* read, const int32_t* ctg_pos /* SAM POS, 1-based */, const uint64_t* run_off,
+                              const uint8_t* run_op /* ASCII */, const uint32_t* run_len, const uint64_t* read_off,
+                              const uint8_t* read_seq, uint8_t want_scores, struct fg_classify_batch* out);
+
 #ifdef __cplusplus
 }
 #endif
