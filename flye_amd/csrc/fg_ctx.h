@@ -384,6 +384,10 @@ struct fg_ctx {
 	DevBuf<u32> dRecvErr;
 	DevBuf<u64> dCntA, dCntB, dGroupCnt, dGroupOff, dPrimCnt, dPrimOff, dDpGroups, dDpElems;
 	DevBuf<u32> dPrimFlag, dDpSize, dListSmall, dListBig, dListDp, dListFused, dListCnt;
+	// flat listing (fg_overlap.hip, FG_GROUP_FLAT): head counts of the hit tiles (scanned in place into the tiles' first
+	// group numbers, + 1 element = nGroups), every group's first record position (+ 1 element = nPrim) and the scratch
+	// of their fgprim::scan calls
+	DevBuf<u32> dTileCnt, dPrimPos, dScanScratch;
 	DevBuf<u32> dCur, dExt;		// (cur, ext) columns of the groups in DP order
 	DevBuf<char> dPrimOut;	// PrimRec array
 	// keep_alignment: per primary the chain's last hit (global hit index), its group's first
@@ -393,7 +397,9 @@ struct fg_ctx {
 	PinnedBuf<u64> hMatches, hMatchOff;
 	PinnedBuf<u32> hMatchCnt;
 	DevBuf<char> dSortTasks, dSortBig;
-	DevBuf<unsigned long long> dSmallElems;	// DP elements in groups of <= 256 hits (work counter)
+	// DP elements in groups of <= 256 hits (work counter); the flat listing adds the call's DP groups and DP elements
+	// behind it (three totals)
+	DevBuf<unsigned long long> dSmallElems;
 	// fg_debug_chain_lazy: FG_LAZY_STRIPES rows of 8 counters the chaining kernels bump once per group (fg_chain.hip),
 	// zeroed per fg_overlaps call; the second lane's is a view of this one
 	DevBuf<unsigned long long> dLazyCnt;
@@ -525,12 +531,19 @@ struct NoVal {
 // u32 = ((extId - firstId) << curBits | curPos), PK = the packed record above, K32V16 = the u32 keys with
 // 16-bit values (every target position below 2^16: two bytes less per hit in every pass over the values)
 struct K32V16;
+// key(i) hands out the stored key; ext_of / ext_raw_of / cur_of read it as ext / ext_raw / cur read hit i (a kernel that has
+// the key in a register need not load it again)
 template <class KT> struct HitKeyView;
 template <> struct HitKeyView<u64> {
 	const u64* k; const u32* v; int curBits; u32 firstId;
 	__device__ __forceinline__ u32 ext(u64 i) const { return (u32)(k[i] >> 32); }
 	__device__ __forceinline__ u32 ext_raw(u64 i) const { return (u32)(k[i] >> 32); }
 	__device__ __forceinline__ u32 cur(u64 i) const { return (u32)k[i]; }
+	typedef u64 Word;
+	__device__ __forceinline__ u64 key(u64 i) const { return k[i]; }
+	__device__ __forceinline__ u32 ext_of(u64 x) const { return (u32)(x >> 32); }
+	__device__ __forceinline__ u32 ext_raw_of(u64 x) const { return (u32)(x >> 32); }
+	__device__ __forceinline__ u32 cur_of(u64 x) const { return (u32)x; }
 	__device__ __forceinline__ u32 val(u64 i) const { return v[i]; }
 };
 template <> struct HitKeyView<u32> {
@@ -538,6 +551,11 @@ template <> struct HitKeyView<u32> {
 	__device__ __forceinline__ u32 ext(u64 i) const { return (k[i] >> curBits) + firstId; }
 	__device__ __forceinline__ u32 ext_raw(u64 i) const { return k[i] >> curBits; }
 	__device__ __forceinline__ u32 cur(u64 i) const { return k[i] & ((1u << curBits) - 1u); }
+	typedef u32 Word;
+	__device__ __forceinline__ u32 key(u64 i) const { return k[i]; }
+	__device__ __forceinline__ u32 ext_of(u32 x) const { return (x >> curBits) + firstId; }
+	__device__ __forceinline__ u32 ext_raw_of(u32 x) const { return x >> curBits; }
+	__device__ __forceinline__ u32 cur_of(u32 x) const { return x & ((1u << curBits) - 1u); }
 	__device__ __forceinline__ u32 val(u64 i) const { return v[i]; }
 };
 template <> struct HitKeyView<K32V16> {
@@ -545,6 +563,11 @@ template <> struct HitKeyView<K32V16> {
 	__device__ __forceinline__ u32 ext(u64 i) const { return (k[i] >> curBits) + firstId; }
 	__device__ __forceinline__ u32 ext_raw(u64 i) const { return k[i] >> curBits; }
 	__device__ __forceinline__ u32 cur(u64 i) const { return k[i] & ((1u << curBits) - 1u); }
+	typedef u32 Word;
+	__device__ __forceinline__ u32 key(u64 i) const { return k[i]; }
+	__device__ __forceinline__ u32 ext_of(u32 x) const { return (x >> curBits) + firstId; }
+	__device__ __forceinline__ u32 ext_raw_of(u32 x) const { return x >> curBits; }
+	__device__ __forceinline__ u32 cur_of(u32 x) const { return x & ((1u << curBits) - 1u); }
 	__device__ __forceinline__ u32 val(u64 i) const { return v[i]; }
 };
 template <> struct HitKeyView<PK> {
@@ -552,6 +575,11 @@ template <> struct HitKeyView<PK> {
 	__device__ __forceinline__ u32 ext(u64 i) const { return (u32)(k[i].v >> (FG_PK_VALBITS + curBits)) + firstId; }
 	__device__ __forceinline__ u32 ext_raw(u64 i) const { return (u32)(k[i].v >> (FG_PK_VALBITS + curBits)); }
 	__device__ __forceinline__ u32 cur(u64 i) const { return (u32)(k[i].v >> FG_PK_VALBITS) & ((1u << curBits) - 1u); }
+	typedef u64 Word;
+	__device__ __forceinline__ u64 key(u64 i) const { return k[i].v; }
+	__device__ __forceinline__ u32 ext_of(u64 x) const { return (u32)(x >> (FG_PK_VALBITS + curBits)) + firstId; }
+	__device__ __forceinline__ u32 ext_raw_of(u64 x) const { return (u32)(x >> (FG_PK_VALBITS + curBits)); }
+	__device__ __forceinline__ u32 cur_of(u64 x) const { return (u32)(x >> FG_PK_VALBITS) & ((1u << curBits) - 1u); }
 	__device__ __forceinline__ u32 val(u64 i) const { return (u32)k[i].v & ((1u << FG_PK_VALBITS) - 1u); }
 };
 

@@ -1282,6 +1282,252 @@ __global__ void k_prim_gather(const u64* __restrict__ groupOff, const u32* __res
 	}
 }
 
+// ---- the same listings, flat over the hits and the groups (FG_GROUP_FLAT, the default) ----------------------
+// The kernels above give a query a workgroup that walks its hits (or groups) in dependent steps, a block scan behind
+// each.  Nothing they list needs the query: a group starts where two neighbouring hits differ in their target or a
+// non-empty query starts, and where a group (or a primary) goes is a prefix sum over the whole sub-range.  Here a
+// tile of FG_GROUP_TILE consecutive hits is a workgroup's whole job, its loads are issued before anything waits, and
+// fgprim::scan over the tiles' head counts (over the groups' primary counts) places the output.
+constexpr int FG_GROUP_GF = 8;						// consecutive hits per thread
+constexpr int FG_GROUP_TILE = WG * FG_GROUP_GF;		// hits per tile
+constexpr u32 NO_QUERY = 0xFFFFFFFFu;
+
+// Query starts inside the tile [tileBegin, tileEnd) of a sub-range with hits: shStartQ[i] = the non-empty query whose
+// first hit is hit tileBegin + i, NO_QUERY elsewhere (empty queries start no group; two neighbouring queries may end and
+// begin on one target record, so the keys do not tell).  Returns the query that holds hit tileBegin.
+template <int GF>
+__device__ __forceinline__ u32 tile_query_starts(const u64* __restrict__ hitOff, u32 nq, u64 tileBegin, u64 tileEnd,
+												 u32* shStartQ /* WG * GF */)
+{
+#pragma unroll
+	for (int t = 0; t < GF; ++t) shStartQ[t * WG + threadIdx.x] = NO_QUERY;
+	// the last query with hitOff[q] <= tileBegin, the same bisection in every lane: hitOff[0] = 0 <= tileBegin < nHits = hitOff[nq]
+	u32 lo = 0, hi = nq;
+	while (hi - lo > 1)
+	{
+		const u32 m = lo + ((hi - lo) >> 1);
+		if (fg_uni(hitOff[m]) <= tileBegin) lo = m; else hi = m;
+	}
+	const u32 q0 = lo;
+	__syncthreads();
+	if (threadIdx.x == 0 && hitOff[q0] == tileBegin) shStartQ[0] = q0;
+	for (u32 q = q0 + 1 + threadIdx.x; q < nq; q += WG)
+	{
+		const u64 b = hitOff[q];
+		if (b >= tileEnd) break;
+		if (hitOff[q + 1] > b) shStartQ[(u32)(b - tileBegin)] = q;
+	}
+	__syncthreads();
+	return q0;
+}
+
+// One tile: the keys of the thread's GF consecutive hits behind `first` (key[t + 1] = hit first + t, key[0] = the hit in
+// front) and their head flags (mark[t] = the query starting there).  All keys are loaded, without a branch between
+// them, before the query starts are looked for; a full tile's loads are consecutive per thread (wide loads).
+template <class KT> using HitKeyWord = typename HitKeyView<KT>::Word;
+template <class KT, int GF>
+__device__ __forceinline__ u32 tile_heads(const u64* __restrict__ hitOff, u32 nq, const HitKeyView<KT>& hitKey, u64 nHits,
+										  u32* shStartQ, u64& first, u64& tileEnd, HitKeyWord<KT> (&key)[GF + 1], bool (&head)[GF],
+										  u32 (&mark)[GF])
+{
+	const u64 tileBegin = (u64)blockIdx.x * (WG * GF);
+	tileEnd = tileBegin + WG * GF < nHits ? tileBegin + WG * GF : nHits;
+	first = tileBegin + (u64)threadIdx.x * GF;
+	const u64 last = tileEnd - 1;		// behind the tile's end: its last hit once more, never a head
+	const u64 prev = first ? first - 1 : 0;
+	key[0] = hitKey.key(prev < last ? prev : last);
+	if (tileEnd - tileBegin == WG * GF)
+	{
+#pragma unroll
+		for (int t = 0; t < GF; ++t) key[t + 1] = hitKey.key(first + t);
+	}
+	else
+	{
+#pragma unroll
+		for (int t = 0; t < GF; ++t) key[t + 1] = hitKey.key(first + t < last ? first + t : last);
+	}
+	const u32 q0 = tile_query_starts<GF>(hitOff, nq, tileBegin, tileEnd, shStartQ);
+#pragma unroll
+	for (int t = 0; t < GF; ++t)
+	{
+		mark[t] = shStartQ[threadIdx.x * GF + t];
+		head[t] = first + t < tileEnd &&		// hit 0 starts a query
+				  (mark[t] != NO_QUERY || hitKey.ext_raw_of(key[t + 1]) != hitKey.ext_raw_of(key[t]));
+	}
+	return q0;
+}
+
+// head count of every tile; tileCnt[number of tiles] = 0, so that the exclusive scan over all of it ends on nGroups
+template <class KT, int GF>
+__global__ void __launch_bounds__(WG) k_group_count_flat(const u64* __restrict__ hitOff, u32 nq, HitKeyView<KT> hitKey, u64 nHits,
+														 u32* __restrict__ tileCnt)
+{
+	__shared__ u32 shStartQ[WG * GF];
+	__shared__ u32 sh[WG / 64];
+	u64 first, tileEnd;
+	HitKeyWord<KT> key[GF + 1];
+	bool head[GF];
+	u32 mark[GF];
+	(void)tile_heads<KT, GF>(hitOff, nq, hitKey, nHits, shStartQ, first, tileEnd, key, head, mark);
+	u32 c = 0;
+#pragma unroll
+	for (int t = 0; t < GF; ++t) c += head[t];
+	for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
+	if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = c;
+	__syncthreads();
+	if (threadIdx.x == 0)
+	{
+		u32 t = 0;
+		for (int i = 0; i < WG / 64; ++i) t += sh[i];
+		tileCnt[blockIdx.x] = t;
+		if (blockIdx.x == 0) tileCnt[gridDim.x] = 0;
+	}
+}
+
+// Head number g (global: tileBase of the tile + its rank among the tile's heads) writes group g's start, query, target
+// and first query position, and closes group g - 1 -- whichever query that one belongs to; hit nHits - 1 closes the last.
+template <class KT, int GF>
+__global__ void __launch_bounds__(WG) k_group_fill_flat(const u64* __restrict__ hitOff, u32 nq, HitKeyView<KT> hitKey, u64 nHits,
+														const u32* __restrict__ tileBase, u64 nGroups, u64* __restrict__ groupStart,
+														u32* __restrict__ groupQuery, u32* __restrict__ groupExt,
+														u32* __restrict__ groupFirstCur, u32* __restrict__ groupLastCur)
+{
+	__shared__ u32 shStartQ[WG * GF];
+	__shared__ u32 shS[WG / 64], shM[WG / 64];
+	u64 first, tileEnd;
+	HitKeyWord<KT> key[GF + 1];
+	bool head[GF];
+	u32 mark[GF];
+	const u32 base = tileBase[blockIdx.x];
+	const u32 q0 = tile_heads<KT, GF>(hitOff, nq, hitKey, nHits, shStartQ, first, tileEnd, key, head, mark);
+	// two scans over the threads behind one barrier: heads in front of the thread (a sum) and the last query start in
+	// front of it (the queries ascend with the hits: a maximum; as q + 1, 0 = none in this tile)
+	u32 nHead = 0, lastQ = 0;
+#pragma unroll
+	for (int t = 0; t < GF; ++t) { nHead += head[t]; if (mark[t] != NO_QUERY) lastQ = mark[t] + 1; }
+	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+	u32 incS = nHead, incM = lastQ;
+#pragma unroll
+	for (int o = 1; o < 64; o <<= 1)
+	{
+		const u32 tS = __shfl_up(incS, o), tM = __shfl_up(incM, o);
+		if (lane >= o) { incS += tS; incM = tM > incM ? tM : incM; }
+	}
+	if (lane == 63) { shS[w] = incS; shM[w] = incM; }
+	u32 curQ = __shfl_up(incM, 1);
+	if (lane == 0) curQ = 0;
+	__syncthreads();
+	u32 pos = incS - nHead;
+	for (int i = 0; i < w; ++i) { pos += shS[i]; curQ = shM[i] > curQ ? shM[i] : curQ; }
+	u64 g = (u64)base + pos;
+#pragma unroll
+	for (int t = 0; t < GF; ++t)
+	{
+		const u64 i = first + t;
+		if (mark[t] != NO_QUERY) curQ = mark[t] + 1;
+		if (head[t])
+		{
+			groupStart[g] = i; groupQuery[g] = curQ ? curQ - 1 : q0;
+			groupExt[g] = hitKey.ext_of(key[t + 1]); groupFirstCur[g] = hitKey.cur_of(key[t + 1]);
+			if (i > 0) groupLastCur[g - 1] = hitKey.cur_of(key[t]);
+			++g;
+		}
+		if (i + 1 == nHits) groupLastCur[nGroups - 1] = hitKey.cur_of(key[t + 1]);
+	}
+}
+
+// groupOff[q] = the first group of query q (of the next query with hits, where q has none), groupOff[nq] = nGroups
+__global__ void k_group_off(const u64* __restrict__ hitOff, u32 nq, const u64* __restrict__ groupStart, u64 nGroups,
+							u64* __restrict__ groupOff)
+{
+	const u32 q = blockIdx.x * blockDim.x + threadIdx.x;
+	if (q > nq) return;
+	const u64 h = hitOff[q];
+	u64 lo = 0, hi = nGroups;
+	while (lo < hi) { const u64 m = (lo + hi) >> 1; if (groupStart[m] < h) lo = m + 1; else hi = m; }
+	groupOff[q] = lo;
+}
+
+// The work counters of k_prim_count as three totals (totals[0]: DP elements of the small class, [1]: DP groups, [2]: DP
+// elements; a bounded grid strides over the groups, so the atomics on the three words stay few), and primOff[q] = the
+// record position of query q's first group, primOff[nq] = nPrim
+constexpr unsigned PRIM_COUNT_BLOCKS = 1024;
+__global__ void __launch_bounds__(WG) k_prim_count_flat(const u32* __restrict__ dpSize, const u64* __restrict__ groupStart,
+														u64 nGroups, u64 nHits, u32 smallMax, unsigned long long* __restrict__ totals,
+														const u64* __restrict__ groupOff, const u32* __restrict__ primPos, u32 nq,
+														u64* __restrict__ primOff)
+{
+	__shared__ u64 sh[3][WG / 64];
+	const u64 stride = (u64)gridDim.x * WG;
+	for (u64 q = (u64)blockIdx.x * WG + threadIdx.x; q <= nq; q += stride) primOff[q] = primPos[groupOff[q]];
+	u64 dg = 0, de = 0, ds = 0;
+	for (u64 g = (u64)blockIdx.x * WG + threadIdx.x; g < nGroups; g += stride)
+	{
+		const u32 d = dpSize[g];
+		dg += d != 0; de += d;
+		if (d && smallMax)		// the class k_group_list routes to k_chain_small: by the group's hits before the prefilter
+		{
+			const u64 n = (g + 1 < nGroups ? groupStart[g + 1] : nHits) - groupStart[g];
+			ds += n <= smallMax ? d : 0u;
+		}
+	}
+	for (int o = 32; o > 0; o >>= 1) { dg += __shfl_down(dg, o); de += __shfl_down(de, o); ds += __shfl_down(ds, o); }
+	if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = ds; sh[1][threadIdx.x >> 6] = dg; sh[2][threadIdx.x >> 6] = de; }
+	__syncthreads();
+	if (threadIdx.x < 3)
+	{
+		u64 t = 0;
+		for (int i = 0; i < WG / 64; ++i) t += sh[threadIdx.x][i];
+		if (t) atomicAdd(totals + threadIdx.x, (unsigned long long)t);
+	}
+}
+
+// k_prim_gather with a thread per group: the records land behind the group's scanned position, (query, group,
+// selection) order as above
+__global__ void k_prim_gather_flat(u64 nGroups, const u32* __restrict__ primCount, const u32* __restrict__ primPos,
+								   const u32* __restrict__ groupQuery, const u64* __restrict__ groupStart,
+								   const u32* __restrict__ groupExt, const u32* __restrict__ gCur, const u32* __restrict__ gExt,
+								   const int4* __restrict__ cand, const i32* __restrict__ len, u32 firstId, int k,
+								   const u64* __restrict__ filtOff, const i32* __restrict__ filtPos, PrimRec* __restrict__ out,
+								   u64* __restrict__ primNode, u64* __restrict__ primBase, u64* __restrict__ matchSize)
+{
+	const u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+	if (g >= nGroups) return;
+	const u32 cnt = primCount[g];
+	if (!cnt) return;
+	const u32 q = groupQuery[g];
+	const u64 obase = primPos[g];
+	const i32* fp = filtPos + filtOff[q];
+	const i32 nf = (i32)(filtOff[q + 1] - filtOff[q]);
+	const u64 g0 = groupStart[g];
+	const u32 extId = groupExt[g];
+	const i32 extLen = len[(extId - firstId) >> 1];
+	for (u32 a = 0; a < cnt; ++a)
+	{
+		const int4 c4 = cand[g0 + a];
+		PrimRec r;
+		r.query = q; r.extId = extId;
+		r.curBegin = (i32)gCur[g0 + c4.x]; r.extBegin = (i32)gExt[g0 + c4.x];
+		r.curEnd = (i32)gCur[g0 + c4.y] + k - 1; r.extEnd = (i32)gExt[g0 + c4.y] + k - 1;
+		r.extLen = extLen; r.score = c4.w; r.chainLength = c4.z;
+		// repetitive query positions inside [curBegin, curEnd] (overlap.cpp:407-413)
+		i32 lo = 0, hi = nf;
+		while (lo < hi) { const i32 m = (lo + hi) >> 1; if (fp[m] < r.curBegin) lo = m + 1; else hi = m; }
+		const i32 firstF = lo;
+		hi = nf;
+		while (lo < hi) { const i32 m = (lo + hi) >> 1; if (fp[m] <= r.curEnd) lo = m + 1; else hi = m; }
+		r.filtered = lo - firstF;
+		r.editDistance = -1; r.hpcLenCur = 0; r.hpcLenExt = 0;
+		out[obase + a] = r;
+		if (primNode)	// keep_alignment
+		{
+			primNode[obase + a] = g0 + (u64)c4.y;
+			primBase[obase + a] = g0;
+			matchSize[obase + a] = (u64)c4.z + 2;
+		}
+	}
+}
+
 // kmerMatches of every primary (overlap.cpp:368-377, 398-405): the chain is walked again from
 // its last hit along the DP's back pointers (chainLength nodes -- where the consuming walk of
 // k_chain_finish stopped), keeping a match when it lies > k query bases before the last kept
@@ -1915,17 +2161,50 @@ static void deviceSub(fg_ctx* c, const fg_detector_params* p, uint8_t forceLocal
 	const HitKeyView<u32> hk32{c->dHitKey32.p, c->dHitVal.p, curBits, c->firstId};
 	const HitKeyView<u64> hk64{c->dHitKey.p, c->dHitVal.p, curBits, c->firstId};
 	const HitKeyView<PK> hkp{(const PK*)c->dHitKey.p, nullptr, curBits, c->firstId};
-	{ ScopedK t(c->timer, "k_group_count");
-	  if (keyMode == 0) hipLaunchKernelGGL(k_group_count<u32>, nq, WG, 0, s, c->dHitOff.p, hk32, c->dGroupCnt.p);
-	  else if (keyMode == 1) hipLaunchKernelGGL(k_group_count<PK>, nq, WG, 0, s, c->dHitOff.p, hkp, c->dGroupCnt.p);
-	  else hipLaunchKernelGGL(k_group_count<u64>, nq, WG, 0, s, c->dHitOff.p, hk64, c->dGroupCnt.p); }
-	{ ScopedK t(c->timer, "k_exscan");
-	  hipLaunchKernelGGL(k_exscan, 1, 1024, 0, s, c->dGroupCnt.p, c->dGroupOff.p, nq); }
-	const u64 nGroups = fetchScalar(c, c->dGroupOff.p + nq);
+	// FG_GROUP_FLAT=0: the per-query listing kernels (A/B runs, parity tests).  The flat form counts groups and
+	// primaries in 32 bits: a sub-range of 2^32 hits or more (none within the default hit budget) takes the other.
+	const bool flat = nHits < 0xFFFFFFFFULL && !(getenv("FG_GROUP_FLAT") && atoi(getenv("FG_GROUP_FLAT")) == 0);
+	const u64 nTiles = (nHits + FG_GROUP_TILE - 1) / FG_GROUP_TILE;
+	u64 nGroups = 0;
+	if (!flat)
+	{
+		{ ScopedK t(c->timer, "k_group_count");
+		  if (keyMode == 0) hipLaunchKernelGGL(k_group_count<u32>, nq, WG, 0, s, c->dHitOff.p, hk32, c->dGroupCnt.p);
+		  else if (keyMode == 1) hipLaunchKernelGGL(k_group_count<PK>, nq, WG, 0, s, c->dHitOff.p, hkp, c->dGroupCnt.p);
+		  else hipLaunchKernelGGL(k_group_count<u64>, nq, WG, 0, s, c->dHitOff.p, hk64, c->dGroupCnt.p); }
+		{ ScopedK t(c->timer, "k_exscan");
+		  hipLaunchKernelGGL(k_exscan, 1, 1024, 0, s, c->dGroupCnt.p, c->dGroupOff.p, nq); }
+		nGroups = fetchScalar(c, c->dGroupOff.p + nq);
+	}
+	else if (nTiles)		// no hits: no groups, and nothing to wait for
+	{
+		c->dTileCnt.reserve(nTiles + 1); c->dScanScratch.reserve(fgprim::scanScratchElems(nTiles + 1));
+		{ ScopedK t(c->timer, "k_group_count");
+		  if (keyMode == 0) hipLaunchKernelGGL((k_group_count_flat<u32, FG_GROUP_GF>), (unsigned)nTiles, WG, 0, s, c->dHitOff.p, nq, hk32, nHits, c->dTileCnt.p);
+		  else if (keyMode == 1) hipLaunchKernelGGL((k_group_count_flat<PK, FG_GROUP_GF>), (unsigned)nTiles, WG, 0, s, c->dHitOff.p, nq, hkp, nHits, c->dTileCnt.p);
+		  else hipLaunchKernelGGL((k_group_count_flat<u64, FG_GROUP_GF>), (unsigned)nTiles, WG, 0, s, c->dHitOff.p, nq, hk64, nHits, c->dTileCnt.p); }
+		{ ScopedK t(c->timer, "k_group_scan");		// in place: the tiles' first group numbers, nGroups behind them
+		  fgprim::scan<u32>(s, c->dTileCnt.p, c->dTileCnt.p, nTiles + 1, false, c->dScanScratch.p); }
+		nGroups = fetchScalar(c, c->dTileCnt.p + nTiles);
+	}
 	if (nGroups >= 0xFFFFFFFFULL) throw FgError{FG_ERR_ARG, "too many target groups in one chunk"};
 	c->dGroupStart.reserve(nGroups + 1); c->dGroupQuery.reserve(nGroups + 1);
 	c->dGroupExt.reserve(nGroups + 1); c->dGroupFirstCur.reserve(nGroups + 1); c->dGroupLastCur.reserve(nGroups + 1);
 	c->dPrimFlag.reserve(nGroups + 1); c->dDpSize.reserve(nGroups + 1);
+	if (flat)
+	{
+		if (nTiles)
+		{ ScopedK t(c->timer, "k_group_fill");
+		  if (keyMode == 0) hipLaunchKernelGGL((k_group_fill_flat<u32, FG_GROUP_GF>), (unsigned)nTiles, WG, 0, s, c->dHitOff.p, nq, hk32, nHits, c->dTileCnt.p,
+											   nGroups, c->dGroupStart.p, c->dGroupQuery.p, c->dGroupExt.p, c->dGroupFirstCur.p, c->dGroupLastCur.p);
+		  else if (keyMode == 1) hipLaunchKernelGGL((k_group_fill_flat<PK, FG_GROUP_GF>), (unsigned)nTiles, WG, 0, s, c->dHitOff.p, nq, hkp, nHits, c->dTileCnt.p,
+													nGroups, c->dGroupStart.p, c->dGroupQuery.p, c->dGroupExt.p, c->dGroupFirstCur.p, c->dGroupLastCur.p);
+		  else hipLaunchKernelGGL((k_group_fill_flat<u64, FG_GROUP_GF>), (unsigned)nTiles, WG, 0, s, c->dHitOff.p, nq, hk64, nHits, c->dTileCnt.p,
+								  nGroups, c->dGroupStart.p, c->dGroupQuery.p, c->dGroupExt.p, c->dGroupFirstCur.p, c->dGroupLastCur.p); }
+		ScopedK t(c->timer, "k_group_off");
+		hipLaunchKernelGGL(k_group_off, (nq + 1 + WG - 1) / WG, WG, 0, s, c->dHitOff.p, nq, c->dGroupStart.p, nGroups, c->dGroupOff.p);
+	}
+	else
 	{ ScopedK t(c->timer, "k_group_fill");
 	  if (keyMode == 0) hipLaunchKernelGGL(k_group_fill<u32>, nq, WG, 0, s, c->dHitOff.p, hk32, c->dGroupOff.p, c->dGroupStart.p,
 										   c->dGroupQuery.p, c->dGroupExt.p, c->dGroupFirstCur.p, c->dGroupLastCur.p);
@@ -1934,18 +2213,51 @@ static void deviceSub(fg_ctx* c, const fg_detector_params* p, uint8_t forceLocal
 	  else hipLaunchKernelGGL(k_group_fill<u64>, nq, WG, 0, s, c->dHitOff.p, hk64, c->dGroupOff.p, c->dGroupStart.p,
 							  c->dGroupQuery.p, c->dGroupExt.p, c->dGroupFirstCur.p, c->dGroupLastCur.p); }
 	fgChainStage(c, p, forceLocal, nGroups, nHits, keyMode, curBits);
-	c->dSmallElems.reserve(1);
-	HIP_CHECK(hipMemsetAsync(c->dSmallElems.p, 0, 8, s));
-	{ ScopedK t(c->timer, "k_prim_count");
-	  hipLaunchKernelGGL(k_prim_count, nq, WG, 0, s, c->dGroupOff.p, c->dPrimFlag.p, c->dDpSize.p, c->dPrimCnt.p,
-						 c->dDpGroups.p, c->dDpElems.p, c->dGroupStart.p, nGroups, nHits, fgChainSmallMax(), c->dSmallElems.p); }
-	{ ScopedK t(c->timer, "k_exscan");
-	  hipLaunchKernelGGL(k_exscan, 1, 1024, 0, s, c->dPrimCnt.p, c->dPrimOff.p, nq); }
-	const u64 nPrim = fetchScalar(c, c->dPrimOff.p + nq);
+	c->dSmallElems.reserve(3);
+	HIP_CHECK(hipMemsetAsync(c->dSmallElems.p, 0, 24, s));
+	u64 nPrim = 0;
+	if (flat)
+	{
+		c->dPrimPos.reserve(nGroups + 1); c->dScanScratch.reserve(fgprim::scanScratchElems(nGroups + 1));
+		HIP_CHECK(hipMemsetAsync(c->dPrimFlag.p + nGroups, 0, 4, s));		// the scan below ends on nPrim
+		{ ScopedK t(c->timer, "k_prim_scan");
+		  fgprim::scan<u32>(s, c->dPrimFlag.p, c->dPrimPos.p, nGroups + 1, false, c->dScanScratch.p); }
+		// the total is on its way to the host while the counters and the per-query offsets are made
+		c->hScalar.reserve(8);
+		HIP_CHECK(hipMemcpyAsync(c->hScalar.p, c->dPrimPos.p + nGroups, 4, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(hipEventRecord(c->evOff, s));
+		{ ScopedK t(c->timer, "k_prim_count");
+		  const u64 n = std::max<u64>(nGroups, (u64)nq + 1);
+		  hipLaunchKernelGGL(k_prim_count_flat, (unsigned)std::min<u64>(PRIM_COUNT_BLOCKS, (n + WG - 1) / WG), WG, 0, s, c->dDpSize.p, c->dGroupStart.p, nGroups, nHits,
+							 fgChainSmallMax(), c->dSmallElems.p, c->dGroupOff.p, c->dPrimPos.p, nq, c->dPrimOff.p); }
+		HIP_CHECK(hipEventSynchronize(c->evOff));
+		u32 v;
+		memcpy(&v, c->hScalar.p, 4);
+		nPrim = v;
+	}
+	else
+	{
+		{ ScopedK t(c->timer, "k_prim_count");
+		  hipLaunchKernelGGL(k_prim_count, nq, WG, 0, s, c->dGroupOff.p, c->dPrimFlag.p, c->dDpSize.p, c->dPrimCnt.p,
+							 c->dDpGroups.p, c->dDpElems.p, c->dGroupStart.p, nGroups, nHits, fgChainSmallMax(), c->dSmallElems.p); }
+		{ ScopedK t(c->timer, "k_exscan");
+		  hipLaunchKernelGGL(k_exscan, 1, 1024, 0, s, c->dPrimCnt.p, c->dPrimOff.p, nq); }
+		nPrim = fetchScalar(c, c->dPrimOff.p + nq);
+	}
 	c->dPrimOut.reserve((nPrim + 1) * sizeof(PrimRec));
 	const bool keepAln = p->keep_alignment;
 	if (keepAln) { c->dPrimNode.reserve(nPrim + 1); c->dPrimBase.reserve(nPrim + 1); c->dMatchSize.reserve(nPrim + 1);
 				   c->dMatchOff.reserve(nPrim + 2); c->dMatchCnt.reserve(nPrim + 1); }
+	if (flat)
+	{
+		if (nPrim)
+		{ ScopedK t(c->timer, "k_prim_gather");
+		  hipLaunchKernelGGL(k_prim_gather_flat, (unsigned)((nGroups + WG - 1) / WG), WG, 0, s, nGroups, c->dPrimFlag.p, c->dPrimPos.p,
+							 c->dGroupQuery.p, c->dGroupStart.p, c->dGroupExt.p, c->dCur.p, c->dExt.p, c->dCand.p, c->dLen.p, c->firstId, k,
+							 c->dFiltOff.p, c->dFiltPos.p, (PrimRec*)c->dPrimOut.p, keepAln ? c->dPrimNode.p : (u64*)nullptr,
+							 keepAln ? c->dPrimBase.p : (u64*)nullptr, keepAln ? c->dMatchSize.p : (u64*)nullptr); }
+	}
+	else
 	{ ScopedK t(c->timer, "k_prim_gather");
 	  hipLaunchKernelGGL(k_prim_gather, nq, WG, 0, s, c->dGroupOff.p, c->dPrimFlag.p, c->dGroupStart.p, c->dGroupExt.p,
 						 c->dCur.p, c->dExt.p, c->dCand.p, c->dLen.p, c->firstId, k, c->dFiltOff.p, c->dFiltPos.p,
@@ -1978,12 +2290,17 @@ static void deviceSub(fg_ctx* c, const fg_detector_params* p, uint8_t forceLocal
 		HIP_CHECK(hipStreamSynchronize(s));		// copies of earlier chunks may still be on their way into the old buffer
 		c->hPrim.reserveKeep((primBase + nPrim + 1) * sizeof(PrimRec), primBase * sizeof(PrimRec));
 	}
-	c->hOff.reserve(3 * (size_t)(nq + 1) + 1);
+	// hOff: the per-query record offsets (nq + 1); the per-query DP groups and DP elements of the per-query form
+	// (nq + 1 each; the flat form leaves them alone); the three totals of dSmallElems
+	c->hOff.reserve(3 * (size_t)(nq + 1) + 3);
 	{ ScopedK t(c->timer, "copy_results_d2h");
 	  HIP_CHECK(hipMemcpyAsync(c->hOff.p, c->dPrimOff.p, (nq + 1) * 8ULL, hipMemcpyDeviceToHost, s));
-	  HIP_CHECK(hipMemcpyAsync(c->hOff.p + (nq + 1), c->dDpGroups.p, nq * 8ULL, hipMemcpyDeviceToHost, s));
-	  HIP_CHECK(hipMemcpyAsync(c->hOff.p + 2 * (size_t)(nq + 1), c->dDpElems.p, nq * 8ULL, hipMemcpyDeviceToHost, s));
-	  HIP_CHECK(hipMemcpyAsync(c->hOff.p + 3 * (size_t)(nq + 1), c->dSmallElems.p, 8, hipMemcpyDeviceToHost, s));
+	  if (!flat)
+	  {
+		  HIP_CHECK(hipMemcpyAsync(c->hOff.p + (nq + 1), c->dDpGroups.p, nq * 8ULL, hipMemcpyDeviceToHost, s));
+		  HIP_CHECK(hipMemcpyAsync(c->hOff.p + 2 * (size_t)(nq + 1), c->dDpElems.p, nq * 8ULL, hipMemcpyDeviceToHost, s));
+	  }
+	  HIP_CHECK(hipMemcpyAsync(c->hOff.p + 3 * (size_t)(nq + 1), c->dSmallElems.p, 24, hipMemcpyDeviceToHost, s));
 	  HIP_CHECK(hipEventRecord(c->evOff, s));
 	  // the records in pieces, an event behind each: the caller does not wait for them here (the host shim's
 	  // threads wait for the piece they read)
@@ -2004,7 +2321,8 @@ static void deviceSub(fg_ctx* c, const fg_detector_params* p, uint8_t forceLocal
 	res->nPrim = nPrim;
 	res->dpGroups = 0; res->dpElems = 0;
 	res->dpElemsSmall = c->hOff.p[3 * (size_t)(nq + 1)];
-	for (u32 i = 0; i < nq; ++i) { res->dpGroups += c->hOff.p[(nq + 1) + i]; res->dpElems += c->hOff.p[2 * (size_t)(nq + 1) + i]; }
+	if (flat) { res->dpGroups = c->hOff.p[3 * (size_t)(nq + 1) + 1]; res->dpElems = c->hOff.p[3 * (size_t)(nq + 1) + 2]; }
+	else for (u32 i = 0; i < nq; ++i) { res->dpGroups += c->hOff.p[(nq + 1) + i]; res->dpElems += c->hOff.p[2 * (size_t)(nq + 1) + i]; }
 }
 
 // Chunk budgets of the overlap stage: query k-mers per probed chunk, seed hits per sub-range
