@@ -138,7 +138,10 @@ __global__ void k_probe(const u32* __restrict__ query, const u64* __restrict__ w
 			if (cnt == FG_CNT_REPETITIVE) ++filt;
 			else
 			{
-				const u32 self = (selfWord >> (bit & 31)) & 1u;
+				// a k-mer that is its own reverse complement (even k) is stored under the FORWARD record: for a
+				// reverse-strand query its own entry is (rec ^ 1, L - k - p) -- not the trivial match of
+				// overlap.cpp:188-190, it stays a hit
+				const u32 self = ((selfWord >> (bit & 31)) & 1u) && !(rc && fw == rv);
 				hits += cnt - self;
 				if (self) v |= FLAG_SELF;
 				if (flip) v |= FLAG_FLIP;
@@ -196,7 +199,7 @@ __global__ void k_probe_emit(u32 q0, const u32* __restrict__ query, const u64* _
 		{
 			const i32 qf = rc ? nk - p : p;
 			const u64 bit = kbase + (u64)qf;
-			const u32 self = (indexedBits && qf < nk) ? ((indexedBits[bit >> 5] >> (bit & 31)) & 1u) : 0u;
+			u32 self = (indexedBits && qf < nk) ? ((indexedBits[bit >> 5] >> (bit & 31)) & 1u) : 0u;
 			emit = (maybeBits && qf < nk) ? ((maybeBits[bit >> 5] >> (bit & 31)) & 1u) : true;
 			if (emit)
 			{
@@ -205,6 +208,7 @@ __global__ void k_probe_emit(u32 q0, const u32* __restrict__ query, const u64* _
 				const u64 fw = rc ? b : a, rv = rc ? a : b;
 				const bool flip = rv < fw;
 				const u64 km = flip ? rv : fw;
+				if (rc && fw == rv) self = 0;	// its own reverse complement: the entry is the forward record's (see k_probe)
 				u32 part = 0;
 				if (table.nParts > 1)
 					while (part + 1 < table.nParts && km >= table.bound[part + 1]) ++part;
