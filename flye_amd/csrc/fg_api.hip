@@ -77,7 +77,7 @@ const char* fg_strerror(int code)
 	}
 }
 
-const char* fg_last_error(const fg_ctx* ctx) { return ctx ? ctx->lastError.c_str() : ""; }
+const char* fg_last_error(const fg_ctx* ctx) { return ctx ? ctx->lastError.c_str() : fgHostError().c_str(); }
 
 int fg_create(fg_ctx** out, int device, int kmer_size)
 {

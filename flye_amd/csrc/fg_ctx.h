@@ -467,6 +467,8 @@ struct fg_ctx {
 	DevBuf<char> dDv[28];
 	// fg_confirm_positions / fg_classify_reads (fg_partition.hip): the buffers of one sub-batch, handed out in call order
 	DevBuf<char> dPt[36];
+	// fg_paf_groups / fg_paf_circular / fg_components (fg_plasmid.hip): the buffers of one call, handed out in call order
+	DevBuf<char> dPaf[32];
 	PinnedBuf<char> hPrim;
 	PinnedBuf<u64> hOff;
 	PinnedBuf<u64> hScalar;		// staging of the counts the host reads between kernels (pinned: no bounce buffer)

@@ -3,3 +3,10 @@
 #include <string>
 
 struct FgError { int code; std::string msg; };
+
+// the text of the calling thread's last failed call that has no context (fg_paf_parse); fg_last_error(NULL) returns it
+inline std::string& fgHostError()
+{
+	static thread_local std::string text;
+	return text;
+}

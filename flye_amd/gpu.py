@@ -29,6 +29,9 @@ like calls into the reference:
   consensuses, confirmed_pos_path, part_file, headers_to_id)`` / ``confirm`` / ``classify``
   (flye/trestle/trestle.py:1075-1628, on fg_confirm_positions and fg_classify_reads); ``partition_reads_sam`` /
   ``classify_sam`` on fg_classify_reads_cigars
+* ``PlasmidFinder(ctx).calc_mapping_rates / extract_unmapped_reads / extract_circular_reads / extract_circular_pairs /
+  trim_circular_reads / trim_circular_pairs / extract_unique_plasmids``  (flye/short_plasmids/unmapped_reads.py:51-88 and
+  circular_sequences.py:33-191, on fg_paf_parse, fg_paf_groups, fg_paf_circular and fg_components)
 
 There is no CPU fallback: if the HIP library or a device is missing every entry
 point raises ``FlyeGpuError``.
@@ -73,6 +76,8 @@ ABI_SYMBOLS = ["fg_abi_version", "fg_create", "fg_destroy", "fg_strerror", "fg_l
                "fg_divergence_profile", "fg_release_divergence",
                "fg_confirm_positions", "fg_release_confirm", "fg_classify_reads", "fg_release_classify",
                "fg_divergence_profile_cigars", "fg_classify_reads_cigars",
+               "fg_paf_groups", "fg_release_paf_groups", "fg_paf_circular", "fg_release_paf_circular", "fg_components",
+               "fg_paf_parse", "fg_release_paf_text",
                "fg_index_keep_targets", "fg_index_shard", "fg_probe_hits", "fg_overlaps_from_hits",
                "fg_index_piece_split", "fg_index_scatter_begin", "fg_index_scatter_end", "fg_debug_probe_skip_check",
                "fg_group_create", "fg_group_destroy", "fg_group_size", "fg_group_member", "fg_group_last_error",
@@ -90,6 +95,10 @@ RANGE_PAIR_DTYPE = np.dtype([("cur_id", "<u4"), ("ext_id", "<u4"), ("cur_begin",
 TRIM_REC_DTYPE = np.dtype([("cur_begin", "<i4"), ("cur_end", "<i4"), ("ext_begin", "<i4"), ("ext_end", "<i4"),
                            ("run_start", "<i4"), ("run_end", "<i4"), ("range_err", "<i4"), ("range_len", "<i4"),
                            ("seq_divergence", "<f4")])
+
+# struct fg_paf_hit: one PAF line, names as ids of one name space (fg_paf_groups / fg_paf_circular)
+PAF_HIT_DTYPE = np.dtype([("query", "<u4"), ("target", "<u4"), ("query_len", "<i4"), ("query_start", "<i4"), ("query_end", "<i4"),
+                          ("target_len", "<i4"), ("target_start", "<i4"), ("target_end", "<i4")])
 
 # struct fg_seed_hit: KmerMatch{curPos, extPos, extId} (overlap.cpp:176-196)
 SEED_HIT_DTYPE = np.dtype([("cur_pos", "<i4"), ("ext_pos", "<i4"), ("ext_id", "<u4")])
@@ -284,6 +293,27 @@ class ClassifyBatch(C.Structure):
                 ("owner_", C.c_void_p)]
 
 
+class PafGroupBatch(C.Structure):
+    _fields_ = [("n_hits", C.c_uint64), ("n_groups", C.c_uint32), ("order", C.POINTER(C.c_uint32)),
+                ("group_off", C.POINTER(C.c_uint64)), ("group_query", C.POINTER(C.c_uint32)), ("group_target", C.POINTER(C.c_uint32)),
+                ("query_cover", C.POINTER(C.c_int64)), ("target_cover", C.POINTER(C.c_int64)), ("owner_", C.c_void_p)]
+
+
+class PafCircularBatch(C.Structure):
+    _fields_ = [("n_hits", C.c_uint64), ("n_circular", C.c_uint32), ("circ_query", C.POINTER(C.c_uint32)),
+                ("circ_hit", C.POINTER(C.c_uint32)), ("n_groups", C.c_uint32), ("group_query", C.POINTER(C.c_uint32)),
+                ("group_target", C.POINTER(C.c_uint32)), ("pair_first", C.POINTER(C.c_int32)), ("pair_second", C.POINTER(C.c_int32)),
+                ("pair_ok", C.POINTER(C.c_uint8)), ("owner_", C.c_void_p)]
+
+
+class PafText(C.Structure):
+    _fields_ = [("n_hits", C.c_uint64), ("query_name_off", C.POINTER(C.c_uint64)), ("query_name_len", C.POINTER(C.c_uint32)),
+                ("target_name_off", C.POINTER(C.c_uint64)), ("target_name_len", C.POINTER(C.c_uint32)),
+                ("query_len", C.POINTER(C.c_int32)), ("query_start", C.POINTER(C.c_int32)), ("query_end", C.POINTER(C.c_int32)),
+                ("target_len", C.POINTER(C.c_int32)), ("target_start", C.POINTER(C.c_int32)), ("target_end", C.POINTER(C.c_int32)),
+                ("owner_", C.c_void_p)]
+
+
 class BridgeStats(C.Structure):
     _fields_ = [("device_calls", C.c_uint64), ("reads_computed", C.c_uint64), ("requests", C.c_uint64),
                 ("cache_hits", C.c_uint64), ("cached_overlaps", C.c_uint64), ("reads_ahead", C.c_uint64),
@@ -471,6 +501,13 @@ def load_library():
                                         C.c_uint8, C.POINTER(OverlapBatch)]
         L.fg_group_stats.argtypes = [C.c_void_p, C.POINTER(GroupStats)]
         L.fg_group_build_info.argtypes = [C.c_void_p, C.POINTER(GroupBuildInfo)]
+        L.fg_paf_groups.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(PafGroupBatch)]
+        L.fg_release_paf_groups.argtypes = [C.POINTER(PafGroupBatch)]
+        L.fg_paf_circular.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.POINTER(PafCircularBatch)]
+        L.fg_release_paf_circular.argtypes = [C.POINTER(PafCircularBatch)]
+        L.fg_components.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.fg_paf_parse.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(PafText)]
+        L.fg_release_paf_text.argtypes = [C.POINTER(PafText)]
         # include/flye_gpu_bridge.h
         L.fgb_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(DetectorParams), C.c_uint32, C.c_uint32]
         L.fgb_destroy.argtypes = [C.c_void_p]
@@ -768,6 +805,57 @@ def cigar_parse(cigar):
     if rc != 0:
         raise FlyeGpuError(rc, "fg_cigar_parse: " + L.fg_strerror(rc).decode())
     return ops[:n.value], lens[:n.value]
+
+
+class PafHits:
+    """fg_paf_text copied out of its arena, for the PAF buffer `text`: `hits` (PAF_HIT_DTYPE, file order) with the ids
+    of `names` (bytes, the distinct names of the file in ascending byte order); first_seen: the ids in order of first
+    appearance, the query before the target of a line."""
+
+    def __init__(self, text, hits, names, first_seen):
+        self.text, self.hits, self.names, self.first_seen = text, hits, names, first_seen
+
+    def name(self, i):
+        return self.names[int(i)].decode()
+
+
+def paf_parse(text):
+    """fg_paf_parse on a whole PAF buffer (bytes) -> PafHits.  The tokens come from the library; the ids are numpy's:
+    the names gathered into fixed-width byte strings, np.unique for the ranks."""
+    L = load_library()
+    text = bytes(text)
+    b = PafText()
+    t0 = time.perf_counter()
+    rc = L.fg_paf_parse(text, len(text), C.byref(b))
+    if rc != 0:
+        raise FlyeGpuError(rc, L.fg_last_error(None).decode())
+    t1 = time.perf_counter()
+    n = int(b.n_hits)
+    hits = np.zeros(n, PAF_HIT_DTYPE)
+    if n == 0:
+        L.fg_release_paf_text(C.byref(b))
+        return PafHits(text, hits, [], np.zeros(0, np.uint32))
+    take = lambda ptr: np.ctypeslib.as_array(ptr, (n,)).copy()
+    for f in ("query_len", "query_start", "query_end", "target_len", "target_start", "target_end"):
+        hits[f] = take(getattr(b, f))
+    off = np.concatenate([take(b.query_name_off), take(b.target_name_off)]).astype(np.int64)
+    ln = np.concatenate([take(b.query_name_len), take(b.target_name_len)]).astype(np.int64)
+    L.fg_release_paf_text(C.byref(b))
+    width = int(ln.max())
+    raw = np.frombuffer(text, np.uint8)
+    col = np.arange(width, dtype=np.int64)
+    idx = np.minimum(off[:, None] + col[None, :], len(raw) - 1)
+    table = np.where(col[None, :] < ln[:, None], raw[idx], 0).astype(np.uint8)
+    keys = np.ascontiguousarray(table).view("S%d" % width).ravel()       # a name holds no NUL: no blank ends a field
+    names, ids = np.unique(keys, return_inverse=True)
+    ids = ids.ravel()
+    hits["query"], hits["target"] = ids[:n], ids[n:]
+    # position in file order: line i's query is 2 i, its target 2 i + 1
+    pos = np.full(len(names), 2 * n, np.int64)
+    np.minimum.at(pos, ids, np.concatenate([2 * np.arange(n), 2 * np.arange(n) + 1]))
+    out = PafHits(text, hits, [bytes(x) for x in names.tolist()], np.argsort(pos, kind="stable").astype(np.uint32))
+    out.parse_seconds, out.id_seconds = t1 - t0, time.perf_counter() - t1        # the tokeniser; the copies and the ids
+    return out
 
 
 class PolishResult:
@@ -1641,6 +1729,51 @@ class Context:
             out_chains += mine + [complement(ch)[::-1] for ch in mine]
             out_off.append(len(out_chains))
         return ReadAlignments(q, out_off, out_chains, self.first_id, nl, nr, chain_off, chain_div)
+
+    def paf_groups(self, hits):
+        """fg_paf_groups on hits (PAF_HIT_DTYPE, file order) -> dict of order, group_off, group_query, group_target,
+        query_cover, target_cover"""
+        h = np.ascontiguousarray(hits, PAF_HIT_DTYPE)
+        b = PafGroupBatch()
+        t0 = time.perf_counter()
+        self._check(self.L.fg_paf_groups(self.h, h.ctypes.data if len(h) else None, len(h), C.byref(b)))
+        self.last_paf_seconds = time.perf_counter() - t0
+        ng = int(b.n_groups)
+        take = lambda ptr, n, dtype: np.ctypeslib.as_array(ptr, (n,)).copy() if n else np.zeros(0, dtype)
+        out = dict(order=take(b.order, len(h), np.uint32), group_off=take(b.group_off, ng + 1, np.uint64),
+                   group_query=take(b.group_query, ng, np.uint32), group_target=take(b.group_target, ng, np.uint32),
+                   query_cover=take(b.query_cover, ng, np.int64), target_cover=take(b.target_cover, ng, np.int64))
+        self.L.fg_release_paf_groups(C.byref(b))
+        return out
+
+    def paf_circular(self, hits, max_overhang_read=150, max_overhang_pair=300):
+        """fg_paf_circular on hits (PAF_HIT_DTYPE, file order) -> dict of circ_query, circ_hit, group_query,
+        group_target, pair_first, pair_second, pair_ok"""
+        h = np.ascontiguousarray(hits, PAF_HIT_DTYPE)
+        b = PafCircularBatch()
+        t0 = time.perf_counter()
+        self._check(self.L.fg_paf_circular(self.h, h.ctypes.data if len(h) else None, len(h), int(max_overhang_read),
+                                           int(max_overhang_pair), C.byref(b)))
+        self.last_paf_seconds = time.perf_counter() - t0
+        nc, ng = int(b.n_circular), int(b.n_groups)
+        take = lambda ptr, n, dtype: np.ctypeslib.as_array(ptr, (n,)).copy() if n else np.zeros(0, dtype)
+        out = dict(circ_query=take(b.circ_query, nc, np.uint32), circ_hit=take(b.circ_hit, nc, np.uint32),
+                   group_query=take(b.group_query, ng, np.uint32), group_target=take(b.group_target, ng, np.uint32),
+                   pair_first=take(b.pair_first, ng, np.int32), pair_second=take(b.pair_second, ng, np.int32),
+                   pair_ok=take(b.pair_ok, ng, np.uint8))
+        self.L.fg_release_paf_circular(C.byref(b))
+        return out
+
+    def components(self, n_vertices, edge_u, edge_v):
+        """fg_components: labels[v] = the smallest vertex of v's connected component"""
+        u = np.ascontiguousarray(edge_u, np.uint32)
+        v = np.ascontiguousarray(edge_v, np.uint32)
+        if len(u) != len(v):
+            raise ValueError("components: edge_u and edge_v differ in length")
+        labels = np.zeros(int(n_vertices), np.uint32)
+        self._check(self.L.fg_components(self.h, int(n_vertices), len(u), u.ctypes.data if len(u) else None,
+                                         v.ctypes.data if len(v) else None, labels.ctypes.data if len(labels) else None))
+        return labels
 
     def kernel_times(self):
         arr = (KernelTime * 64)()
@@ -3219,3 +3352,131 @@ class SamAlignments:
             run_op=np.concatenate([r.ops for r in recs]) if recs else np.zeros(0, np.uint8),
             run_len=np.concatenate([r.lens for r in recs]) if recs else np.zeros(0, np.uint32),
             read_off=np.cumsum([0] + [len(r.seq) for r in recs]), read_seq=b"".join(r.seq for r in recs))
+
+
+class PlasmidFinder:
+    """Mirror of the reference's short-plasmid rescue (flye/short_plasmids/unmapped_reads.py, circular_sequences.py,
+    utils.py) with one device call per pass: a PAF file is read at once, tokenised by fg_paf_parse, and its hits go to
+    fg_paf_groups (calc_mapping_rates, extract_unique_plasmids), fg_paf_circular (extract_circular_reads,
+    extract_circular_pairs) and fg_components.  The divisions, round(.., 3), the thresholds, the greedy used_reads filter
+    and the slices are Python, as in the reference.  Names are str, hits are PafHit records with the reference's fields."""
+
+    PafHit = collections.namedtuple("PafHit", ["query", "query_length", "query_start", "query_end", "target", "target_length",
+                                               "target_start", "target_end"])
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+
+    @staticmethod
+    def read_paf(path):
+        opener = gzip.open if path.endswith(".gz") else open
+        with opener(path, "rb") as f:
+            return paf_parse(f.read())
+
+    @classmethod
+    def _hit(cls, paf, i):
+        h = paf.hits[int(i)]
+        return cls.PafHit(paf.name(h["query"]), int(h["query_len"]), int(h["query_start"]), int(h["query_end"]),
+                          paf.name(h["target"]), int(h["target_len"]), int(h["target_start"]), int(h["target_end"]))
+
+    @staticmethod
+    def stream_sequence(path):
+        """(header, sequence) as str for the records of a FASTA or FASTQ file, plain or .gz, by its suffix"""
+        plain = path[:-3] if path.endswith(".gz") else path
+        if plain.endswith((".fasta", ".fa")):
+            for h, s in DivergenceFinder.read_fasta(path).items():
+                yield h.decode(), s.decode()
+        elif plain.endswith((".fastq", ".fq")):
+            opener = gzip.open if path.endswith(".gz") else open
+            with opener(path, "rb") as f:
+                lines = [ln.strip() for ln in f if ln.strip()]
+            for k in range(0, len(lines) - 3, 4):
+                if not lines[k].startswith(b"@") or not lines[k + 2].startswith(b"+"):
+                    raise ValueError("Fastq format error: " + path)
+                yield lines[k][1:].split()[0].decode(), lines[k + 1].translate(DivergenceFinder.TO_ACGT).decode()
+        else:
+            raise ValueError("Unknown file extension: " + path)
+
+    def calc_mapping_rates(self, paf_path):
+        """{query: {target: rate}} of calc_mapping_rates (unmapped_reads.py:51-61)"""
+        paf = paf_path if isinstance(paf_path, PafHits) else self.read_paf(paf_path)
+        g = self.ctx.paf_groups(paf.hits)
+        first = paf.hits[g["order"][g["group_off"][:-1].astype(np.int64)].astype(np.int64)]
+        rates = collections.defaultdict(dict)
+        for q, t, cover, length in zip(first["query"].tolist(), first["target"].tolist(), g["query_cover"].tolist(),
+                                       first["query_len"].tolist()):
+            rates[paf.name(q)][paf.name(t)] = round(cover / length, 3)
+        return rates
+
+    def extract_unmapped_reads(self, read_files, paf_path, unmapped_reads_path, mapping_rate_threshold):
+        """extract_unmapped_reads (unmapped_reads.py:64-88); returns (total bases, unmapped bases)"""
+        rates = self.calc_mapping_rates(paf_path)
+        total = unmapped = 0
+        with open(unmapped_reads_path, "w") as out:
+            for path in read_files:
+                for hdr, seq in self.stream_sequence(path):
+                    total += len(seq)
+                    contigs = rates.get(hdr)
+                    if contigs is None or not any(r >= mapping_rate_threshold for r in contigs.values()):
+                        unmapped += len(seq)
+                        out.write(">{0}\n{1}\n".format(hdr, seq))
+        return total, unmapped
+
+    def extract_circular_reads(self, paf_path, max_overhang=150):
+        """{read: PafHit} in the reference's dict order (circular_sequences.py:33-44)"""
+        paf = paf_path if isinstance(paf_path, PafHits) else self.read_paf(paf_path)
+        c = self.ctx.paf_circular(paf.hits, max_overhang, 300)
+        return {paf.name(q): self._hit(paf, i) for q, i in zip(c["circ_query"].tolist(), c["circ_hit"].tolist())}
+
+    def extract_circular_pairs(self, paf_path, max_overhang=300):
+        """[[hit, hit]] of extract_circular_pairs (:82-118): the device finds every group's candidate, the greedy
+        used_reads filter runs here over the groups in order"""
+        paf = paf_path if isinstance(paf_path, PafHits) else self.read_paf(paf_path)
+        c = self.ctx.paf_circular(paf.hits, 150, max_overhang)
+        used, pairs = set(), []
+        for k in np.flatnonzero(c["pair_ok"]).tolist():
+            q, t = int(c["group_query"][k]), int(c["group_target"][k])
+            if q in used or t in used:
+                continue
+            used.update((q, t))
+            pairs.append([self._hit(paf, c["pair_first"][k]), self._hit(paf, c["pair_second"][k])])
+        return pairs
+
+    @staticmethod
+    def trim_circular_reads(circular_reads, unmapped_reads):
+        return {"circular_read_" + str(i): unmapped_reads[read][:hit.target_start].upper()
+                for i, (read, hit) in enumerate(circular_reads.items())}
+
+    @staticmethod
+    def trim_circular_pairs(circular_pairs, unmapped_reads):
+        return {"circular_pair_" + str(i): (unmapped_reads[p[0].query][p[1].query_end:p[0].query_end] +
+                                            unmapped_reads[p[0].target][p[0].target_end:]).upper()
+                for i, p in enumerate(circular_pairs)}
+
+    def extract_unique_plasmids(self, paf_path, fasta_path, mapping_rate_threshold=0.8, max_length_difference=500,
+                                min_sequence_length=1000, vertex_order=None):
+        """extract_unique_plasmids (:121-191).  The reference numbers its vertices by list(set(names)), an order that
+        changes from process to process, so the representative it reports for a group is arbitrary; here vertex_order
+        (names) fixes it, by default the order of first appearance in the file, the query before the target of a line.
+        max_length_difference is unused, as in the reference."""
+        paf = paf_path if isinstance(paf_path, PafHits) else self.read_paf(paf_path)
+        if vertex_order is None:
+            vertex_order = [paf.name(i) for i in paf.first_seen.tolist()]
+        number = {name: i for i, name in enumerate(vertex_order)}
+        g = self.ctx.paf_groups(paf.hits)
+        first = paf.hits[g["order"][g["group_off"][:-1].astype(np.int64)].astype(np.int64)]
+        eu, ev = [], []
+        for q, t, qc, tc, ql, tl in zip(first["query"].tolist(), first["target"].tolist(), g["query_cover"].tolist(),
+                                        g["target_cover"].tolist(), first["query_len"].tolist(), first["target_len"].tolist()):
+            if q != t and (round(qc / ql, 3) > mapping_rate_threshold or round(tc / tl, 3) > mapping_rate_threshold):
+                eu.append(number[paf.name(q)])
+                ev.append(number[paf.name(t)])
+        labels = self.ctx.components(len(vertex_order), eu, ev)
+        size = np.bincount(labels, minlength=len(vertex_order))
+        seqs = dict(self.stream_sequence(fasta_path))
+        unique = {}
+        for v in np.flatnonzero(size > 1).tolist():     # a label is its component's smallest vertex: ascending, as the DFS numbers them
+            seq = seqs[vertex_order[v]]
+            if len(seq) >= min_sequence_length:
+                unique[vertex_order[v]] = seq
+        return unique

@@ -56,7 +56,7 @@ typedef struct fg_ctx fg_ctx;
 int  fg_create(fg_ctx** out, int device, int kmer_size);
 void fg_destroy(fg_ctx* ctx);
 const char* fg_strerror(int code);
-const char* fg_last_error(const fg_ctx* ctx);
+const char* fg_last_error(const fg_ctx* ctx);   /* NULL: the calling thread's last failed fg_paf_parse ("" before any) */
 int  fg_abi_version(void);
 
 /* Id range of the indexed container and of the optional query container (n_fwd forward records
@@ -1257,6 +1257,114 @@ int  fg_classify_reads_cigars(fg_ctx* ctx, int32_t buffer_count, uint32_t n_jobs
                               const uint32_t* read, const int32_t* ctg_pos /* SAM POS, 1-based */, const uint64_t* run_off,
                               const uint8_t* run_op /* ASCII */, const uint32_t* run_len, const uint64_t* read_off,
                               const uint8_t* read_seq, uint8_t want_scores, struct fg_classify_batch* out);
+
+/* The short-plasmid rescue (flye/short_plasmids/, called from flye/main.py after the contigger): the four passes its
+ * Python makes over every hit of three PAF files, as integer passes on the device.  The round(cover / length, 3) of
+ * calc_mapping_rate, the threshold comparisons, the greedy used_reads filter and the FASTA slices stay with the caller.
+ *
+ * One hit is one PAF line (flye/utils/sam_parser.py:55-90).  query and target are name ids of ONE name space: the
+ * caller numbers the distinct names of the file, queries and targets together, by rank in ascending byte order, so
+ * that equal id means equal name and ascending id is the order of sorted(target_hits) (sam_parser.py:102-120).
+ * Hits come in file order.  A RUN is a maximal stretch of consecutive hits with one query (a query that comes back
+ * later starts a new run, as in read_paf_grouped).  A GROUP is the hits of one run with one target, in file order;
+ * groups are numbered run after run and inside a run by ascending target: the order read_paf_grouped yields them in. */
+struct fg_paf_hit {
+	uint32_t query, target;
+	int32_t  query_len, query_start, query_end, target_len, target_start, target_end;
+};
+
+/* calc_mapping_rates (unmapped_reads.py:27-61) and the two rates of extract_unique_plasmids (circular_sequences.py:
+ * 146-159) before their division: per group the bases unite_mapping_segments leaves on the query side and on the
+ * target side.  Over the group's (start, end) pairs sorted by start a segment joins the last united one when start <=
+ * last.end (start == last.end + 1 does NOT join) and a united segment counts end - start + 1.  Under the precondition
+ * start <= end that is the sum over the sorted segments of max(0, end_i - max(M_i, start_i - 1)), M_i the largest end
+ * before segment i (none before the first); the order among equal starts does not matter.  The reference computes
+ * something else for end < start, which is why such input is refused.
+ * One call is one device batch.  Groups may have any size: up to FG_PAF_WAVE_MAX hits (environment, default and at
+ * most 64) a wave takes a group, up to FG_PAF_WG_MAX (default and at most 1024) a workgroup, above that the group's
+ * segments are sorted by (group, start) and a segmented running maximum runs over tiles of FG_PAF_TILE segments
+ * (64 .. 1024) with a carry from tile to tile.  The three are switches for tests; the result depends on none of them.
+ * FG_ERR_ARG, found before any device work: NULL out; NULL hits with n_hits > 0; n_hits > 2^31 - 1; a hit without
+ * 0 <= start <= end on either side.  FG_ERR_NOMEM: more than 2^30 - 1 hits (one sort) or device memory.  After an
+ * error *out is all zero and the context stays usable.  n_hits = 0 gives an empty batch (group_off = {0}). */
+struct fg_paf_group_batch {
+	uint64_t  n_hits;
+	uint32_t  n_groups;
+	uint32_t* order;          /* n_hits: hit indices, group after group, file order inside a group */
+	uint64_t* group_off;      /* n_groups + 1 offsets into order */
+	uint32_t* group_query;    /* n_groups */
+	uint32_t* group_target;   /* n_groups */
+	int64_t*  query_cover;    /* n_groups: what calc_mapping_rate sums over the (query_start, query_end) pairs */
+	int64_t*  target_cover;   /* n_groups: likewise over (target_start, target_end) */
+	void*     owner_;
+};
+int  fg_paf_groups(fg_ctx* ctx, const struct fg_paf_hit* hits, uint64_t n_hits, struct fg_paf_group_batch* out);
+void fg_release_paf_groups(struct fg_paf_group_batch* b);
+
+/* extract_circular_reads (circular_sequences.py:17-44) and the per-group search of extract_circular_pairs (:87-111).
+ * The reference's overhangs are 150 (reads) and 300 (pairs).
+ * A hit is circular when query == target, query_start < query_end < target_start < target_end, query_start <
+ * max_overhang_read and target_len - target_end + 1 < max_overhang_read.  Per query, over the whole file and not per
+ * run, the FIRST circular hit with the largest query_end - query_start + 1 is kept (the reference replaces on strict >
+ * only).  circ_query / circ_hit list the queries by the index of their first circular hit: the insertion order of the
+ * reference's dict, which trim_circular_reads turns into the names circular_read_<i>.
+ * The groups are those of fg_paf_groups on the same hits.  For a group with query != target, with
+ *   A: query_len - query_end + 1 < max_overhang_pair and target_start < max_overhang_pair
+ *   B: query_start < max_overhang_pair and target_len - target_end + 1 < max_overhang_pair
+ * pair_first is the first hit of the group in file order with A; pair_second the first hit OTHER than pair_first with
+ * B (hits before pair_first, which fail A, are tested; pair_first itself is not); pair_ok is 1 when both exist and
+ * mapping_segments_without_intersection (:70-79) holds: second.query_start < second.query_end < first.query_start <
+ * first.query_end and first.target_start < first.target_end < second.target_start < second.target_end.  -1 stands for
+ * an absent hit; a group with query == target has -1, -1, 0.  The used_reads filter over the groups in order is the
+ * caller's.  Overhang sums are formed in 64 bits.
+ * Errors as fg_paf_groups.  n_hits = 0 gives an empty batch. */
+struct fg_paf_circular_batch {
+	uint64_t  n_hits;
+	uint32_t  n_circular;
+	uint32_t* circ_query;     /* n_circular name ids */
+	uint32_t* circ_hit;       /* n_circular hit indices */
+	uint32_t  n_groups;
+	uint32_t* group_query;    /* n_groups */
+	uint32_t* group_target;   /* n_groups */
+	int32_t*  pair_first;     /* n_groups: hit index or -1 */
+	int32_t*  pair_second;    /* n_groups: hit index or -1 */
+	uint8_t*  pair_ok;        /* n_groups */
+	void*     owner_;
+};
+int  fg_paf_circular(fg_ctx* ctx, const struct fg_paf_hit* hits, uint64_t n_hits, int32_t max_overhang_read,
+                     int32_t max_overhang_pair, struct fg_paf_circular_batch* out);
+void fg_release_paf_circular(struct fg_paf_circular_batch* b);
+
+/* Connected components of an undirected graph: labels[v] (n_vertices entries, the caller's array) = the smallest
+ * vertex index of v's component.  Self loops, duplicate edges, n_edges = 0 and isolated vertices are valid input.
+ * find_connected_components (flye/short_plasmids/utils.py:7-29) follows from the labels: its DFS numbers the
+ * components by ascending smallest member, and a group lists its members ascending, so group[0] is the label.
+ * On the device: every edge hooks the larger of its two labels under the smaller (an integer atomic minimum), every
+ * vertex then jumps to the root of its label chain; the two repeat until a pass over the edges finds both ends of
+ * every edge under one label (the host reads one flag per round).  Labels only decrease and a label never exceeds its
+ * vertex, so the rounds end and the result is the same however the atomics interleave.
+ * FG_ERR_ARG, found before any device work: NULL labels with n_vertices > 0; NULL edge_u or edge_v with n_edges > 0; a
+ * vertex index >= n_vertices.  The context stays usable. */
+int  fg_components(fg_ctx* ctx, uint32_t n_vertices, uint64_t n_edges, const uint32_t* edge_u, const uint32_t* edge_v,
+                   uint32_t* labels);
+
+/* The tokens of PafHit.__init__ (sam_parser.py:61-72) for a whole PAF buffer; host only, no context.  Lines end at
+ * '\n' (a last line need not); the fields of a line are split at runs of the bytes bytes.split() treats as space
+ * (' ', '\t', '\n', '\r', '\v', '\f'); fields 0 and 5 are the names, returned as offset and length into text; fields
+ * 1-3 and 6-8 are the integers; further fields are ignored.
+ * FG_ERR_ARG for NULL out, NULL text with n_bytes > 0, a line with fewer than 9 fields (an empty line included), an
+ * integer field that is not an optionally signed decimal number, and a value outside int32.  fg_last_error(NULL) then
+ * holds the text, with the 1-based line number, of the calling thread's last failed fg_paf_parse. */
+struct fg_paf_text {
+	uint64_t  n_hits;
+	uint64_t* query_name_off;  uint32_t* query_name_len;
+	uint64_t* target_name_off; uint32_t* target_name_len;
+	int32_t*  query_len;  int32_t* query_start;  int32_t* query_end;
+	int32_t*  target_len; int32_t* target_start; int32_t* target_end;
+	void*     owner_;
+};
+int  fg_paf_parse(const char* text, uint64_t n_bytes, struct fg_paf_text* out);
+void fg_release_paf_text(struct fg_paf_text* b);
 
 #ifdef __cplusplus
 }
