@@ -546,6 +546,26 @@ int fg_debug_sort_pairs(fg_ctx* c, uint64_t* keys, uint32_t* vals, const uint64_
 	});
 }
 
+int fg_debug_sort_pairs64(fg_ctx* c, uint64_t* keys, uint32_t* vals, const uint64_t* seg_off, uint32_t n_seg, int cur_bits)
+{
+	if (!c || !seg_off || (seg_off[n_seg] && (!keys || !vals)) || cur_bits < 0 || cur_bits > 32) return FG_ERR_ARG;
+	return guarded(c, [&]()
+	{
+		HIP_CHECK(hipSetDevice(c->device));
+		fgDebugSortPairs(c, keys, vals, seg_off, n_seg, cur_bits);
+	});
+}
+
+int fg_debug_sort_packed(fg_ctx* c, uint64_t* recs, const uint64_t* seg_off, uint32_t n_seg, int cur_bits)
+{
+	if (!c || !seg_off || (seg_off[n_seg] && !recs) || cur_bits < 0 || cur_bits + FG_PK_VALBITS >= 64) return FG_ERR_ARG;
+	return guarded(c, [&]()
+	{
+		HIP_CHECK(hipSetDevice(c->device));
+		fgDebugSortPacked(c, recs, seg_off, n_seg, cur_bits);
+	});
+}
+
 int fg_debug_sort_pairs32(fg_ctx* c, uint32_t* keys, uint32_t* vals, const uint64_t* seg_off, uint32_t n_seg, int cur_bits,
 						  int rec_bits, const uint32_t* tie_free, uint64_t* radix_segments, uint64_t* radix_hits)
 {

@@ -848,7 +848,8 @@ void fgPolishBubbles(fg_ctx* c, const int64_t* score36, const uint8_t* cand, con
 					 const uint64_t* branchOff, const uint64_t* bubbleBranchOff, u32 nBubbles, bool fixDinucleotides, bool wantSteps,
 					 std::vector<std::string>& outCand, std::vector<uint32_t>& nSteps, std::vector<uint8_t>& status,
 					 std::vector<std::vector<std::pair<std::string, int64_t>>>& steps);
-void fgDebugSortPairs(fg_ctx* c, u64* keys, u32* vals, const u64* segOff, u32 nSeg);
+void fgDebugSortPairs(fg_ctx* c, u64* keys, u32* vals, const u64* segOff, u32 nSeg, int curBits = 0);
+void fgDebugSortPacked(fg_ctx* c, u64* recs, const u64* segOff, u32 nSeg, int curBits);
 void fgDebugSortPairs32(fg_ctx* c, u32* keys, u32* vals, const u64* segOff, u32 nSeg, int curBits, int recBits,
 						const u32* tieFree, u64* radixSegments, u64* radixHits);
 void fgDebugSortPairs32v16(fg_ctx* c, u32* keys, u16* vals, const u64* segOff, u32 nSeg, int curBits, int recBits,

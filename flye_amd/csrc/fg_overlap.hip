@@ -1802,7 +1802,9 @@ void fgSortSegments(fg_ctx* c, const u64* dSegOff, u32 nSeg, u64* dKeys, u32* dV
 	if (nSeg && n) sortSegments<u64>(c, dSegOff, nSeg, dKeys, dVals, n);
 }
 
-void fgDebugSortPairs(fg_ctx* c, u64* keys, u32* vals, const u64* segOff, u32 nSeg)
+// curBits = 0: arbitrary keys (fg_debug_sort_pairs); else keys extId << 32 | curPos with curPos < 2^curBits, the form and
+// the curBits deviceSub passes in key mode 2 (fg_debug_sort_pairs64)
+void fgDebugSortPairs(fg_ctx* c, u64* keys, u32* vals, const u64* segOff, u32 nSeg, int curBits)
 {
 	hipStream_t s = c->stream;
 	const u64 n = segOff[nSeg];
@@ -1811,9 +1813,23 @@ void fgDebugSortPairs(fg_ctx* c, u64* keys, u32* vals, const u64* segOff, u32 nS
 	HIP_CHECK(hipMemcpyAsync(dK.p, keys, n * 8, hipMemcpyHostToDevice, s));
 	HIP_CHECK(hipMemcpyAsync(dV.p, vals, n * 4, hipMemcpyHostToDevice, s));
 	HIP_CHECK(hipMemcpyAsync(dOff.p, segOff, (nSeg + 1) * 8ULL, hipMemcpyHostToDevice, s));
-	if (nSeg) sortSegments<u64>(c, dOff.p, nSeg, dK.p, dV.p, n);
+	if (nSeg) sortSegments<u64>(c, dOff.p, nSeg, dK.p, dV.p, n, curBits);
 	HIP_CHECK(hipMemcpyAsync(keys, dK.p, n * 8, hipMemcpyDeviceToHost, s));
 	HIP_CHECK(hipMemcpyAsync(vals, dV.p, n * 4, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(hipStreamSynchronize(s));
+}
+
+// fg_debug_sort_packed: the packed records of key mode 1, sorted as deviceSub sorts them: no value array, no flags
+void fgDebugSortPacked(fg_ctx* c, u64* recs, const u64* segOff, u32 nSeg, int curBits)
+{
+	hipStream_t s = c->stream;
+	const u64 n = segOff[nSeg];
+	DevBuf<u64> dK, dOff;
+	dK.alloc(n + 1); dOff.alloc(nSeg + 1);
+	HIP_CHECK(hipMemcpyAsync(dK.p, recs, n * 8, hipMemcpyHostToDevice, s));
+	HIP_CHECK(hipMemcpyAsync(dOff.p, segOff, (nSeg + 1) * 8ULL, hipMemcpyHostToDevice, s));
+	if (nSeg && n) sortSegments<PK>(c, dOff.p, nSeg, (PK*)dK.p, (u32*)nullptr, n, curBits);
+	HIP_CHECK(hipMemcpyAsync(recs, dK.p, n * 8, hipMemcpyDeviceToHost, s));
 	HIP_CHECK(hipStreamSynchronize(s));
 }
 

@@ -65,7 +65,8 @@ ABI_SYMBOLS = ["fg_abi_version", "fg_create", "fg_destroy", "fg_strerror", "fg_l
                "fg_index_kmer_hist", "fg_index_count_slice", "fg_index_batch_freq", "fg_index_batch_select",
                "fg_index_selection_done", "fg_index_gather_begin", "fg_index_gather_end", "fg_memory_stats",
                "fg_import_index", "fg_index_device_arrays", "fg_clear_index", "fg_export_index", "fg_overlaps", "fg_release_batch",
-               "fg_kernel_times", "fg_debug_sort_pairs", "fg_debug_edit_distances", "fg_align_cigar_ksw", "fg_release_cigars",
+               "fg_kernel_times", "fg_debug_sort_pairs", "fg_debug_sort_pairs64", "fg_debug_sort_packed",
+               "fg_debug_edit_distances", "fg_align_cigar_ksw", "fg_release_cigars",
                "fg_align_ranges", "fg_trim_ranges", "fg_release_trims", "fg_edit_ranges", "fg_chain_divergence",
                "fg_chain_alignments", "fg_release_chains",
                "fg_read_coverage", "fg_release_coverage", "fg_coverage_windows", "fg_coverage_verdict",
@@ -399,6 +400,8 @@ def load_library():
                                             C.c_uint8, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(OverlapBatch)]
         L.fg_kernel_times.argtypes = [C.c_void_p, C.POINTER(KernelTime), C.c_int]
         L.fg_debug_sort_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+        L.fg_debug_sort_pairs64.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int]
+        L.fg_debug_sort_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int]
         L.fg_debug_sort_pairs32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int,
                                             C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.fg_debug_sort_pairs32_val16.argtypes = L.fg_debug_sort_pairs32.argtypes
@@ -937,6 +940,32 @@ class Context:
         self._check(self.L.fg_debug_sort_pairs(self.h, k.ctypes.data, v.ctypes.data, off.ctypes.data,
                                                len(off) - 1))
         return k, v
+
+    def debug_sort_pairs64(self, keys, vals, seg_off, cur_bits):
+        """The hit sort in its 64-bit key + value form: keys ``ext_id << 32 | cur_pos`` with ``cur_pos < 2^cur_bits``,
+        ``vals`` (uint32, one per key) travel with them.  Returns (sorted keys, their values)."""
+        k = np.ascontiguousarray(keys, np.uint64).copy()
+        v = np.ascontiguousarray(vals, np.uint32).copy()
+        off = np.ascontiguousarray(seg_off, np.uint64)
+        if len(v) != len(k) or len(k) != int(off[-1]):
+            raise ValueError("one value per key, seg_off ending at their number")
+        self._check(self.L.fg_debug_sort_pairs64(self.h, k.ctypes.data, v.ctypes.data, off.ctypes.data, len(off) - 1,
+                                                 int(cur_bits)))
+        return k, v
+
+    def debug_sort_packed(self, keys, vals, seg_off, cur_bits):
+        """The hit sort on packed records ``key << 24 | val`` (key = ``record << cur_bits | cur_pos``, val below 2^24),
+        which are ordered on the key alone.  Returns (sorted keys, their values), unpacked."""
+        k = np.ascontiguousarray(keys, np.uint64)
+        v = np.ascontiguousarray(vals, np.uint64)
+        off = np.ascontiguousarray(seg_off, np.uint64)
+        if len(v) != len(k) or len(k) != int(off[-1]):
+            raise ValueError("one value per key, seg_off ending at their number")
+        if len(k) and (int(k.max()) >> 40 or int(v.max()) >> 24):
+            raise ValueError("a key of more than 40 bits or a value of more than 24")
+        rec = np.ascontiguousarray((k << np.uint64(24)) | v)
+        self._check(self.L.fg_debug_sort_packed(self.h, rec.ctypes.data, off.ctypes.data, len(off) - 1, int(cur_bits)))
+        return rec >> np.uint64(24), (rec & np.uint64(0xFFFFFF)).astype(np.uint32)
 
     def debug_sort_pairs32(self, keys, seg_off, cur_bits, rec_bits, tie_free=None):
         """The hit sort in its 32-bit key form (``record << cur_bits | cur_pos``) with per-segment tie-free flags

@@ -429,6 +429,17 @@ int fg_kernel_times(fg_ctx* ctx, struct fg_kernel_time* out, int max_entries);
 int fg_debug_sort_pairs(fg_ctx* ctx, uint64_t* keys, uint32_t* vals,
                         const uint64_t* seg_off, uint32_t n_seg);
 
+/* Test hook: fg_debug_sort_pairs in the overlap stage's 64-bit key + value form (sequences of 2^24 bases and more, or
+ * FG_PACKED_KEYS=0): key = ext_id << 32 | cur_pos with cur_pos < 2^cur_bits, and the sort is told cur_bits (0..32) as
+ * the stage tells it.  cur_bits = 0 is fg_debug_sort_pairs. */
+int fg_debug_sort_pairs64(fg_ctx* ctx, uint64_t* keys, uint32_t* vals, const uint64_t* seg_off, uint32_t n_seg,
+                          int cur_bits);
+
+/* Test hook: the same sort on the overlap stage's packed records, one 64-bit word per hit: record << (cur_bits + 24) |
+ * cur_pos << 24 | ext_pos, ordered on word >> 24 alone (the low 24 bits travel as the value); no value array, no
+ * tie-free flags, as the stage calls it.  cur_bits >= 0 and cur_bits + 24 < 64. */
+int fg_debug_sort_packed(fg_ctx* ctx, uint64_t* recs, const uint64_t* seg_off, uint32_t n_seg, int cur_bits);
+
 /* Test hook: the same sort in the overlap stage's 32-bit key form, key = record << cur_bits | cur_pos with rec_bits
  * record bits (cur_bits + rec_bits <= 32), every segment given by ascending cur_pos as the seed expansion emits it.
  * tie_free (n_seg words, or NULL = none): non-zero promises that the segment holds no two equal keys; such segments

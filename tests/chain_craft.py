@@ -399,11 +399,40 @@ def key_mode_case(name, n_reads):
     return c
 
 
-CASE_NAMES = ["sizes_s", "sizes_m", "sizes_l", "prefilter", "dp", "tandem", "ties", "key32", "key33"]
+KEY33_HIGH_CUR_BITS = 20    # a 530 kb query: 20 position bits beside the 13 record bits of 2049 reads
+
+
+def key33_high_case(name, first_id=0):
+    """The key33 construction with the target records at the top of the record range: 2046 short filler reads first,
+    then the 530 kb query (read 2046; 20 position bits, 13 record bits: 33 key bits) and its two targets, reads 2047
+    and 2048, the second stored reverse-complemented.  The hit keys ``record << 20 | cur`` of the one query then lie
+    below 2^32 on record 4094 and at or above it on the odd record 4097: its segment straddles 2^32.  ``first_id``:
+    the packed form keys on ext_id - first_id, the 64-bit key + value form on ext_id itself."""
+    c = Case(name, 79, first_id=first_id)
+    L = 530_000
+    while len(c.seqs) < 2046:
+        c.add_read(c.rand(60))
+    q = c.add_read(c.rand(L))
+    pair(c, 1300, spread(100, 1250), left_q=L - 3000, q_read=q, t_len=1700)
+    pair(c, 1300, spread(600, 1250), left_q=L - 1500, q_read=q, t_len=1800, rc=True)
+    assert len(c.seqs) == 2049 and sorted(t for _, t in c.groups) == [2 * 2047, 2 * 2048 + 1]
+    return c
+
+
+def hit_key_range(case, cur_bits):
+    """(smallest, largest) ``record << cur_bits | cur`` over the declared hits of every query"""
+    keys = [(t << cur_bits) | cur for (_, t), hits in case.groups.items() for cur, _ in hits]
+    return min(keys), max(keys)
+
+
+CASE_NAMES = ["sizes_s", "sizes_m", "sizes_l", "prefilter", "dp", "tandem", "ties", "key32", "key33", "key33_high",
+              "key33_high_id"]
 
 
 def make_case(name):
     return {"sizes_s": lambda: sizes_case("sizes_s", 11), "sizes_m": lambda: sizes_case("sizes_m", 13),
             "sizes_l": lambda: sizes_case("sizes_l", 17), "prefilter": prefilter_case, "dp": dp_case,
             "tandem": tandem_case, "ties": ties_case, "key32": lambda: key_mode_case("key32", 2048),
-            "key33": lambda: key_mode_case("key33", 2049)}[name]()
+            "key33": lambda: key_mode_case("key33", 2049),
+            "key33_high": lambda: key33_high_case("key33_high"),
+            "key33_high_id": lambda: key33_high_case("key33_high_id", first_id=1000)}[name]()

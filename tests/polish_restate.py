@@ -71,12 +71,19 @@ def load_matrix(path):
 
 # ---- std::sort of libstdc++ as a permutation ------------------------------------------------------------------------
 
-def std_sort_perm(keys):
+def std_sort_perm(keys, trace=None, leaf=0):
     """the order std::sort(first, last, key(a) < key(b)) of libstdc++ leaves n elements in: introsort down to pieces of
     16 with the median of three moved to the front and an unguarded partition, heap sort where the depth budget
-    2 * floor(log2 n) runs out, then one insertion pass"""
+    2 * floor(log2 n) runs out, then one insertion pass.
+
+    ``trace(first, last, depth, heap)`` is called for every range the introsort loop comes to hold, at the moment it gets
+    it (the whole input, then both sides of every partition), with the depth budget left; ``heap`` says that the range
+    is heap sorted because the budget ran out (more than 16 elements at depth 0).  ``leaf`` > 16: ranges of at most
+    ``leaf`` elements are reported and then left as they are, and there is no insertion pass -- the partitions of the
+    larger ranges alone, which is what a caller wants who asks where the pieces of that size come from."""
     n = len(keys)
     a = list(range(n))
+    stop = max(16, leaf)
 
     def less(x, y):
         return keys[x] < keys[y]
@@ -136,7 +143,11 @@ def std_sort_perm(keys):
             lo += 1
 
     def loop(first, last, depth):
-        while last - first > 16:
+        while True:
+            if trace:
+                trace(first, last, depth, last - first > stop and depth == 0)
+            if last - first <= stop:
+                return
             if depth == 0:
                 heap_sort(first, last)
                 return
@@ -163,6 +174,8 @@ def std_sort_perm(keys):
 
     if n:
         loop(0, n, 2 * (n.bit_length() - 1))
+        if leaf > 16:
+            return a
         if n > 16:
             insertion(0, 16)
             for i in range(16, n):

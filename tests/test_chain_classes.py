@@ -24,6 +24,12 @@ SETTINGS = [
     {"FG_CHAIN_STREAMS": "1", "FG_CHAIN_FUSED": "0"},
     {"FG_FORCE_KEY64": "1"},
     {"FG_FORCE_KEY64": "1", "FG_PACKED_KEYS": "0"},
+    # the 64-bit hit forms where a case needs them (key33, key33_high: hit keys above 2^32 in the latter): the packed
+    # sort without its narrowing, the 64-bit key + value form, and both read through the per-query listing kernels
+    {"FG_NARROW_MAX": "0"},
+    {"FG_PACKED_KEYS": "0"},
+    {"FG_GROUP_FLAT": "0"},
+    {"FG_PACKED_KEYS": "0", "FG_GROUP_FLAT": "0"},
 ]
 SWITCHES = sorted({k for s in SETTINGS for k in s})
 CHAIN_KERNELS = ("k_chain_small", "k_group_prep", "k_chain_dp", "k_chain_finish<lds256>",

@@ -54,6 +54,22 @@ def test_oracle_counts_the_declared_groups(built, case):
         assert len(res.recs) > 0
 
 
+@pytest.mark.parametrize("name", ["key33_high", "key33_high_id"])
+def test_key33_high_straddles_2_to_the_32(name):
+    """from the declared hits: the one query's keys record << 20 | cur lie on both sides of 2^32, an odd record among
+    the high ones, while key33's stay far below"""
+    c = cc.make_case(name)
+    bits = cc.KEY33_HIGH_CUR_BITS
+    assert len(c.queries) == 1 and (1 << (bits - 1)) < c.rec_len(c.queries[0]) <= (1 << bits)
+    assert len(c.seqs) == 2049                                       # 13 record bits: 33 with the position bits
+    lo, hi = cc.hit_key_range(c, bits)
+    assert lo < (1 << 32) <= hi
+    by_side = {t: (t << bits) >= (1 << 32) for _, t in c.groups}
+    assert sorted(by_side.values()) == [False, True] and any(t & 1 for t, high in by_side.items() if high)
+    assert c.first_id == (1000 if name.endswith("_id") else 0)
+    assert cc.hit_key_range(cc.make_case("key33"), bits)[1] < 1 << 24
+
+
 def test_cases_reach_every_boundary():
     """The size classes and boundaries the device tests rely on are among the declared groups."""
     passing = {}

@@ -274,10 +274,20 @@ def test_group_overlaps_repeat_stage_flags_rc_ids_first_id(built, monkeypatch, w
     _same(g.overlaps(p_cut, q, forceLocal=True), full_cut.getSeqOverlapsBatch(q, forceLocal=True))
 
 
+# the hit form the members' receivers write: 32-bit keys at this size, and with the switches the packed records and the
+# 64-bit keys beside values of read sets that need more than 32 key bits
+KEY_FORMS = {"key32": {}, "key64": {"FG_FORCE_KEY64": "1"}, "key64_unpacked": {"FG_FORCE_KEY64": "1", "FG_PACKED_KEYS": "0"}}
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("world", [2, 3])
-def test_group_overlaps_separate_query_container(built, monkeypatch, world):
-    """queries in a container of their own (fg_group_set_queries: the ReadAligner shape)"""
+@pytest.mark.parametrize("world,key_form", [pytest.param(2, "key32", id="2"), pytest.param(3, "key32", id="3"),
+                                            pytest.param(2, "key64", id="2-key64"),
+                                            pytest.param(2, "key64_unpacked", id="2-key64_unpacked")])
+def test_group_overlaps_separate_query_container(built, monkeypatch, world, key_form):
+    """queries in a container of their own (fg_group_set_queries: the ReadAligner shape); with two members also in the
+    64-bit hit forms, where the group and the full index must both give what the full index gives in the 32-bit form"""
+    for sw in ("FG_FORCE_KEY64", "FG_PACKED_KEYS"):
+        monkeypatch.delenv(sw, raising=False)
     cfg, rs, qrs, ctx, vi = _single("raw", "pb_raw", 0, 12, 6)
     g = _group(world, "raw", "pb_raw", 0, 12, 6)
     q_first = 2 * rs.n
@@ -287,7 +297,11 @@ def test_group_overlaps_separate_query_container(built, monkeypatch, world):
     p = _params(cfg, only_max_ext=0)
     full = _full_detector(ctx, vi, cfg, p)
     assert _has_tied_keys(full, q)
-    _same(g.overlaps(p, q), full.getSeqOverlapsBatch(q))
+    want = full.getSeqOverlapsBatch(q)
+    for sw, value in KEY_FORMS[key_form].items():
+        monkeypatch.setenv(sw, value)
+    _same(full.getSeqOverlapsBatch(q), want)
+    _same(g.overlaps(p, q), want)
     from flye_amd import gpu
     with pytest.raises(gpu.FlyeGpuError) as e:
         g.overlaps(p, np.array([0], np.uint32))            # an id of the indexed container is no query id here

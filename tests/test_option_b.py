@@ -189,13 +189,36 @@ def _recv_form(monkeypatch, two_pass):
         monkeypatch.delenv("FG_RECV_TWO_PASS", raising=False)
 
 
+# The hit form the receiver writes (recvFill / k_recv_place): 32-bit keys on read sets of this size, and with the
+# switches the two forms a read set too large for 32 key bits takes -- packed records, 64-bit keys beside values.
+KEY_FORMS = {"key32": {}, "key64": {"FG_FORCE_KEY64": "1"}, "key64_unpacked": {"FG_FORCE_KEY64": "1", "FG_PACKED_KEYS": "0"}}
+
+
+def _key_form(monkeypatch, form):
+    for sw in ("FG_FORCE_KEY64", "FG_PACKED_KEYS"):
+        monkeypatch.delenv(sw, raising=False)
+    for sw, value in KEY_FORMS[form].items():
+        monkeypatch.setenv(sw, value)
+
+
+def _full_index_params():
+    out = []
+    for preset, kind in (("raw", "pb_raw"), ("hifi", "hifi")):
+        for world, two_pass in ((2, False), (3, False), (2, True), (3, True)):
+            for form in KEY_FORMS:
+                if form != "key32" and not (preset == "raw" and world == 2):
+                    continue
+                name = f"{preset}-{kind}-{world}" + ("-two_pass" if two_pass else "") + ("" if form == "key32" else "-" + form)
+                out.append(pytest.param(preset, kind, world, two_pass, form, id=name))
+    return out
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("world,two_pass", [pytest.param(2, False, id="2"), pytest.param(3, False, id="3"),
-                                            pytest.param(2, True, id="2-two_pass"), pytest.param(3, True, id="3-two_pass")])
-@pytest.mark.parametrize("preset,kind", [("raw", "pb_raw"), ("hifi", "hifi")])
-def test_option_b_equals_full_index(built, monkeypatch, preset, kind, world, two_pass):
+@pytest.mark.parametrize("preset,kind,world,two_pass,key_form", _full_index_params())
+def test_option_b_equals_full_index(built, monkeypatch, preset, kind, world, two_pass, key_form):
     from flye_amd import config
     _recv_form(monkeypatch, two_pass)
+    _key_form(monkeypatch, "key32")
     cfg = config.preset(preset)
     rs = _reads(kind)
     ctx, vi = _index(rs, cfg)
@@ -206,7 +229,11 @@ def test_option_b_equals_full_index(built, monkeypatch, preset, kind, world, two
         v.keep_targets(world, r)
         shards.append(_detector(c, v, cfg))
     q = np.arange(0, 2 * rs.n, 2, dtype=np.uint32)
+    plain = full.getSeqOverlapsBatch(q) if key_form != "key32" else None
+    _key_form(monkeypatch, key_form)
     probes = _run_option_b(full, shards, q, (q >> 1) % world, np.random.default_rng(world))
+    if plain is not None:       # and the form changes nothing
+        _same(full.getSeqOverlapsBatch(q), plain)
     # the shards' hits are exactly the full index's, split by target owner
     fc, fh = _shard_hits(full, q)
     assert np.array_equal(sum(c for c, _ in probes), fc)
@@ -219,12 +246,16 @@ def test_option_b_equals_full_index(built, monkeypatch, preset, kind, world, two
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("two_pass", TWO_PASS)
-def test_option_b_repeat_stage_flags_rc_queries_first_id(built, monkeypatch, two_pass):
+@pytest.mark.parametrize("two_pass,key_form",
+                         [pytest.param(tp, form, id=tid + ("" if form == "key32" else "-" + form))
+                          for tp, tid in ((False, "auto"), (True, "two_pass")) for form in KEY_FORMS])
+def test_option_b_repeat_stage_flags_rc_queries_first_id(built, monkeypatch, two_pass, key_form):
     """only_max_ext = 0, keep_alignment, partition_bad_mappings; max_overlaps > 0; reverse-complement query ids;
-    first_seq_id != 0"""
+    first_seq_id != 0; in every hit form (the match arrays of the 64-bit forms come from what k_recv_place<PK> and
+    k_recv_place<u64> wrote)"""
     from flye_amd import config
     _recv_form(monkeypatch, two_pass)
+    _key_form(monkeypatch, "key32")
     cfg = config.preset("raw")
     rs = _reads("pb_raw", seed=77)
     first, world = 10, 2
@@ -241,10 +272,17 @@ def test_option_b_repeat_stage_flags_rc_queries_first_id(built, monkeypatch, two
     q = (first + np.arange(1, 2 * rs.n, 2)).astype(np.uint32)          # reverse-complement strands
     owner = ((q - first) >> 1) % world
     rng = np.random.default_rng(3)
+    plain = plain_cut = None
+    if key_form != "key32":
+        plain, plain_cut = full.getSeqOverlapsBatch(q), full_cut.getSeqOverlapsBatch(q, maxOverlaps=3)
+    _key_form(monkeypatch, key_form)
     _run_option_b(full, shards, q, owner, rng)
     got = full.getSeqOverlapsBatch(q)
     assert got.needs_trim is not None and len(got.matches) > 0
     _run_option_b(full_cut, shards_cut, q, owner, rng, maxOverlaps=3)
+    if plain is not None:       # and the form changes nothing
+        _same(got, plain)
+        _same(full_cut.getSeqOverlapsBatch(q, maxOverlaps=3), plain_cut)
 
 
 @pytest.mark.gpu
