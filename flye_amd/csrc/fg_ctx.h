@@ -469,6 +469,8 @@ struct fg_ctx {
 	DevBuf<char> dPt[36];
 	// fg_paf_groups / fg_paf_circular / fg_components (fg_plasmid.hip): the buffers of one call, handed out in call order
 	DevBuf<char> dPaf[32];
+	// fg_sam_parse (fg_samtext.hip): a sub-batch's text, its per-byte and per-line tables and its results, in call order
+	DevBuf<char> dSam[16];
 	PinnedBuf<char> hPrim;
 	PinnedBuf<u64> hOff;
 	PinnedBuf<u64> hScalar;		// staging of the counts the host reads between kernels (pinned: no bounce buffer)

@@ -1,6 +1,6 @@
 // What the stage calls of the C ABI share on the host (fg_uniform_alignments, fg_contig_consensus[_cigars],
 // fg_make_bubbles[_cigars], fg_expand_cigars, fg_divergence_profile[_cigars], fg_confirm_positions,
-// fg_classify_reads[_cigars], fg_paf_groups, fg_paf_circular):
+// fg_classify_reads[_cigars], fg_paf_groups, fg_paf_circular, fg_sam_parse):
 //   host part (no HIP: fg_error.h and include/flye_gpu.h alone; tests/stage_host_check.cpp builds it with g++)
 //     stageEnvU64 / stageEnvCap             the u64 switches of the environment
 //     stageOffsets .. stageColumnWalk       the argument checks; each takes the call's name, so a message reads the same
@@ -194,7 +194,7 @@ inline void stageRelease(Out* b)
 	memset(b, 0, sizeof(*b));
 }
 
-// One of the context's per-stage buffer arrays (fg_ctx: dBub, dCc, dCig, dDv, dPt, dPaf), handed out in order from slot
+// One of the context's per-stage buffer arrays (fg_ctx: dBub, dCc, dCig, dDv, dPt, dPaf, dSam), handed out in order from slot
 // `start`; a buffer keeps its size between calls and only grows.
 struct DevPool {
 	DevBuf<char>* bufs;

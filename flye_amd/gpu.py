@@ -21,7 +21,8 @@ like calls into the reference:
 * ``SamAlignments(ctx, sam_path, contigs, max_coverage, use_secondary).chunks() / by_contig()``
   (flye/utils/sam_parser.py:123-404, SynchronizedSamReader: get_chunk on fg_expand_cigars); with ``want_cols=False`` it
   keeps runs and SEQ in place of the gapped strings, for ``ContigConsensus.consensus_sam`` and ``BubbleMaker.make_sam`` /
-  ``polish_sam`` (fg_contig_consensus_cigars / fg_make_bubbles_cigars: the columns are made and stay on the device)
+  ``polish_sam`` (fg_contig_consensus_cigars / fg_make_bubbles_cigars: the columns are made and stay on the device); with
+  ``device_text=True`` the file's text is cut into records on the device as well (``Context.sam_parse``, fg_sam_parse)
 * ``DivergenceFinder(ctx).find_divergence(alignment_path, contigs_path, contigs_info, frequency_path, positions_path,
   div_sum_path, sub_thresh, del_thresh, ins_thresh)`` / ``profile``  (flye/trestle/divergence.py:55-232, on
   fg_divergence_profile); ``find_divergence_sam`` / ``profile_sam`` on fg_divergence_profile_cigars
@@ -78,7 +79,7 @@ ABI_SYMBOLS = ["fg_abi_version", "fg_create", "fg_destroy", "fg_strerror", "fg_l
                "fg_confirm_positions", "fg_release_confirm", "fg_classify_reads", "fg_release_classify",
                "fg_divergence_profile_cigars", "fg_classify_reads_cigars",
                "fg_paf_groups", "fg_release_paf_groups", "fg_paf_circular", "fg_release_paf_circular", "fg_components",
-               "fg_paf_parse", "fg_release_paf_text",
+               "fg_paf_parse", "fg_release_paf_text", "fg_sam_parse", "fg_release_sam_text",
                "fg_index_keep_targets", "fg_index_shard", "fg_probe_hits", "fg_overlaps_from_hits",
                "fg_index_piece_split", "fg_index_scatter_begin", "fg_index_scatter_end", "fg_debug_probe_skip_check",
                "fg_group_create", "fg_group_destroy", "fg_group_size", "fg_group_member", "fg_group_last_error",
@@ -315,6 +316,17 @@ class PafText(C.Structure):
                 ("owner_", C.c_void_p)]
 
 
+class SamText(C.Structure):
+    _fields_ = ([("n_lines", C.c_uint64), ("n_records", C.c_uint64), ("n_chunks", C.c_uint64), ("n_runs", C.c_uint64),
+                 ("chunk_off", C.POINTER(C.c_uint64)), ("line_no", C.POINTER(C.c_uint64)), ("line_off", C.POINTER(C.c_uint64)),
+                 ("line_len", C.POINTER(C.c_uint32)), ("status", C.POINTER(C.c_uint8))] +
+                [(k + s, C.POINTER(t)) for k in ("tab_rname", "qname", "rname", "cigar", "seq")
+                 for s, t in (("_off", C.c_uint64), ("_len", C.c_uint32))] +
+                [("flag", C.POINTER(C.c_int32)), ("pos", C.POINTER(C.c_int32)), ("qry_start", C.POINTER(C.c_int64)),
+                 ("qry_end", C.POINTER(C.c_int64)), ("run_off", C.POINTER(C.c_uint64)), ("run_op", C.POINTER(C.c_uint8)),
+                 ("run_len", C.POINTER(C.c_uint32)), ("owner_", C.c_void_p)])
+
+
 class BridgeStats(C.Structure):
     _fields_ = [("device_calls", C.c_uint64), ("reads_computed", C.c_uint64), ("requests", C.c_uint64),
                 ("cache_hits", C.c_uint64), ("cached_overlaps", C.c_uint64), ("reads_ahead", C.c_uint64),
@@ -511,6 +523,8 @@ def load_library():
         L.fg_components.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.fg_paf_parse.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(PafText)]
         L.fg_release_paf_text.argtypes = [C.POINTER(PafText)]
+        L.fg_sam_parse.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(SamText)]
+        L.fg_release_sam_text.argtypes = [C.POINTER(SamText)]
         # include/flye_gpu_bridge.h
         L.fgb_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(DetectorParams), C.c_uint32, C.c_uint32]
         L.fgb_destroy.argtypes = [C.c_void_p]
@@ -859,6 +873,31 @@ def paf_parse(text):
     out = PafHits(text, hits, [bytes(x) for x in names.tolist()], np.argsort(pos, kind="stable").astype(np.uint32))
     out.parse_seconds, out.id_seconds = t1 - t0, time.perf_counter() - t1        # the tokeniser; the copies and the ids
     return out
+
+
+class SamTextResult:
+    """fg_sam_text copied out of its arena, for the SAM buffer `text` (the bytes the call saw): the counts n_lines,
+    n_records, n_chunks, n_runs and one numpy array per field of the struct, under its name.  The status bits are
+    FEW_TOKENS (fewer than 11 tokens: the token fields are 0), BAD_FLAG / BAD_POS (int() of the token bytes is the
+    caller's), NO_SEQ (SEQ is '*') and RUN_OVERFLOW (a CIGAR length beyond uint32)."""
+    FEW_TOKENS, BAD_FLAG, BAD_POS, NO_SEQ, RUN_OVERFLOW = 1, 2, 4, 8, 16
+    PER_RECORD = ("line_no", "line_off", "line_len", "status", "tab_rname_off", "tab_rname_len", "qname_off", "qname_len", "rname_off",
+                  "rname_len", "cigar_off", "cigar_len", "seq_off", "seq_len", "flag", "pos", "qry_start", "qry_end")
+    ARRAYS = ("chunk_off",) + PER_RECORD + ("run_off", "run_op", "run_len")
+
+    def __init__(self, text, **fields):
+        self.text = text
+        self.__dict__.update(fields)
+
+    def token(self, i, which):
+        """the bytes of record i's qname, rname, cigar, seq, tab_rname or line"""
+        a = int(getattr(self, which + "_off")[i])
+        return bytes(self.text[a:a + int(getattr(self, which + "_len")[i])])
+
+    def runs(self, i):
+        """(ops, lens) of record i, views"""
+        a, b = int(self.run_off[i]), int(self.run_off[i + 1])
+        return self.run_op[a:b], self.run_len[a:b]
 
 
 class PolishResult:
@@ -1803,6 +1842,28 @@ class Context:
         self._check(self.L.fg_components(self.h, int(n_vertices), len(u), u.ctypes.data if len(u) else None,
                                          v.ctypes.data if len(v) else None, labels.ctypes.data if len(labels) else None))
         return labels
+
+    def sam_parse(self, data, offset=0, n_bytes=None) -> SamTextResult:
+        """fg_sam_parse on the SAM text data[offset : offset + n_bytes] (bytes, bytearray, memoryview or uint8 array;
+        by default all of it): lines, records, chunks, tokens, FLAG / POS, CIGAR runs and spans, cut on the device.
+        Offsets in the result are relative to the start of that window."""
+        buf = np.frombuffer(data, np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, np.uint8)
+        n = len(buf) - int(offset) if n_bytes is None else int(n_bytes)
+        if offset < 0 or n < 0 or offset + n > len(buf):
+            raise ValueError("sam_parse: the window leaves the buffer")
+        b = SamText()
+        t0 = time.perf_counter()
+        self._check(self.L.fg_sam_parse(self.h, buf.ctypes.data + int(offset) if n else None, n, C.byref(b)))
+        self.last_sam_seconds = time.perf_counter() - t0
+        self.sam_parse_calls = getattr(self, "sam_parse_calls", 0) + 1
+        nr, nu = int(b.n_records), int(b.n_runs)
+        size = dict(chunk_off=int(b.n_chunks) + 1, run_off=nr + 1, run_op=nu, run_len=nu)
+        dtype = {name: np.dtype(t._type_) for name, t in SamText._fields_ if name in SamTextResult.ARRAYS}
+        take = lambda ptr, n, dt: np.ctypeslib.as_array(ptr, (n,)).copy() if n else np.zeros(0, dt)
+        res = SamTextResult(buf[int(offset):int(offset) + n], n_lines=int(b.n_lines), n_records=nr, n_chunks=int(b.n_chunks), n_runs=nu,
+                            **{k: take(getattr(b, k), size.get(k, nr), dtype[k]) for k in SamTextResult.ARRAYS})
+        self.L.fg_release_sam_text(C.byref(b))
+        return res
 
     def kernel_times(self):
         arr = (KernelTime * 64)()
@@ -2882,12 +2943,12 @@ class DivergenceFinder:
                                                                    for label, fmt, value, end in rows)
 
     def find_divergence(self, alignment_path, contigs_path, contigs_info, frequency_path, positions_path, div_sum_path,
-                        sub_thresh, del_thresh, ins_thresh):
+                        sub_thresh, del_thresh, ins_thresh, device_text=False):
         """-> mean_aln_error = sum(err_rate) / (n + 1), which the reference logs.  contigs_info maps contig id to a record
         with length."""
         if not os.path.isfile(alignment_path) or not os.path.isfile(contigs_path):
             raise ValueError("_get_median() arg is an empty sequence")
-        sam = SamAlignments(self.ctx, alignment_path, self.read_fasta(contigs_path), self.max_read_coverage)
+        sam = SamAlignments(self.ctx, alignment_path, self.read_fasta(contigs_path), self.max_read_coverage, device_text=device_text)
         chunks = sam.chunks()
         Contig = collections.namedtuple("Contig", ["id", "length"])
         contigs = [Contig(cid, contigs_info[cid].length) for cid, _ in chunks]
@@ -2912,12 +2973,13 @@ class DivergenceFinder:
         return self.result
 
     def find_divergence_sam(self, alignment_path, contigs_path, contigs_info, frequency_path, positions_path, div_sum_path,
-                            sub_thresh, del_thresh, ins_thresh):
+                            sub_thresh, del_thresh, ins_thresh, device_text=False):
         """find_divergence on profile_sam: the same three files and the same return value.  A contig's positions are
         those of the bytes read from contigs_path, which is where the reference's contigs_info has its lengths from."""
         if not os.path.isfile(alignment_path) or not os.path.isfile(contigs_path):
             raise ValueError("_get_median() arg is an empty sequence")
-        sam = SamAlignments(self.ctx, alignment_path, self.read_fasta(contigs_path), self.max_read_coverage, want_cols=False)
+        sam = SamAlignments(self.ctx, alignment_path, self.read_fasta(contigs_path), self.max_read_coverage, want_cols=False,
+                            device_text=device_text)
         Contig = collections.namedtuple("Contig", ["id", "length"])
         contigs = [Contig(cid, contigs_info[cid].length) for cid, _ in sam.chunks()]
         res = self.profile_sam(sam, contigs, sub_thresh, del_thresh, ins_thresh)
@@ -3137,14 +3199,15 @@ class ReadPartitioner:
                         for h, (st, edge, top, total) in zip(headers_to_id, res.reads(j))])
         return out
 
-    def _read_records(self, alignment, target_path):
+    def _read_records(self, alignment, target_path, device_text=False):
         """-> ([records per chunk], the consensus bytes the first chunk lies on)"""
-        sam = SamAlignments(self.ctx, alignment, DivergenceFinder.read_fasta(target_path), self.max_read_coverage, want_cols=False)
+        sam = SamAlignments(self.ctx, alignment, DivergenceFinder.read_fasta(target_path), self.max_read_coverage, want_cols=False,
+                            device_text=device_text)
         chunks = sam.chunks()
         return [recs for _, recs in chunks], sam.contigs[chunks[0][0].encode("latin-1")] if chunks else b""
 
     def partition_reads_sam(self, edges, it, side, position_path, cons_align_path, template, read_align_path, consensuses,
-                            confirmed_pos_path, part_file, headers_to_id):
+                            confirmed_pos_path, part_file, headers_to_id, device_text=False):
         """partition_reads with the read SAM files read without columns and scored by classify_sam; the consensus SAM
         files are read as there and go through confirm.  The same two files."""
         skip = False
@@ -3154,7 +3217,7 @@ class ReadPartitioner:
             if not os.path.isfile(cons_align_path.format(it, side, edge_id)):
                 skip = True
             else:
-                cons_aligns[edge_id] = self._read_alignment(cons_align_path.format(it, side, edge_id), template)
+                cons_aligns[edge_id] = self._read_alignment(cons_align_path.format(it, side, edge_id), template, device_text)
             if skip or not cons_aligns or not cons_aligns[edge_id] or not cons_aligns[edge_id][0]:
                 skip = True
         if skip:
@@ -3173,7 +3236,7 @@ class ReadPartitioner:
                 skip = True
             elif not skip:
                 read_aligns[edge_id], edge_seqs[edge_id] = self._read_records(read_align_path.format(it, side, edge_id),
-                                                                              consensuses[(it, side, edge_id)])
+                                                                              consensuses[(it, side, edge_id)], device_text)
             if skip or not read_aligns or not read_aligns[edge_id] or not read_aligns[edge_id][0]:
                 skip = True
         if skip:
@@ -3182,12 +3245,13 @@ class ReadPartitioner:
             partitioning, = self.classify_sam([(read_aligns, consensus_pos, headers_to_id, edge_seqs)])
         self._write_partitioning_file(partitioning, part_file.format(it, side))
 
-    def _read_alignment(self, alignment, target_path):
-        sam = SamAlignments(self.ctx, alignment, DivergenceFinder.read_fasta(target_path), self.max_read_coverage)
+    def _read_alignment(self, alignment, target_path, device_text=False):
+        sam = SamAlignments(self.ctx, alignment, DivergenceFinder.read_fasta(target_path), self.max_read_coverage,
+                            device_text=device_text)
         return [alns for _, alns in sam.chunks()]
 
     def partition_reads(self, edges, it, side, position_path, cons_align_path, template, read_align_path, consensuses,
-                        confirmed_pos_path, part_file, headers_to_id):
+                        confirmed_pos_path, part_file, headers_to_id, device_text=False):
         skip = False
         pos = self.read_positions(position_path)
         cons_aligns = {}
@@ -3195,7 +3259,7 @@ class ReadPartitioner:
             if not os.path.isfile(cons_align_path.format(it, side, edge_id)):
                 skip = True
             else:
-                cons_aligns[edge_id] = self._read_alignment(cons_align_path.format(it, side, edge_id), template)
+                cons_aligns[edge_id] = self._read_alignment(cons_align_path.format(it, side, edge_id), template, device_text)
             if skip or not cons_aligns or not cons_aligns[edge_id] or not cons_aligns[edge_id][0]:
                 skip = True
         if skip:
@@ -3213,7 +3277,8 @@ class ReadPartitioner:
             if not os.path.isfile(read_align_path.format(it, side, edge_id)) or not os.path.isfile(consensuses[(it, side, edge_id)]):
                 skip = True
             elif not skip:
-                read_aligns[edge_id] = self._read_alignment(read_align_path.format(it, side, edge_id), consensuses[(it, side, edge_id)])
+                read_aligns[edge_id] = self._read_alignment(read_align_path.format(it, side, edge_id), consensuses[(it, side, edge_id)],
+                                                               device_text)
             if skip or not read_aligns or not read_aligns[edge_id] or not read_aligns[edge_id][0]:
                 skip = True
         if skip:
@@ -3243,18 +3308,26 @@ class SamAlignments:
     Python 3 refuses).  Raises ValueError where the reference raises AlignmentException("Alignment file is not sorted").
     want_cols=False expands without columns (err_rate and the scalars only) and keeps, per record, a SamRecord with the
     runs and the SEQ bytes where want_cols=True builds an Alignment with the two gapped strings: what
-    ContigConsensus.consensus_sam and BubbleMaker.make_sam / polish_sam hand to the fused device calls."""
+    ContigConsensus.consensus_sam and BubbleMaker.make_sam / polish_sam hand to the fused device calls.
+    device_text=True tokenises on the device instead: the file's bytes make ONE fg_sam_parse, and the chunks, the
+    filters, the cut, the runs and the SEQ bytes come from its arrays; what stays in Python is the unsorted test over the
+    chunk names, the seeded shuffle (a permutation of the chunk's record count), int() on a FLAG or POS the device could
+    not read, and the loop of the cut.  Records, order and exceptions are those of the host tokeniser.  The default stays
+    False: a stand-in context without a device (one that restates expand_cigars alone) still serves the host tokeniser."""
 
     HEADERS = (b"@PG", b"@HD", b"@SQ", b"@RG", b"@CO")
 
-    def __init__(self, ctx, sam_path, contigs, max_coverage=None, use_secondary=False, want_cols=True):
+    def __init__(self, ctx, sam_path, contigs, max_coverage=None, use_secondary=False, want_cols=True, device_text=False):
         self.ctx = ctx
         self.max_coverage, self.use_secondary, self.want_cols = max_coverage, use_secondary, bool(want_cols)
         as_bytes = lambda x: x if isinstance(x, bytes) else x.encode("latin-1")
         self.contigs = {as_bytes(h): as_bytes(s) for h, s in contigs.items()}
         opener = gzip.open if sam_path.endswith(".gz") else open
         with opener(sam_path, "rb") as f:
-            self._chunks = self._parse(self._file_chunks(f))
+            if device_text:
+                self._chunks = self._finish(*self._select_device(f.read()))
+            else:
+                self._chunks = self._parse(self._file_chunks(f))
 
     @classmethod
     def _file_chunks(cls, lines):
@@ -3316,21 +3389,84 @@ class SamAlignments:
                 if self.max_coverage is not None and sequence_length // contig_length > self.max_coverage:
                     break
             kept.append(recs)
+        return self._finish([contig for contig, _ in file_chunks], kept)
+
+    @staticmethod
+    def _gather(arrays, off, length, sel):
+        """(offsets, [pieces of each array side by side]): the pieces off[i] .. off[i] + length[i], i in sel"""
+        a, n = off[sel].astype(np.int64), length[sel].astype(np.int64)
+        cuts = list(zip(a.tolist(), (a + n).tolist()))
+        return np.concatenate([np.zeros(1, np.int64), np.cumsum(n)]), \
+            [np.concatenate([x[lo:hi] for lo, hi in cuts]) if cuts else np.zeros(0, x.dtype) for x in arrays]
+
+    def _select_device(self, data):
+        """_file_chunks and the selection of _parse from the arrays of ONE fg_sam_parse -> (chunk names, kept, text)"""
+        t = self.ctx.sam_parse(data)
+        off = t.chunk_off.astype(np.int64).tolist()
+        names = [t.token(off[c], "tab_rname") for c in range(t.n_chunks)]
+        seen = set()
+        for name in names:                          # neighbours differ, so "processed" is every chunk name before
+            if name in seen:
+                raise ValueError("Alignment file is not sorted")
+            seen.add(name)
+        status, flag, pos = t.status.tolist(), t.flag.tolist(), t.pos.tolist()
+        span = (t.qry_end - t.qry_start).tolist()
+        kept = []
+        for c, contig in enumerate(names):
+            order = list(range(off[c], off[c + 1]))
+            random.Random(42).shuffle(order)
+            sequence_length, recs = 0, []
+            for i in order:
+                st = status[i]
+                if st & t.FEW_TOKENS:
+                    continue
+                flags = int(t.token(i, "line").split()[1]) if st & t.BAD_FLAG else flag[i]
+                if flags & 0x4:
+                    continue
+                if flags & 0x100 and not self.use_secondary:
+                    continue
+                if st & t.NO_SEQ:
+                    raise Exception("Error parsing SAM: record without read sequence")
+                if st & t.RUN_OVERFLOW:
+                    cigar_parse(t.token(i, "cigar"))            # raises what the host tokeniser raises here
+                ops, lens = t.runs(i)
+                tokens = {0: t.token(i, "qname"), 2: t.token(i, "rname"), 3: t.token(i, "line").split()[3] if st & t.BAD_POS else pos[i],
+                          9: None if self.want_cols else t.token(i, "seq"), "record": i}
+                recs.append((tokens, flags, ops, lens))
+                sequence_length += span[i]
+                contig_length = len(self.contigs[contig])
+                if self.max_coverage is not None and sequence_length // contig_length > self.max_coverage:
+                    break
+            kept.append(recs)
+        return names, kept, t
+
+    def _finish(self, names, kept, text=None):
+        """the kept records of every chunk through ONE fg_expand_cigars; text: the SamTextResult they index (their runs and
+        SEQ bytes are gathered from its arrays), None: they carry both"""
         flat = [r for recs in kept for r in recs]
         used = []
         for tokens, _, _, _ in flat:
             if tokens[2] not in used:
                 used.append(tokens[2])
         number = {h: i for i, h in enumerate(used)}
+        if text is None:
+            runs_and_reads = lambda: (np.cumsum([0] + [len(r[2]) for r in flat]),
+                                      np.concatenate([r[2] for r in flat]) if flat else np.zeros(0, np.uint8),
+                                      np.concatenate([r[3] for r in flat]) if flat else np.zeros(0, np.uint32),
+                                      np.cumsum([0] + [len(r[0][9]) for r in flat]), b"".join(r[0][9] for r in flat))
+        else:
+            def runs_and_reads():
+                sel = np.array([r[0]["record"] for r in flat], np.int64)
+                run_off, (run_op, run_len) = self._gather((text.run_op, text.run_len), text.run_off[:-1],
+                                                          np.diff(text.run_off.astype(np.int64)), sel)
+                read_off, (read_seq,) = self._gather((text.text,), text.seq_off, text.seq_len, sel)
+                return run_off, run_op, run_len, read_off, read_seq
         res = self.ctx.expand_cigars(
             np.cumsum([0] + [len(self.contigs[h]) for h in used]), b"".join(self.contigs[h] for h in used),
-            [number[r[0][2]] for r in flat], [int(r[0][3]) for r in flat], np.cumsum([0] + [len(r[2]) for r in flat]),
-            np.concatenate([r[2] for r in flat]) if flat else np.zeros(0, np.uint8),
-            np.concatenate([r[3] for r in flat]) if flat else np.zeros(0, np.uint32),
-            np.cumsum([0] + [len(r[0][9]) for r in flat]), b"".join(r[0][9] for r in flat), want_cols=self.want_cols)
+            [number[r[0][2]] for r in flat], [int(r[0][3]) for r in flat], *runs_and_reads(), want_cols=self.want_cols)
         self.result = res
         out, a = [], 0
-        for (contig, _), recs in zip(file_chunks, kept):
+        for contig, recs in zip(names, kept):
             alns = []
             for tokens, flags, ops, lens in recs:
                 if not self.want_cols:

@@ -1377,6 +1377,66 @@ struct fg_paf_text {
 int  fg_paf_parse(const char* text, uint64_t n_bytes, struct fg_paf_text* out);
 void fg_release_paf_text(struct fg_paf_text* b);
 
+/* The tokeniser in front of the SAM paths, on the device: what SynchronizedSamReader._read_file_chunk
+ * (flye/utils/sam_parser.py:168-213), the per-line part of get_chunk (:355-377) and the expression of :140 make of a
+ * whole SAM text, as arrays.  The context lends its device and stream only.  The text goes up once; the host walks none
+ * of it.  What needs a dictionary or Python's generator stays with the caller: name lookup, the "Alignment file is not
+ * sorted" test over the chunk names, the seeded shuffle, the coverage cut, the sort by read id.
+ * Lines: the text is split at 0x0A; the last line may lack it and a final 0x0A starts no further line.  Lines are
+ * numbered from 1 over all lines of the text.
+ * Records: a line is a record when its first three bytes are none of @PG @HD @SQ @RG @CO (a prefix test: "@PGx" is a
+ * header, a line of fewer than three bytes is none) and it holds at least three 0x09.  Every other line is dropped and
+ * counts nowhere.  Records come in file order.
+ * Chunks: the tab RNAME of a record is the bytes strictly between its second and third tab (may be empty).  A chunk is
+ * a maximal run of consecutive records with equal tab RNAME, compared by bytes with the record before, however many
+ * dropped lines lie between.
+ * Tokens: maximal runs of bytes outside {0x09, 0x0A, 0x0B, 0x0C, 0x0D, 0x20}, what bytes.strip().split() gives, numbered
+ * from 0 in the line; tokens 0 .. 10 matter.  A record with fewer than 11 tokens has status bit 0; it stays a record (it
+ * takes part in the reference's shuffle); its token fields, flag, pos and span are 0 and it has no runs.
+ * status, per record: bit 0 fewer than 11 tokens; bit 1 FLAG (token 1) / bit 2 POS (token 3) is not of the form
+ * [+-]?[0-9]+ or does not fit int32 -- the value is 0 and the caller does what Python's int() does on the bytes; bit 3
+ * SEQ (token 9) is the single byte '*'; bit 4 a CIGAR run length beyond uint32 (that run_len is 0).
+ * Runs: within CIGAR (token 5) byte i ends a run when it is one of MIDNSHP=X and byte i - 1 is a decimal digit; the
+ * length is the value of the maximal digit run that ends at i - 1 (leading zeros allowed); every other byte belongs to
+ * no run: re.findall(b"[0-9]+[MIDNSHP=X]"), the tokens of fg_cigar_parse.  N P = X are reported; refusing them stays
+ * with fg_expand_cigars.
+ * Span: qry_start = hard_left + soft_left and qry_end = (sum of M, I, S) + hard_left - (sum of S - soft_left), with
+ * hard_left the first run's length if it is H and soft_left the first non-H run's length if it is S (_parse_cigar
+ * :316-320): the coverage cut needs no walk over the runs.
+ * All offsets are 64-bit and relative to text; line_len leaves the 0x0A out.
+ * The text goes up in sub-batches of whole lines of at most FG_SAM_BATCH_BYTES bytes (environment, default and at most
+ * 2^30), found by one backward search for 0x0A from the budget; the device numbers bytes in 32 bits inside one.  It
+ * holds 27 words per line of a sub-batch.  FG_SAM_TILE (environment; a power of two in 256 .. 16384, default 4096, other
+ * values are rounded down into that set) is the bytes a workgroup takes; a switch for tests.  The result depends on
+ * neither.  fg_kernel_times afterwards reports the sums over the sub-batches.
+ * FG_ERR_ARG: NULL out; NULL text with n_bytes > 0.  FG_ERR_NOMEM: a line that alone exceeds FG_SAM_BATCH_BYTES (the
+ * message names the switch), or device memory.  After an error *out is all zero and the context stays usable.
+ * n_bytes = 0 or a text without records gives an empty batch (chunk_off = {0}, run_off = {0}). */
+struct fg_sam_text {
+	uint64_t  n_lines;         /* all lines of the text, dropped ones included */
+	uint64_t  n_records;
+	uint64_t  n_chunks;
+	uint64_t  n_runs;
+	uint64_t* chunk_off;       /* n_chunks + 1 offsets into the records */
+	uint64_t* line_no;         /* per record from here on: 1-based */
+	uint64_t* line_off;  uint32_t* line_len;
+	uint8_t*  status;
+	uint64_t* tab_rname_off;   uint32_t* tab_rname_len;
+	uint64_t* qname_off;       uint32_t* qname_len;     /* token 0 */
+	uint64_t* rname_off;       uint32_t* rname_len;     /* token 2 */
+	uint64_t* cigar_off;       uint32_t* cigar_len;     /* token 5 */
+	uint64_t* seq_off;         uint32_t* seq_len;       /* token 9 */
+	int32_t*  flag;            /* token 1 */
+	int32_t*  pos;             /* token 3 */
+	int64_t*  qry_start;  int64_t* qry_end;
+	uint64_t* run_off;         /* n_records + 1 offsets into the runs */
+	uint8_t*  run_op;          /* n_runs, ASCII */
+	uint32_t* run_len;         /* n_runs */
+	void*     owner_;
+};
+int  fg_sam_parse(fg_ctx* ctx, const char* text, uint64_t n_bytes, struct fg_sam_text* out);
+void fg_release_sam_text(struct fg_sam_text* b);
+
 #ifdef __cplusplus
 }
 #endif
